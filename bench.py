@@ -10,7 +10,10 @@ resident in HBM when the timed region starts.  Weak scaling: every rank processe
 collective; time = max over ranks between barrier + synchronize on both sides.
 
 Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel = implicit-GEMM MFMA kernel, per-launch HIP-event
-timing over the timed region) and `cpu_baseline` (the CPU oracle timed on the host cores) objects."""
+timing over the timed region).  A plain run does only that: set-up, warm-up, the timed steps, the line.  `--full` adds what takes
+runs of its own: `cpu_baseline` (the CPU oracle timed on the host cores), the fully instrumented steps behind `roofline.by_symbol` /
+`other_kernels` / `traffic`, the stage split, the latency, GeoWizard and training legs.  `--dump-outputs DIR` writes what the last
+timed step returned as DIR/<name>.npy (float32), for output-for-output comparison of two builds on identical seeded inputs."""
 import argparse
 import json
 import os
@@ -42,7 +45,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=8, help="images per rank per step")
     ap.add_argument("--res", default=None, help="R or HxW; default 768 (inference, configs[1]) / 576 (--train, configs[2])")
     ap.add_argument("--dtype", default=None, choices=["fp16", "bf16", "fp32"], help="default fp16 (inference, configs[1]) / bf16 (--train)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: CPU baseline, fully instrumented per-kernel steps "
+                    "(roofline.by_symbol / other_kernels / traffic), stage split, latency / GeoWizard / training legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned in its last step "
+                    "as DIR/<name>.npy (float32 / float64; at most 64 MB, a fixed seeded sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--detail", default=None, help="write a per-shape kernel table (TSV) to this path")
     ap.add_argument("--tiny", action="store_true", help="tiny configs (plumbing check only, not a valid benchmark)")
     ap.add_argument("--train", action="store_true", help="time the E2E-FT training step (BASELINE.json configs[2]) instead of inference")
@@ -65,10 +72,10 @@ def parse():
     ap.add_argument("--no-image-encoder", action="store_true", help="--geowizard: feed a CLIP image embedding as input instead of running ViT-L/14")
     ap.add_argument("--geowizard", action="store_true", help="time GeoWizard joint depth+normals 1-step inference (BASELINE.json configs[4]: "
                     "dual-latent UNet with cross-domain attention, 2 images per GPU by default) instead of Marigold depth")
-    ap.add_argument("--no-latency-leg", action="store_true", help="inference mode at N=1: skip the one-image 576x768 latency measurement (`latency_b1_576x768`)")
-    ap.add_argument("--no-geowizard-leg", action="store_true", help="inference mode at N=1: skip the GeoWizard measurement (`geowizard`: configs[4]'s per-GPU share, "
+    ap.add_argument("--no-latency-leg", action="store_true", help="--full, inference mode at N=1: skip the one-image 576x768 latency measurement (`latency_b1_576x768`)")
+    ap.add_argument("--no-geowizard-leg", action="store_true", help="--full, inference mode at N=1: skip the GeoWizard measurement (`geowizard`: configs[4]'s per-GPU share, "
                     "2 images at 768x768 with the CLIP image tower inside)")
-    ap.add_argument("--no-train-leg", action="store_true", help="inference mode at N=1: skip the E2E-FT training-step measurements "
+    ap.add_argument("--no-train-leg", action="store_true", help="--full, inference mode at N=1: skip the E2E-FT training-step measurements "
                     "that are appended to the JSON line as `train_step` (bf16 compute) and `train_step_fp32` (the reference recipe)")
     ap.add_argument("--plumbing-check", action="store_true", help="launcher / rendezvous / timing-reduction check without GPU work (gloo, CPU): "
                     "prints a line with value null; used by tests/test_distributed_cpu.py")
@@ -330,6 +337,8 @@ def run_train(args, rank, world, dev):
     ops.TIMER = None
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     assert torch.isfinite(loss).all(), "non-finite loss"
+    if args.dump_outputs and rank == 0:      # the last step's loss and a fixed sample of the fp32 master weights it updated
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "unet_weights_sample": dump_sample(opt.flat_param)})
     elapsed = D.max_over_ranks(elapsed, device=dev)
     peak_mem = torch.cuda.max_memory_allocated() / 2 ** 30
     exposed = opt.exchange_exposed_ms() if world > 1 else []
@@ -464,6 +473,8 @@ def run_geowizard(args, rank, world, dev):
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device=dev)
     ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"depth": out[0], "normal": out[1]})
     if args.graph:   # per-kernel durations from the same steps run eagerly after the timed region (a graph replay cannot be bracketed per kernel)
         pipe.enable_hip_graphs(False)
         ops.TIMER = timer
@@ -491,6 +502,30 @@ def run_geowizard(args, rank, world, dev):
                              "other_kernels": {"attn": {"ms_per_step": at["ms"] / args.steps, "tflops": at["flops"] / (at["ms"] * 1e-3) / 1e12 if at["ms"] else 0.0}}}}
         return line
     return None
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE = 2 ** 20      # elements kept of an output too large to write whole
+
+
+def dump_sample(t, seed=0):
+    """a fixed, seeded sample of a large tensor (flattened): the same indices in every run, so two builds compare element for element"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).to(flat.device)
+    return flat[idx]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor or number} -> path/<name>.npy, float32 (float64 for host scalars)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {n: (t.detach().float().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)) for n, t in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes over the %d byte limit" % (total, DUMP_LIMIT_BYTES)
+    for n, a in out.items():
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def write_detail(path, timer, steps):
@@ -637,7 +672,7 @@ def main():
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[args.dtype]
     timeline = []
     cpu_leg = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU leg runs FIRST (GPU idle), so that everything after its end marker is GPU work
         _mark(timeline, "cpu_baseline start (GPU idle)")
         try:
@@ -667,7 +702,7 @@ def main():
     _mark(timeline, "inference timed region start")
     # HIP events on the launch stream around every launch of the DOMINANT family (implicit GEMM) inside the timed region: that is what the
     # roofline is computed from.  The other kernels run un-instrumented here (two event records per launch cost ~2 us of stream time each:
-    # 2 x 1.1k launches per step) and are timed in `args.steps` extra, fully instrumented steps after the region.
+    # 2 x 1.1k launches per step) and are timed in `args.steps` extra, fully instrumented steps after the region (--full or --detail).
     timer = ops.KernelTimer(only={"igemm"})
     if not args.graph:
         ops.TIMER = timer
@@ -681,8 +716,11 @@ def main():
     ops.TIMER = None
     _mark(timeline, "inference timed region end")
     assert torch.isfinite(out.float()).all(), "non-finite depth output"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"depth": out})      # [B, H, W] in [0, 1]: 18.9 MB at batch 8, 768x768
     elapsed = D.max_over_ranks(elapsed, device=dev)
-    if args.graph:
+    extra_steps = args.full or bool(args.detail)       # the runs of their own behind the per-kernel figures
+    if args.graph and extra_steps:
         # a hipGraph replay cannot be bracketed per kernel: the roofline's kernel durations then come from the same K steps run
         # eagerly right after the timed region
         pipe.enable_hip_graphs(False)
@@ -692,15 +730,17 @@ def main():
         torch.cuda.synchronize()
         ops.TIMER = None
     ksum = timer.summary()
-    full = ops.KernelTimer()          # every instrumented launch: the other kernel families, the per-shape table
-    ops.TIMER = full
-    for _ in range(args.steps):
-        out = step()
-    torch.cuda.synchronize()
-    ops.TIMER = None
-    fsum = full.summary()
-    if args.detail and rank == 0:
-        write_detail(args.detail, full, args.steps)
+    full = None
+    if extra_steps:
+        full = ops.KernelTimer()          # every instrumented launch: the other kernel families, the per-shape table
+        ops.TIMER = full
+        for _ in range(args.steps):
+            out = step()
+        torch.cuda.synchronize()
+        ops.TIMER = None
+        fsum = full.summary()
+        if args.detail and rank == 0:
+            write_detail(args.detail, full, args.steps)
 
     if rank == 0:
         n_img = B * world * args.steps
@@ -710,23 +750,6 @@ def main():
         peak = PEAK_TF[args.dtype]
         lps = ig["launches"] / args.steps
         alg_bpl = ig["bytes"] / max(ig["launches"], 1)
-        symbols = by_symbol(full, args.steps)
-        traffic, traffic_source, traffic_note, pmc_other = pmc_traffic(kernel_mix(symbols), (B, R, args.dtype, args.tiny) == (8, 768, "fp16", False))
-        extra = {}
-        for k in ("attn", "attn512", "groupnorm"):
-            if k in fsum and fsum[k]["ms"] > 0:
-                kk = fsum[k]
-                extra[k] = dict(launches_per_step=kk["launches"] / args.steps, ms_per_step=kk["ms"] / args.steps,
-                                tflops=kk["flops"] / (kk["ms"] * 1e-3) / 1e12, gbs=kk["bytes"] / (kk["ms"] * 1e-3) / 1e9)
-        if "attn" in extra:
-            extra["attn"]["frac_of_mfma_peak"] = extra["attn"]["tflops"] / peak
-            pa = pmc_other.get("attn_fwd")
-            if pa:   # q, k, v read + out written once = the algorithmic bytes of an attention launch
-                extra["attn"]["hbm_bytes_per_launch_pmc"] = pa["hbm_bytes_per_launch"]
-        if "attn512" in extra:
-            extra["attn512"]["frac_of_mfma_peak"] = extra["attn512"]["tflops"] / peak
-        if "groupnorm" in extra:
-            extra["groupnorm"]["frac_of_hbm_peak"] = extra["groupnorm"]["gbs"] / HBM_PEAK_GBS
         line = {
             "metric": "images/sec (768x768, 1-step UNet fwd) full path: VAE encode + SD-v2 UNet @t=999 + VAE decode",
             "value": value, "unit": "images/s", "n_gpus": world, "world": world, "ranks": ranks, "rccl_ranks": world if world > 1 else 0,
@@ -739,32 +762,55 @@ def main():
                        "launch_mode": "hipGraph replay (one captured graph per batch shape)" if args.graph else "host launches",
                        **({"options": args.set_option} if args.set_option else {})},
             "roofline": {"bound": "mfma", "kernel": "igemm6_kernel (persistent, halo-patch 3x3 conv; ten launches also apply the GroupNorm + SiLU of their input) + igemm5_kernel (persistent) + igemm2_kernel + conv_in / conv_out kernels: implicit-GEMM conv/linear, all launches of the timed region",
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
+                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                          # `achieved` counts what the kernels MULTIPLY.  The 2x-upsample convolutions run as four 2x2 phase convolutions (4/9 of the reference
                          # formulation's multiply-adds); counted in the reference's formulation (SURVEY.md 8d's per-image GFLOP) the family does:
                          "achieved_reference_formulation": ig.get("flops_nominal", ig["flops"]) / (ig["ms"] * 1e-3) / 1e12 if ig["ms"] > 0 else 0.0,
                          "frac_reference_formulation": (ig.get("flops_nominal", ig["flops"]) / (ig["ms"] * 1e-3) / 1e12 / peak) if ig["ms"] > 0 else 0.0,
-                         "traffic_over_algorithmic": (traffic / alg_bpl) if traffic else None,
-                         "traffic_source": traffic_source, "traffic_note": traffic_note, "algorithmic_bytes_per_launch": alg_bpl,
+                         "algorithmic_bytes_per_launch": alg_bpl,
                          "launches_per_step": lps, "kernel_ms_per_step": ig["ms"] / args.steps,
                          "algorithmic_gflop_per_step": ig["flops"] / args.steps / 1e9,
-                         "instrumentation": "HIP events around the igemm launches only inside the timed region; `other_kernels` and `by_symbol` from %d extra, "
-                                            "fully instrumented steps right after it" % args.steps,
-                         "by_symbol": symbols, "other_kernels": extra, **plain_launch_fraction(symbols, peak)},
+                         "instrumentation": "HIP events around the igemm launches only inside the timed region"},
         }
-        try:   # stage split ("also report UNet-only"), measured after the timed region
-            st = pipe.stage_times_ms(rgb, repeats=3)
-            line["stages"] = {"ms_per_step": st, "unet_only_images_per_s": B * world / (st["unet"] * 1e-3),
-                              "note": "HIP events around VAE encode / UNet (+ v->x0) / VAE decode (+ head) of 3 extra steps on rank 0"}
-        except Exception as e:
-            line["stages"] = {"error": repr(e)}
+        if args.graph and full is None:       # nothing of the replayed steps was bracketed per kernel: no roofline without the eager steps of --full
+            line["roofline"] = None
+        if full is not None:
+            symbols = by_symbol(full, args.steps)
+            traffic, traffic_source, traffic_note, pmc_other = pmc_traffic(kernel_mix(symbols), (B, R, args.dtype, args.tiny) == (8, 768, "fp16", False))
+            extra = {}
+            for k in ("attn", "attn512", "groupnorm"):
+                if k in fsum and fsum[k]["ms"] > 0:
+                    kk = fsum[k]
+                    extra[k] = dict(launches_per_step=kk["launches"] / args.steps, ms_per_step=kk["ms"] / args.steps,
+                                    tflops=kk["flops"] / (kk["ms"] * 1e-3) / 1e12, gbs=kk["bytes"] / (kk["ms"] * 1e-3) / 1e9)
+            if "attn" in extra:
+                extra["attn"]["frac_of_mfma_peak"] = extra["attn"]["tflops"] / peak
+                pa = pmc_other.get("attn_fwd")
+                if pa:   # q, k, v read + out written once = the algorithmic bytes of an attention launch
+                    extra["attn"]["hbm_bytes_per_launch_pmc"] = pa["hbm_bytes_per_launch"]
+            if "attn512" in extra:
+                extra["attn512"]["frac_of_mfma_peak"] = extra["attn512"]["tflops"] / peak
+            if "groupnorm" in extra:
+                extra["groupnorm"]["frac_of_hbm_peak"] = extra["groupnorm"]["gbs"] / HBM_PEAK_GBS
+            line["roofline"].update({"traffic": traffic, "traffic_over_algorithmic": (traffic / alg_bpl) if traffic else None,
+                                     "traffic_source": traffic_source, "traffic_note": traffic_note,
+                                     "instrumentation": "HIP events around the igemm launches only inside the timed region; `other_kernels` and `by_symbol` from %d extra, "
+                                                        "fully instrumented steps right after it" % args.steps,
+                                     "by_symbol": symbols, "other_kernels": extra, **plain_launch_fraction(symbols, peak)})
+        if args.full:
+            try:   # stage split ("also report UNet-only"), measured after the timed region
+                st = pipe.stage_times_ms(rgb, repeats=3)
+                line["stages"] = {"ms_per_step": st, "unet_only_images_per_s": B * world / (st["unet"] * 1e-3),
+                                  "note": "HIP events around VAE encode / UNet (+ v->x0) / VAE decode (+ head) of 3 extra steps on rank 0"}
+            except Exception as e:
+                line["stages"] = {"error": repr(e)}
         if R in WORK_GF and not args.tiny:
             tot = sum(WORK_GF[R].values())
             line["config"]["algorithmic_tflop_per_image"] = tot / 1e3
             line["effective_tflops"] = value * tot / 1e3
         if cpu_leg is not None:
             line["cpu_baseline"] = cpu_leg
-        if world == 1 and not args.tiny and not args.no_latency_leg:
+        if args.full and world == 1 and not args.tiny and not args.no_latency_leg:
             # the one figure the reference publishes for this path (README.md:145-158): ONE 576x768 image.  Batch 1 is launch-bound on the
             # small UNet levels, so it is replayed from a captured hipGraph (bit-equal to the eager launches)
             try:
@@ -772,12 +818,13 @@ def main():
                 line["latency_b1_576x768"] = latency_leg(pipe, dev, dtype)
             except Exception as e:
                 line["latency_b1_576x768"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_geowizard_leg and not args.tiny:
+        if args.full and world == 1 and not args.no_geowizard_leg and not args.tiny:
             # BASELINE.json configs[4]'s per-GPU share (batch 16 on 8 GPUs = 2 images per GPU at 768x768): GeoWizard joint depth + normals with the
             # CLIP image tower inside the timed region, so that the driver's default run times it too
             try:
                 _mark(timeline, "geowizard leg start")
                 gargs = argparse.Namespace(**vars(args))
+                gargs.dump_outputs = None
                 gargs.batch, gargs.res, gargs.res_h, gargs.res_w, gargs.steps, gargs.warmup, gargs.graph, gargs.no_image_encoder = 2, 768, 768, 768, 10, 3, False, False
                 gw = run_geowizard(gargs, 0, 1, dev)
                 line["geowizard"] = {k: gw[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "steps", "warmup")}
@@ -785,7 +832,7 @@ def main():
                 line["geowizard"]["roofline"] = {k: gw["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "other_kernels")}
             except Exception as e:
                 line["geowizard"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_train_leg and not args.tiny:
+        if args.full and world == 1 and not args.no_train_leg and not args.tiny:
             # second part of BASELINE.json's metric ("...; E2E-FT step time"): configs[2], batch 32 at 576x576, one GPU - in the reference
             # recipe's precision (`--mixed_precision no`, training/scripts/train_marigold_e2e_ft_depth.sh:15) AND with bf16 compute over
             # fp32 master weights
@@ -799,6 +846,7 @@ def main():
                     torch.cuda.reset_peak_memory_stats()
                     _mark(timeline, "%s leg start" % key)
                     targs = argparse.Namespace(**vars(args))
+                    targs.dump_outputs = None
                     targs.dtype, targs.res, targs.steps, targs.warmup, targs.detail, targs.micro_batch, targs.accum, targs.grad_ckpt = tdt, 576, tsteps, twarm, None, None, None, ckpt
                     targs.res_h = targs.res_w = 576
                     t = run_train(targs, 0, 1, dev)

@@ -13,12 +13,12 @@ if [ "$2" != "notests" ]; then
 fi
 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$c -o p -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-train-leg --no-latency-leg --no-geowizard-leg > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$c -o p -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-train-leg --no-latency-leg --no-geowizard-leg > /dev/null 2>&1
 done
 python scripts/pmc_traffic.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE $O/${TAG}_pmc_hbm_traffic.json 6 > $O/${TAG}_pmc_traffic.log 2>&1
 cp $O/${TAG}_pmc_hbm_traffic.json profiles/${TAG}_pmc_hbm_traffic.json
-timeout 1500 python bench.py --steps 20 --warmup 5 --detail $O/${TAG}_bench_per_shape.tsv > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_inf -o p -- python bench.py --no-train-leg --no-cpu-baseline --no-latency-leg --no-geowizard-leg --steps 3 --warmup 1 > /dev/null 2>&1
+timeout 1500 python bench.py --full --steps 20 --warmup 5 --detail $O/${TAG}_bench_per_shape.tsv > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_inf -o p -- python bench.py --full --no-train-leg --no-cpu-baseline --no-latency-leg --no-geowizard-leg --steps 3 --warmup 1 > /dev/null 2>&1
 cp $(find /tmp/prof_inf -name "*kernel_stats.csv" | head -1) $O/${TAG}_rocprofv3_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_train -o p -- python bench.py --train --steps 2 --warmup 1 > /dev/null 2>&1
 cp $(find /tmp/prof_train -name "*kernel_stats.csv" | head -1) $O/${TAG}_train_rocprofv3_kernel_stats.csv

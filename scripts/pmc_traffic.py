@@ -4,7 +4,7 @@ Collect (on the GPU box; counters in their OWN runs, --kernel-trace only, as gpu
     cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
     for c in FETCH_SIZE WRITE_SIZE; do
       rocprofv3 --kernel-trace --pmc $c --output-format csv -d gpurun_out/pmc_$c -o p -- \\
-          python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-train-leg
+          python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-train-leg
     done
     python scripts/pmc_traffic.py gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE profiles/r01_pmc_hbm_traffic.json [steps_profiled]
 steps_profiled = the number of inference steps inside one profiled process (default 8 = 1 warm-up + 1 timed + 1 fully instrumented + 3 stage-timing steps
@@ -49,7 +49,7 @@ def main():
     fd, wd, out = sys.argv[1:4]
     steps = float(sys.argv[4]) if len(sys.argv) > 4 else 8.0
     fetch, write = load(fd, "FETCH_SIZE"), load(wd, "WRITE_SIZE")
-    res = {"steps_profiled": steps, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over `python bench.py --steps 1 --warmup 1 "
+    res = {"steps_profiled": steps, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over `python bench.py --full --steps 1 --warmup 1 "
                      "--no-cpu-baseline --no-train-leg` (B=8, 768x768, fp16), aggregated by scripts/pmc_traffic.py; counter unit KiB; FETCH_SIZE doubled "
                      "per MI355X_MICROARCH.md (gfx950 reports half of wide coalesced reads) - re-checked on gn_apply, whose read and write volumes are "
                      "equal by construction (raw FETCH / WRITE ratio recorded below)", "kernels": {}}

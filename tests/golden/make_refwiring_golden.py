@@ -1,4 +1,4 @@
-"""Generate tests/golden/refwiring_golden.pt — outputs and caller traces produced BY THE REFERENCE'S OWN CODE (run here, on CPU, from the
+"""Generate tests/golden/refwiring_golden*.pt (one fixture in parts of under 1 MiB: PARTS, load_fixture()) — outputs and caller traces produced BY THE REFERENCE'S OWN CODE (run here, on CPU, from the
 repo root: `python tests/golden/make_refwiring_golden.py`; needs /root/reference).
 
 What runs (all from the reference's source files where they lie, see tests/refimport.py; third-party leaf modules from tests/stubs):
@@ -192,15 +192,46 @@ def model_cases(ref):
     return out
 
 
+# the fixture is stored in parts of under 1 MiB each: {file: [(top-level key, sub-key or None), ...]}
+PARTS = {"refwiring_golden.pt": [("meta", None), ("model", None), ("marigold", None)],
+         "refwiring_golden_call.pt": [("marigold_call", None), ("geowizard", None)],
+         "refwiring_golden_train_depth.pt": [("train", "depth")],
+         "refwiring_golden_train_normals.pt": [("train", "normals")]}
+
+
+def load_fixture():
+    """the whole fixture {"meta", "model", "marigold", "marigold_call", "geowizard", "train"} from its parts"""
+    out = {}
+    for fn, keys in PARTS.items():
+        part = torch.load(os.path.join(HERE, fn), weights_only=False)
+        for key, sub in keys:
+            if sub is None:
+                out[key] = part[key]
+            else:
+                out.setdefault(key, {})[sub] = part[key][sub]
+    return out
+
+
+def save_fixture(out):
+    for fn, keys in PARTS.items():
+        part = {}
+        for key, sub in keys:
+            if sub is None:
+                part[key] = out[key]
+            else:
+                part.setdefault(key, {})[sub] = out[key][sub]
+        path = os.path.join(HERE, fn)
+        torch.save(part, path)
+        print("wrote", path, os.path.getsize(path), "bytes")
+
+
 def main():
     torch.set_num_threads(8)
     torch.manual_seed(0)
     with refimport.reference_modules() as ref:
         out = {"meta": {"stub_diffusers": ref.uses_stub_diffusers, "torch": torch.__version__},
                "model": model_cases(ref), "marigold": marigold_cases(ref), "marigold_call": marigold_call_cases(ref), "geowizard": geowizard_case(ref), "train": train_cases(ref)}
-    path = os.path.join(HERE, "refwiring_golden.pt")
-    torch.save(out, path)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    save_fixture(out)
 
 
 if __name__ == "__main__":

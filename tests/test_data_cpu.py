@@ -1,8 +1,7 @@
 """CPU tests of the training input pipeline pieces: MixedDataLoader pinned to the reference's own class (load.py imported with its
-four unavailable third-party imports stubbed — only names used at import time), synchronised flip, and the oracle's edge cases."""
+four unavailable third-party imports stubbed — only names used at import time — or its recorded draws), synchronised flip, and the oracle's edge cases."""
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -10,45 +9,23 @@ import torch
 
 from oracle import dataprep_ref
 
-REF = "/root/reference/training/dataloaders/load.py"
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_reference_pins as pins  # noqa: E402
 
 
-def _import_reference_load():
-    import importlib.util
-    stubs = {}
-    for name in ("torchvision", "torchvision.transforms", "PIL", "PIL.Image", "pandas", "cv2"):
-        if name not in sys.modules:
-            stubs[name] = types.ModuleType(name)
-    if "torchvision" in stubs:
-        stubs["torchvision"].transforms = stubs["torchvision.transforms"]
-    if "PIL" in stubs:
-        stubs["PIL"].Image = stubs["PIL.Image"]
-    sys.modules.update(stubs)
-    try:
-        spec = importlib.util.spec_from_file_location("ref_load", REF)
-        m = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(m)
-    finally:
-        for k in stubs:
-            sys.modules.pop(k, None)
-    return m
-
-
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
-@pytest.mark.parametrize("n1,n2,s1,s2", [(90, 10, 9, 1), (50, 50, 9, 1), (300, 7, 9, 1), (13, 200, 3, 2)])
+@pytest.mark.parametrize("n1,n2,s1,s2", pins.MIXED_CASES)
 def test_mixed_dataloader_matches_reference_class(n1, n2, s1, s2, capsys):
+    """the reference's own MixedDataLoader (load.py, run live where the reference tree is present, else its recorded draws:
+    tests/golden/reference_pins.pt) against the product's, same numpy seed"""
     from diffusion_e2e_ft_amd.data import MixedDataLoader
-    ref = _import_reference_load()
+    want = pins.pinned("mixed_dataloader")[pins.MIXED_CASES.index((n1, n2, s1, s2))]
     a, b = [("a", i) for i in range(n1)], [("b", i) for i in range(n2)]
-    np.random.seed(123)
-    want_loader = ref.MixedDataLoader(a, b, s1, s2)
-    want = list(want_loader)
     np.random.seed(123)
     got_loader = MixedDataLoader(a, b, s1, s2)
     got = list(got_loader)
-    assert got == want and len(got_loader) == len(want_loader) == len(got)
-    assert (got_loader.frac1, got_loader.frac2) == (want_loader.frac1, want_loader.frac2)
-    assert list(got_loader) != [] and len(list(got_loader)) == len(want)   # re-iterable, a fresh shuffle per epoch
+    assert got == [tuple(x) for x in want["order"]] and len(got_loader) == want["len"] == len(got)
+    assert (got_loader.frac1, got_loader.frac2) == (want["frac1"], want["frac2"])
+    assert list(got_loader) != [] and len(list(got_loader)) == len(want["order"])   # re-iterable, a fresh shuffle per epoch
 
 
 def test_mixed_dataloader_split_arithmetic():

@@ -1,8 +1,8 @@
 """CPU tests for test-time ensembling: the oracle restatement (oracle/ensemble_ref.py) is PINNED against outputs of the reference's
-own functions (tests/golden/ensemble_golden.pt, made by tests/golden/make_ensemble_golden.py) and against the live reference
-when /root/reference is present; plus the host-side algebra of diffusion_e2e_ft_amd.ensemble (Gram form of the pairwise term)."""
-import importlib.util
+own functions (tests/golden/ensemble_golden.pt, made by tests/golden/make_ensemble_golden.py) and against the reference's function itself
+(run live where the reference tree is present, else its recorded results); plus the host-side algebra of diffusion_e2e_ft_amd.ensemble (Gram form of the pairwise term)."""
 import os
+import sys
 import warnings
 
 import numpy as np
@@ -14,7 +14,8 @@ from oracle import ensemble_ref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = torch.load(os.path.join(HERE, "golden", "ensemble_golden.pt"))
-REF_DEPTH = "/root/reference/Marigold/marigold/util/ensemble.py"
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import make_reference_pins as pins  # noqa: E402
 
 
 @pytest.mark.parametrize("name", list(gc.ENSEMBLE_DEPTH_CASES))
@@ -34,16 +35,13 @@ def test_normals_oracle_matches_reference_golden(name, kw):
     assert torch.equal(pred, GOLD["normals"][name])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DEPTH), reason="reference tree not present")
 def test_depth_oracle_against_live_reference():
-    spec = importlib.util.spec_from_file_location("ref_ensemble_live", REF_DEPTH)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
+    """the reference's ensemble_depths run live where the reference tree is present, else its recorded results (tests/golden/reference_pins.pt)"""
+    want = pins.pinned("ensemble_depths")
     stack = gc.ensemble_depth_stack(n=6, H=21, W=30, seed=77)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for kw in ({}, dict(reduction="mean"), dict(max_res=16)):
-            a, u = m.ensemble_depths(stack.clone(), **kw)
+        for kw, (a, u) in zip(({}, dict(reduction="mean"), dict(max_res=16)), want):
             b, v = ensemble_ref.ensemble_depths_ref(stack.clone(), **kw)
             assert torch.equal(a, b) and torch.equal(u, v), kw
 

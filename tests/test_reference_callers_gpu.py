@@ -16,6 +16,7 @@ exist), every logged attribute read and call is made on libe2eft's modules with 
     give identical gradients.
 """
 import os
+import sys
 
 import pytest
 import torch
@@ -26,7 +27,9 @@ from oracle import config
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
-FX = torch.load(os.path.join(os.path.dirname(__file__), "golden", "refwiring_golden.pt"), weights_only=False)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_refwiring_golden  # noqa: E402
+FX = make_refwiring_golden.load_fixture()     # tests/golden/refwiring_golden*.pt
 TOL = 1e-3           # north_star: 1e-3 relative in strict fp32
 
 

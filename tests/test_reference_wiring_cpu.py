@@ -11,7 +11,8 @@ only part that stays "restated from the published diffusers 0.30.2 definitions")
   * the committed fixtures are what the reference's code produces today: tests/golden/refwiring_golden.pt is regenerated and compared,
     and the oracle-made tests/golden/model_golden.pt / train_golden.pt (which every GPU parity test checks the HIP path against) agree
     with the reference wiring to fp32 round-off.
-Skipped where /root/reference is absent (the GPU box); there the fixtures carry the pin."""
+Where the reference tree is absent the same assertions run against what its code produced when the fixtures were made
+(tests/golden/refwiring_golden*.pt, tests/golden/reference_pins.pt); where it is present, the fixtures are also checked against it."""
 import os
 import sys
 
@@ -20,11 +21,14 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
 import golden_cases as gc  # noqa: E402
+import make_reference_pins as pins  # noqa: E402
+import make_refwiring_golden  # noqa: E402
 import refimport  # noqa: E402
 from oracle import config, pipeline_ref, synth, unet_ref, vae_ref  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not refimport.reference_available(), reason="reference tree not present")
+LIVE = refimport.reference_available()
 TOL = 1e-5      # fp32 round-off between two orderings of the same arithmetic (measured 2e-6)
 
 
@@ -34,80 +38,77 @@ def rel(a, b):
 
 @pytest.fixture(scope="module")
 def ref():
+    """the reference's modules, imported from its source; None where the tree is absent (the recorded results stand in)"""
+    if not LIVE:
+        yield None
+        return
     with refimport.reference_modules() as r:
         yield r
 
 
 @pytest.fixture(scope="module")
-def gen(ref):
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_refwiring_golden as g
-    return g
+def gen():
+    return make_refwiring_golden
 
 
-def test_reference_unet_loads_oracle_state_dict_strictly(ref):
+@pytest.fixture(scope="module")
+def fx():
+    return make_refwiring_golden.load_fixture()
+
+
+def test_reference_unet_loads_oracle_state_dict_strictly():
     """key set and shapes of oracle.unet_param_shapes == the reference constructor's parameters (SD-v2 shape AND the full-size config)"""
-    for cfg in (config.TINY_UNET, config.TINY_GEOWIZARD_UNET):
-        unet = ref.UNet2DConditionModel(**refimport.ref_unet_kwargs(cfg))
-        want = {k: tuple(v.shape) for k, v in unet.state_dict().items()}
-        assert want == {k: tuple(v) for k, v in unet_ref.unet_param_shapes(cfg).items()}
-    with torch.device("meta"):
-        full = ref.UNet2DConditionModel(**refimport.ref_unet_kwargs(config.SD2_UNET))
-    want = {k: tuple(v.shape) for k, v in full.state_dict().items()}
-    assert want == {k: tuple(v) for k, v in unet_ref.unet_param_shapes(config.SD2_UNET).items()}
-    assert sum(p.numel() for p in full.parameters()) == 865_922_244            # SURVEY.md Appendix A
+    want = pins.pinned("unet_keys")
+    for name in ("TINY_UNET", "TINY_GEOWIZARD_UNET", "SD2_UNET"):
+        assert want[name] == {k: tuple(v) for k, v in unet_ref.unet_param_shapes(getattr(config, name)).items()}, name
+    assert want["SD2_UNET_numel"] == 865_922_244            # SURVEY.md Appendix A
 
 
-def test_reference_vae_blocks_load_oracle_state_dict_strictly(ref):
-    for cfg, n in ((config.TINY_VAE, None), (config.SD_VAE, 83_653_863)):
-        with torch.device("meta"):
-            vae = ref.AutoencoderKL(**refimport.ref_vae_kwargs(cfg))
-        want = {k: tuple(v.shape) for k, v in vae.state_dict().items()}
-        assert want == {k: tuple(v) for k, v in vae_ref.vae_param_shapes(cfg).items()}
+def test_reference_vae_blocks_load_oracle_state_dict_strictly():
+    want = pins.pinned("vae_keys")
+    for name, n in (("TINY_VAE", None), ("SD_VAE", 83_653_863)):
+        assert want[name] == {k: tuple(v) for k, v in vae_ref.vae_param_shapes(getattr(config, name)).items()}, name
         if n:
-            assert sum(p.numel() for p in vae.parameters()) == n
+            assert want[name + "_numel"] == n
 
 
-@pytest.mark.parametrize("hw,batch,ctx_len,per_sample_t", [((16, 16), 2, 2, False), ((20, 12), 2, 2, False), ((8, 8), 3, 77, True),
-                                                          ((9, 7), 1, 2, False)])
-def test_oracle_unet_equals_reference_wiring(ref, gen, hw, batch, ctx_len, per_sample_t):
+@pytest.mark.parametrize("hw,batch,ctx_len,per_sample_t", pins.UNET_CASES)
+def test_oracle_unet_equals_reference_wiring(hw, batch, ctx_len, per_sample_t):
     """unet_2d_condition.py:845-1221 incl. the forced-upsample path (:920-930,1185-1186) for latent sizes not divisible by 8"""
-    unet, _ = gen.build_models(ref)
+    want = pins.pinned("unet_wiring")[pins.UNET_CASES.index((hw, batch, ctx_len, per_sample_t))]
     x, ctx = gc.unet_inputs(hw, batch=batch, ctx_len=ctx_len, seed=8)
     t = torch.tensor([999, 500, 1][:batch]) if per_sample_t else 999
     with torch.no_grad():
-        want = unet(x, t, encoder_hidden_states=ctx).sample
         got = unet_ref.unet_forward(gc.tiny_unet_sd(), config.TINY_UNET, x, t, ctx)
     assert rel(got, want) < TOL
 
 
-def test_oracle_joint_attention_equals_reference_processor(ref, gen):
+def test_oracle_joint_attention_equals_reference_processor():
     """GeoWizard: XFormersJointAttnProcessor (attention.py:425-513) installed the way the reference installs it
     (enable_xformers_memory_efficient_attention -> CustomJointAttention.set_use_memory_efficient_attention_xformers), class embedding"""
-    unet, _ = gen.build_models(ref, geo=True)
-    procs = {type(m.processor).__name__ for m in unet.modules() if hasattr(m, "processor")}
-    assert "XFormersJointAttnProcessor" in procs
+    pin = pins.pinned("joint_attention")
+    assert "XFormersJointAttnProcessor" in pin["processors"]
+    want = pin["out"]
     x, ctx, cls = gc.geo_unet_inputs()
     with torch.no_grad():
-        want = unet(x, 999, encoder_hidden_states=ctx, class_labels=cls).sample
         got = unet_ref.unet_forward(gc.tiny_geo_sd(), config.TINY_GEOWIZARD_UNET, x, 999, ctx, class_labels=cls)
         plain = unet_ref.unet_forward(gc.tiny_geo_sd(), dict(config.TINY_GEOWIZARD_UNET, joint_attention=False), x, 999, ctx, class_labels=cls)
     assert rel(got, want) < TOL
     assert rel(plain, want) > 1e-3          # the joint keys matter: the test would notice a processor that was not installed
 
 
-def test_oracle_vae_equals_reference_blocks(ref, gen):
-    _, vae = gen.build_models(ref)
+def test_oracle_vae_equals_reference_blocks():
+    want = pins.pinned("vae_blocks")
     rgb, z = gc.vae_inputs()
     sd = gc.tiny_vae_sd()
     with torch.no_grad():
-        assert rel(vae_ref.quant_conv(sd, vae_ref.encoder_forward(sd, config.TINY_VAE, rgb)), vae.quant_conv(vae.encoder(rgb))) < TOL
-        assert rel(vae_ref.decoder_forward(sd, config.TINY_VAE, vae_ref.post_quant_conv(sd, z)), vae.decoder(vae.post_quant_conv(z))) < TOL
+        assert rel(vae_ref.quant_conv(sd, vae_ref.encoder_forward(sd, config.TINY_VAE, rgb)), want["moments"]) < TOL
+        assert rel(vae_ref.decoder_forward(sd, config.TINY_VAE, vae_ref.post_quant_conv(sd, z)), want["dec"]) < TOL
 
 
-def test_oracle_pipeline_equals_reference_single_infer_source(ref, gen):
-    """marigold_pipeline.py:372-538 run from source (depth, normals, 2-step DDIM) vs oracle.pipeline_ref"""
-    cases = gen.marigold_cases(ref)
+def test_oracle_pipeline_equals_reference_single_infer_source(ref, gen, fx):
+    """marigold_pipeline.py:372-538 run from source (depth, normals, 2-step DDIM; recorded: refwiring_golden.pt) vs oracle.pipeline_ref"""
+    cases = gen.marigold_cases(ref) if ref is not None else fx["marigold"]
     rgb, ctx = synth.synth_inputs(1, 64, 96, 2, 128, seed=3)
     usd, vsd = gc.tiny_unet_sd(), gc.tiny_vae_sd()
     with torch.no_grad():
@@ -124,18 +125,20 @@ def test_oracle_pipeline_equals_reference_single_infer_source(ref, gen):
     assert list(call["kwargs"]) == ["encoder_hidden_states"] and call["args"]["__seq__"][1]["__tensor__"].dim() == 0   # t: 0-dim int64 tensor
 
 
-def test_oracle_geowizard_equals_reference_single_infer_source(ref, gen):
-    case = gen.geowizard_case(ref)
+def test_oracle_geowizard_equals_reference_single_infer_source(ref, gen, fx):
+    case = gen.geowizard_case(ref) if ref is not None else fx["geowizard"]
     rgb, emb = gc.geo_pipe_inputs()
     with torch.no_grad():
         d, n = pipeline_ref.geowizard_infer_ref(gc.tiny_geo_sd(), config.TINY_GEOWIZARD_UNET, gc.tiny_vae_sd(), config.TINY_VAE,
                                                 rgb[:1], emb[:1], "indoor")
-    assert rel(d, case["depth"]) < TOL and rel(n, case["normal"]) < 5 * TOL
+    # unit normals: x / (|x| + 1e-5) amplifies round-off where |x| is small.  Against the recorded result (another host's fp32 convolutions)
+    # the normals get the bound of the unit-normal estimate below (measured 2.2e-5 - 3.8e-5 across thread counts on one host, 5.7e-5 on another)
+    assert rel(d, case["depth"]) < TOL and rel(n, case["normal"]) < (5 * TOL if ref is not None else 2e-4)
 
 
 @pytest.fixture(scope="module")
-def ref_train_cases(ref, gen):
-    return gen.train_cases(ref)
+def ref_train_cases(ref, gen, fx):
+    return gen.train_cases(ref) if ref is not None else fx["train"]
 
 
 @pytest.mark.parametrize("modality", ["depth", "normals"])
@@ -152,10 +155,10 @@ def test_oracle_train_step_equals_reference_step_body_source(ref_train_cases, mo
         assert rel(want["grads"][k], g) < 2e-4, k
 
 
-def test_committed_fixtures_are_what_the_reference_produces(ref, gen):
-    """refwiring_golden.pt is reproducible from the reference's code, and the oracle-made model / train goldens agree with it"""
-    fx = torch.load(os.path.join(HERE, "golden", "refwiring_golden.pt"), weights_only=False)
-    now = gen.model_cases(ref)
+def test_committed_fixtures_are_what_the_reference_produces(ref, gen, fx):
+    """refwiring_golden*.pt is reproducible from the reference's code (where its tree is present), and the oracle-made model / train goldens
+    agree with it"""
+    now = gen.model_cases(ref) if ref is not None else fx["model"]
     for k, v in now.items():
         assert rel(fx["model"][k], v) < 1e-6, k
     old = torch.load(os.path.join(HERE, "golden", "model_golden.pt"), weights_only=False)
@@ -167,6 +170,7 @@ def test_committed_fixtures_are_what_the_reference_produces(ref, gen):
         assert abs(float(tr_old[m]["loss"]) - float(fx["train"][m]["loss"])) < 1e-5 * abs(float(fx["train"][m]["loss"]))
         for k, g in fx["train"][m]["grads"].items():
             assert rel(tr_old[m]["grads"][k], g) < 2e-4, (m, k)
-    cases = gen.marigold_cases(ref)
-    for k in ("depth", "normals", "depth_2step"):
-        assert rel(fx["marigold"][k]["out"], cases[k]["out"]) < 1e-6
+    if ref is not None:
+        cases = gen.marigold_cases(ref)
+        for k in ("depth", "normals", "depth_2step"):
+            assert rel(fx["marigold"][k]["out"], cases[k]["out"]) < 1e-6
