@@ -1,0 +1,410 @@
+// normaleval.hip — surface-normal evaluation on the device: the arithmetic of DSINE's benchmark mode.
+//   per-pixel error  /root/reference/DSINE/utils/utils.py:150-158 (compute_normal_error): acos(clamp(cosine_similarity(pred, gt, dim=1), -1, 1))
+//                    * 180 / pi, fp32, in torch's order (each vector divided by max(|v|, 1e-8), then the dot product)
+//   accumulation     DSINE/projects/dsine/test.py:104-113: the errors of the valid pixels of every image, in (b, y, x) order, appended to one list
+//   metrics          DSINE/utils/utils.py:161-178 (compute_normal_metrics): mean, median, rmse and the shares below 5 / 7.5 / 11.25 / 22.5 / 30 deg
+// Update (HBM-bound): one pass over (pred, gt, mask) with arbitrary element strides writes the errors into a dense fp32 buffer (a masked-out pixel
+// gets +inf, which sorts above every valid value as an unsigned bit pattern) and reduces the update's totals over fixed per-block partials in a
+// fixed order (no atomics: bit-reproducible), then adds them to the running totals on the device.
+// Finalize: the exact median by a radix select on the fp32 bit patterns (11 / 11 / 10 bit digits, LDS histograms, one-block scans), the second
+// middle element of an even count from the last histogram or one unsigned-min pass, and the fp64 record.  Nothing is read back to the host: the
+// launch sequence is fixed and capturable in a graph; the kernels read the counts they need from device memory.
+#include "common.h"
+
+namespace e2eft {
+
+constexpr int NE_UBLK = 2048;         // update: partial blocks (at most: 8 blocks of 4 waves per CU)
+constexpr int NE_UTHREADS = 256;
+constexpr int NE_NTOT = 9;            // totals: int64 n, nan, count[5]; double sum, sumsq
+constexpr int NE_HBLK = 512;          // finalize: histogram / min partial blocks
+constexpr int NE_HTHREADS = 512;
+constexpr int NE_BINS = 2048;
+constexpr uint32_t NE_INF_BITS = 0x7f800000u;
+
+// select state in the workspace (8-byte words)
+//   0 active (n > 0 and no NaN)   1 rank of a inside the current prefix   2 prefix bits of a (after the last pass: a itself)
+//   3 b bits (valid when 4 == 0)  4 b still unknown: the min pass finds it   5 even n
+constexpr int NE_NSTATE = 8;
+
+struct NeLayout {
+    int64_t* upart;       // [NE_UBLK][NE_NTOT] update partials (counts as int64, sums as double bit patterns)
+    uint32_t* hpart;      // [NE_HBLK][NE_BINS] histogram partials
+    uint32_t* hsum;       // [NE_BINS] summed histogram
+    uint32_t* mpart;      // [NE_HBLK] min partials
+    int64_t* state;       // [NE_NSTATE]
+};
+
+static size_t ne_bytes() {
+    return (size_t)NE_UBLK * NE_NTOT * 8 + (size_t)NE_HBLK * NE_BINS * 4 + (size_t)NE_BINS * 4 + (size_t)NE_HBLK * 4 + NE_NSTATE * 8;
+}
+
+static NeLayout ne_layout(void* ws) {
+    NeLayout l;
+    char* p = (char*)ws;
+    l.upart = (int64_t*)p;
+    p += (size_t)NE_UBLK * NE_NTOT * 8;
+    l.state = (int64_t*)p;
+    p += NE_NSTATE * 8;
+    l.hpart = (uint32_t*)p;
+    p += (size_t)NE_HBLK * NE_BINS * 4;
+    l.hsum = (uint32_t*)p;
+    p += (size_t)NE_BINS * 4;
+    l.mpart = (uint32_t*)p;
+    return l;
+}
+
+__device__ __forceinline__ double ne_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t ne_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// torch.cosine_similarity (ATen: x / max(|x|, eps) per vector, then the product summed over the channel) -> clamp -> acos -> degrees, in fp32
+__device__ __forceinline__ float ne_angle(float p0, float p1, float p2, float g0, float g1, float g2) {
+    const float np_ = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(p0, p0), __fmul_rn(p1, p1)), __fmul_rn(p2, p2))), 1e-8f);
+    const float ng = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(g0, g0), __fmul_rn(g1, g1)), __fmul_rn(g2, g2))), 1e-8f);
+    const float a0 = __fdiv_rn(p0, np_), a1 = __fdiv_rn(p1, np_), a2 = __fdiv_rn(p2, np_);
+    const float b0 = __fdiv_rn(g0, ng), b1 = __fdiv_rn(g1, ng), b2 = __fdiv_rn(g2, ng);
+    float c = __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
+    if (c == c) c = fminf(fmaxf(c, -1.0f), 1.0f);             // torch.clamp propagates NaN; fminf / fmaxf alone would drop it
+    const float t = __fmul_rn(acosf(c), 180.0f);
+    return __fdiv_rn(t, 3.14159274101257324f);               // float(np.pi)
+}
+
+// update pass: pixel i of the update (row-major over b, y, x) -> err[i]; per-block totals into part[blockIdx.x]
+__global__ __launch_bounds__(NE_UTHREADS) void ne_update_kernel(e2eft_normal_eval_desc d, const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                const uint8_t* __restrict__ mask, float* __restrict__ err, int64_t* __restrict__ part) {
+    const int64_t hw = (int64_t)d.height * d.width, total = hw * d.batch;
+    double s = 0.0, ss = 0.0;
+    uint32_t cnt[7] = {0, 0, 0, 0, 0, 0, 0};                 // n, nan, < 5, < 7.5, < 11.25, < 22.5, < 30
+    auto pixel = [&](int64_t i, int64_t b, int32_t y, int32_t x) {
+        if (mask && !mask[b * d.mask_stride[0] + y * d.mask_stride[1] + x * d.mask_stride[2]]) {
+            err[i] = __int_as_float(NE_INF_BITS);
+            return;
+        }
+        const float* pp = pred + b * d.pred_stride[0] + y * d.pred_stride[2] + x * d.pred_stride[3];
+        const float* gp = gt + b * d.gt_stride[0] + y * d.gt_stride[2] + x * d.gt_stride[3];
+        const int64_t pc = d.pred_stride[1], gc = d.gt_stride[1];
+        const float t = ne_angle(pp[0], pp[pc], pp[2 * pc], gp[0], gp[gc], gp[2 * gc]);
+        err[i] = t;
+        cnt[0] += 1;
+        if (t != t) {
+            cnt[1] += 1;
+        } else {
+            s += (double)t;
+            ss += (double)t * (double)t;
+        }
+        cnt[2] += t < 5.0f;
+        cnt[3] += t < 7.5f;
+        cnt[4] += t < 11.25f;
+        cnt[5] += t < 22.5f;
+        cnt[6] += t < 30.0f;
+    };
+    if (total < 0x7fffffffLL) {                              // 32-bit index arithmetic (every realistic update)
+        const uint32_t uhw = (uint32_t)hw, uw = (uint32_t)d.width;
+        for (uint32_t i = blockIdx.x * NE_UTHREADS + threadIdx.x; i < (uint32_t)total; i += gridDim.x * NE_UTHREADS) {
+            const uint32_t b = i / uhw, r = i - b * uhw, y = r / uw;
+            pixel(i, b, (int32_t)y, (int32_t)(r - y * uw));
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * NE_UTHREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * NE_UTHREADS) {
+            const int64_t b = i / hw, r = i - b * hw;
+            const int32_t y = (int32_t)(r / d.width);
+            pixel(i, b, y, (int32_t)(r - (int64_t)y * d.width));
+        }
+    }
+    __shared__ double reds[NE_UTHREADS / 64][2];
+    __shared__ uint32_t redc[NE_UTHREADS / 64][7];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    s = ne_wave_sum(s);
+    ss = ne_wave_sum(ss);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) cnt[k] = ne_wave_sum(cnt[k]);
+    if (lane == 0) {
+        reds[wave][0] = s;
+        reds[wave][1] = ss;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) redc[wave][k] = cnt[k];
+    }
+    __syncthreads();
+    int64_t* o = part + (int64_t)blockIdx.x * NE_NTOT;
+    if (threadIdx.x < 7) {
+        int64_t v = 0;
+        for (int w = 0; w < NE_UTHREADS / 64; ++w) v += redc[w][threadIdx.x];
+        o[threadIdx.x] = v;
+    } else if (threadIdx.x < 9) {
+        const int k = threadIdx.x - 7;
+        double v = 0.0;
+        for (int w = 0; w < NE_UTHREADS / 64; ++w) v += reds[w][k];
+        o[threadIdx.x] = __double_as_longlong(v);
+    }
+}
+
+// the update's totals over its nblk partials in a fixed order (thread t takes partials t, t + 256, ...; then a fixed butterfly per wave and the four
+// waves in order), added to the running totals
+__global__ __launch_bounds__(256) void ne_update_reduce_kernel(int nblk, const int64_t* __restrict__ part, int64_t* __restrict__ totals) {
+    __shared__ int64_t redc[4][7];
+    __shared__ double reds[4][2];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int64_t c[7] = {0, 0, 0, 0, 0, 0, 0};
+    double s = 0.0, ss = 0.0;
+    for (int j = t; j < nblk; j += 256) {
+        const int64_t* p = part + (int64_t)j * NE_NTOT;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) c[k] += p[k];
+        s += __longlong_as_double(p[7]);
+        ss += __longlong_as_double(p[8]);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
+    s = ne_wave_sum(s);
+    ss = ne_wave_sum(ss);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) redc[wave][k] = c[k];
+        reds[wave][0] = s;
+        reds[wave][1] = ss;
+    }
+    __syncthreads();
+    if (t < 7) {
+        totals[t] += (redc[0][t] + redc[1][t]) + (redc[2][t] + redc[3][t]);
+    } else if (t < 9) {
+        const int k = t - 7;
+        const double v = (reds[0][k] + reds[1][k]) + (reds[2][k] + reds[3][k]);
+        totals[t] = __double_as_longlong(__longlong_as_double(totals[t]) + v);
+    }
+}
+
+// select setup: rank (n-1)/2 of the n valid values; nothing to select when n == 0 or a NaN is among them (the record is NaN)
+__global__ void ne_select_init_kernel(const int64_t* __restrict__ totals, int64_t* __restrict__ state) {
+    if (threadIdx.x != 0) return;
+    const int64_t n = totals[0], nan = totals[1];
+    state[0] = n > 0 && nan == 0;
+    state[1] = n > 0 ? (n - 1) / 2 : 0;
+    state[2] = 0;
+    state[3] = 0;
+    state[4] = 0;
+    state[5] = n > 0 && (n & 1) == 0;
+}
+
+// histogram of the WIDTH-bit digit (u >> SHIFT) over the values u < +inf whose bits from SHIFT + WIDTH up equal the prefix's
+template <int SHIFT, int WIDTH>
+__global__ __launch_bounds__(NE_HTHREADS) void ne_hist_kernel(int64_t m, const uint32_t* __restrict__ bits, const int64_t* __restrict__ state,
+                                                              uint32_t* __restrict__ hpart) {
+    __shared__ uint32_t h[NE_BINS];
+    for (int j = threadIdx.x; j < NE_BINS; j += NE_HTHREADS) h[j] = 0;
+    __syncthreads();
+    const bool active = state[0] != 0;
+    constexpr int HI = SHIFT + WIDTH;
+    const uint32_t prefix = (uint32_t)state[2];
+    if (active) {
+        auto take = [&](uint32_t u) {
+            if (u >= NE_INF_BITS) return;
+            if (HI < 32 && (u >> (HI & 31)) != (prefix >> (HI & 31))) return;
+            atomicAdd(&h[(u >> SHIFT) & ((1u << WIDTH) - 1)], 1u);
+        };
+        const int64_t m4 = m >> 2;
+        const u32x4* b4 = reinterpret_cast<const u32x4*>(bits);
+        for (int64_t i = (int64_t)blockIdx.x * NE_HTHREADS + threadIdx.x; i < m4; i += (int64_t)gridDim.x * NE_HTHREADS) {
+            const u32x4 v = b4[i];
+            take(v.x);
+            take(v.y);
+            take(v.z);
+            take(v.w);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (m & 3)) take(bits[m4 * 4 + threadIdx.x]);
+    }
+    __syncthreads();
+    uint32_t* o = hpart + (int64_t)blockIdx.x * NE_BINS;
+    for (int j = threadIdx.x; j < NE_BINS; j += NE_HTHREADS) o[j] = h[j];
+}
+
+// column sums of the histogram partials: block j owns 64 bins, its 16 waves take every 16th partial (integer sums: any order gives the same)
+__global__ __launch_bounds__(1024) void ne_hist_sum_kernel(int nblk, const uint32_t* __restrict__ hpart, uint32_t* __restrict__ hsum) {
+    __shared__ uint32_t red[16][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, bin = blockIdx.x * 64 + lane;
+    uint32_t v = 0;
+#pragma unroll 8
+    for (int j = wave; j < nblk; j += 16) v += hpart[(int64_t)j * NE_BINS + bin];
+    red[wave][lane] = v;
+    __syncthreads();
+    if (wave == 0) {
+        for (int w = 1; w < 16; ++w) v += red[w][lane];
+        hsum[bin] = v;
+    }
+}
+
+// one-block scan of the summed histogram: the digit that holds the current rank, the rank inside it, the new prefix.  After the last digit
+// (SHIFT == 0) the prefix is a; for an even count, b is a again when the bin holds the next rank, else the next non-empty bin, else the min pass.
+template <int SHIFT, int WIDTH>
+__global__ __launch_bounds__(1024) void ne_select_kernel(const uint32_t* __restrict__ hsum, int64_t* __restrict__ state) {
+    if (state[0] == 0) return;
+    __shared__ uint32_t wsum[16];
+    __shared__ int64_t pick[3];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) pick[0] = pick[1] = pick[2] = 0;              // (not reached while the counts are consistent)
+    const uint32_t c0 = hsum[2 * t], c1 = hsum[2 * t + 1];
+    uint32_t incl = c0 + c1;                                  // inclusive scan over the threads' bin pairs (counts fit 32 bits: m < 2^32 checked by the host)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    const uint32_t excl = before + incl - (c0 + c1);
+    __syncthreads();
+    const int64_t k = state[1];
+    if (k >= (int64_t)excl && k < (int64_t)excl + c0 + c1) {
+        const bool first = k < (int64_t)excl + c0;
+        const uint32_t dig = 2 * t + (first ? 0 : 1);
+        const int64_t r = k - excl - (first ? 0 : c0);
+        pick[0] = dig;
+        pick[1] = r;
+        pick[2] = first ? c0 : c1;
+    }
+    __syncthreads();
+    const uint32_t dig = (uint32_t)pick[0];
+    const uint32_t prefix = (uint32_t)state[2] | (dig << SHIFT);
+    if (SHIFT == 0 && state[5]) {
+        // b = rank k + 1: inside a's bin, or the first non-empty bin above it (a wave-wide search from thread 0's view), else unknown
+        __shared__ int next;
+        if (t == 0) next = NE_BINS;
+        __syncthreads();
+        if (c0 && 2 * t > (int)dig) atomicMin(&next, 2 * t);
+        else if (c1 && 2 * t + 1 > (int)dig) atomicMin(&next, 2 * t + 1);
+        __syncthreads();
+        if (t == 0) {
+            if (pick[1] + 1 < pick[2]) {
+                state[3] = prefix;
+                state[4] = 0;
+            } else if (next < NE_BINS) {
+                state[3] = (prefix & ~((1u << WIDTH) - 1)) | (uint32_t)next;
+                state[4] = 0;
+            } else {
+                state[4] = 1;
+            }
+        }
+    }
+    if (t == 0) {
+        state[1] = pick[1];
+        state[2] = prefix;
+    }
+}
+
+// b when it lies outside a's last histogram: the unsigned minimum of the values above a (and below +inf)
+__global__ __launch_bounds__(NE_HTHREADS) void ne_min_kernel(int64_t m, const uint32_t* __restrict__ bits, const int64_t* __restrict__ state,
+                                                             uint32_t* __restrict__ mpart) {
+    if (state[0] == 0 || state[4] == 0) return;
+    const uint32_t a = (uint32_t)state[2];
+    uint32_t mn = NE_INF_BITS;
+    for (int64_t i = (int64_t)blockIdx.x * NE_HTHREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * NE_HTHREADS) {
+        const uint32_t u = bits[i];
+        if (u > a && u < mn) mn = u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+    __shared__ uint32_t red[NE_HTHREADS / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < NE_HTHREADS / 64; ++w) mn = min(mn, red[w]);
+        mpart[blockIdx.x] = mn;
+    }
+}
+
+// the record [mean, median, rmse, a1..a5, n] (utils.py:167-177; NaN as numpy: a NaN error makes mean, median, rmse NaN, the a_i count it in n)
+__global__ __launch_bounds__(64) void ne_finish_kernel(int nblk, const int64_t* __restrict__ totals, const int64_t* __restrict__ state,
+                                                       const uint32_t* __restrict__ mpart, double* __restrict__ out) {
+    const int t = threadIdx.x;
+    uint32_t mn = NE_INF_BITS;
+    if (state[0] && state[4])
+        for (int j = t; j < nblk; j += 64) mn = min(mn, mpart[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+    if (t != 0) return;
+    const int64_t n = totals[0], nan = totals[1];
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double dn = (double)n;
+    double mean = qnan, median = qnan, rmse = qnan;
+    if (n > 0 && nan == 0) {
+        mean = __longlong_as_double(totals[7]) / dn;
+        rmse = sqrt(__longlong_as_double(totals[8]) / dn);
+        const float a = __uint_as_float((uint32_t)state[2]);
+        if (state[5]) {
+            const float b = __uint_as_float(state[4] ? mn : (uint32_t)state[3]);
+            median = (double)(__fmul_rn(__fadd_rn(a, b), 0.5f));     // np.median of float32: the float32 mean of the two middle values
+        } else {
+            median = (double)a;
+        }
+    }
+    out[0] = mean;
+    out[1] = median;
+    out[2] = rmse;
+    for (int k = 0; k < 5; ++k) out[3 + k] = n > 0 ? 100.0 * ((double)totals[2 + k] / dn) : qnan;
+    out[8] = dn;
+}
+
+}  // namespace e2eft
+
+using namespace e2eft;
+
+extern "C" size_t e2eft_normal_eval_workspace_bytes(void) { return ne_bytes(); }
+
+extern "C" int e2eft_normal_eval_update(const e2eft_normal_eval_desc* desc, const float* pred, const float* gt, const uint8_t* mask, float* err,
+                                        int64_t err_offset, int64_t err_capacity, int64_t* totals, void* workspace, size_t ws_bytes, void* stream) {
+    E2EFT_REQUIRE(desc && pred && gt && err && totals && workspace, "normal_eval_update: null pointer");
+    const e2eft_normal_eval_desc d = *desc;
+    E2EFT_REQUIRE(d.batch > 0 && d.height > 0 && d.width > 0, "normal_eval_update: shape %d x %d x %d", d.batch, d.height, d.width);
+    const int64_t total = (int64_t)d.batch * d.height * d.width;
+    E2EFT_REQUIRE(err_offset >= 0 && err_capacity >= 0 && err_offset <= err_capacity && total <= err_capacity - err_offset,
+                  "normal_eval_update: %lld errors at offset %lld exceed the capacity %lld", (long long)total, (long long)err_offset, (long long)err_capacity);
+    for (int k = 0; k < 4; ++k)
+        E2EFT_REQUIRE(d.pred_stride[k] >= 0 && d.gt_stride[k] >= 0, "normal_eval_update: negative stride");
+    for (int k = 0; k < 3; ++k) E2EFT_REQUIRE(d.mask_stride[k] >= 0, "normal_eval_update: negative mask stride");
+    const size_t need = ne_bytes();
+    if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "normal_eval_update: workspace %zu < %zu", ws_bytes, need);
+    E2EFT_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)totals & 7) == 0, "normal_eval_update: workspace must be 16-byte, totals 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const NeLayout l = ne_layout(workspace);
+    const int nblk = (int)(total / NE_UTHREADS + 1 < NE_UBLK ? total / NE_UTHREADS + 1 : NE_UBLK);
+    hipLaunchKernelGGL(ne_update_kernel, dim3(nblk), dim3(NE_UTHREADS), 0, s, d, pred, gt, mask, err + err_offset, l.upart);
+    hipLaunchKernelGGL(ne_update_reduce_kernel, dim3(1), dim3(256), 0, s, nblk, (const int64_t*)l.upart, totals);
+    return check_launch("normal_eval_update");
+}
+
+extern "C" int e2eft_normal_eval_finalize(const float* err, int64_t count, const int64_t* totals, double* out, void* workspace, size_t ws_bytes,
+                                          void* stream) {
+    E2EFT_REQUIRE(totals && out && workspace, "normal_eval_finalize: null pointer");
+    E2EFT_REQUIRE(count >= 0 && count < 0xffffffffLL, "normal_eval_finalize: count %lld out of range (< 2^32)", (long long)count);
+    E2EFT_REQUIRE(err || count == 0, "normal_eval_finalize: null error buffer");
+    E2EFT_REQUIRE(((uintptr_t)err & 15) == 0, "normal_eval_finalize: error buffer must be 16-byte aligned");
+    const size_t need = ne_bytes();
+    if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "normal_eval_finalize: workspace %zu < %zu", ws_bytes, need);
+    E2EFT_REQUIRE(((uintptr_t)workspace & 15) == 0, "normal_eval_finalize: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const NeLayout l = ne_layout(workspace);
+    const uint32_t* bits = (const uint32_t*)err;
+    hipLaunchKernelGGL(ne_select_init_kernel, dim3(1), dim3(64), 0, s, totals, l.state);
+    hipLaunchKernelGGL((ne_hist_kernel<21, 11>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
+    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
+    hipLaunchKernelGGL((ne_select_kernel<21, 11>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
+    hipLaunchKernelGGL((ne_hist_kernel<10, 11>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
+    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
+    hipLaunchKernelGGL((ne_select_kernel<10, 11>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
+    hipLaunchKernelGGL((ne_hist_kernel<0, 10>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
+    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
+    hipLaunchKernelGGL((ne_select_kernel<0, 10>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
+    hipLaunchKernelGGL(ne_min_kernel, dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.mpart);
+    hipLaunchKernelGGL(ne_finish_kernel, dim3(1), dim3(64), 0, s, NE_HBLK, totals, (const int64_t*)l.state, l.mpart, out);
+    return check_launch("normal_eval_finalize");
+}

@@ -5,6 +5,12 @@ for whole batches in one launch sequence (csrc/evalmetrics.hip), instead of nump
   align_depth_least_square   same name and return convention as the reference's function, torch tensors on the device
   depth_metrics              per-image metric table (dict name -> tensor [B]) and its mean, named as eval.py's metric functions
   MetricTracker              running averages keyed by metric name (the reference's pandas-backed tracker, metric.py:9-31)
+
+Surface normals (DSINE's benchmark mode, csrc/normaleval.hip), named as DSINE/utils/utils.py names them:
+  normal_error               compute_normal_error (utils.py:150-158): per-pixel angular error in degrees, [B,1,H,W] fp32
+  normal_metrics             compute_normal_metrics(compute_normal_error(pred, gt)[mask]) (utils.py:161-178) in one call
+  NormalMetricAccumulator    the accumulation loop of DSINE/projects/dsine/test.py:104-133 without the torch.cat per image or the host round trip
+  format_normal_metrics      the two lines test.py prints and writes to metrics.txt
 """
 import torch
 
@@ -83,3 +89,145 @@ class MetricTracker:
 
     def result(self):
         return {k: self.avg(k) for k in self._tot if self._cnt[k]}
+
+
+NORMAL_METRIC_NAMES = ("mean", "median", "rmse", "a1", "a2", "a3", "a4", "a5")
+NORMAL_METRIC_HEADER = "mean median rmse 5 7.5 11.25 22.5 30"
+
+
+def _normals4(t, name):
+    """[B,3,H,W] or [3,H,W] device tensor -> fp32 [B,3,H,W] view (any strides: a permuted [H,W,3] array is read in place)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a device tensor" % name)
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise ValueError("%s: expected normals [B,3,H,W] or [3,H,W]; got shape %s" % (name, tuple(t.shape)))
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _normal_mask(mask, B, H, W):
+    """[B,1,H,W] / [B,H,W] / [H,W] bool or uint8 -> uint8 [B,H,W] view (None stays None: every pixel counts)"""
+    if mask is None:
+        return None
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("mask must be bool or uint8, got %s" % mask.dtype)
+    if mask.dim() == 4:
+        if mask.shape[1] != 1:
+            raise ValueError("mask: expected [B,1,H,W]; got shape %s" % (tuple(mask.shape),))
+        mask = mask[:, 0]
+    if mask.dim() == 2:
+        mask = mask.unsqueeze(0)
+    if tuple(mask.shape) != (B, H, W):
+        raise ValueError("mask shape %s does not match the normals' %s" % (tuple(mask.shape), (B, H, W)))
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _check_pair(pred, gt):
+    pred, gt = _normals4(pred, "pred"), _normals4(gt, "gt")
+    if pred.shape != gt.shape:
+        raise ValueError("pred %s and gt %s differ in shape" % (tuple(pred.shape), tuple(gt.shape)))
+    return pred, gt
+
+
+@torch.no_grad()
+@ops.tensor_scoped
+def normal_error(pred, gt):
+    """utils.py:150-158 compute_normal_error: acos(clamp(cosine_similarity(pred, gt, dim=1), -1, 1)) * 180 / pi -> [B,1,H,W] fp32 degrees"""
+    pred, gt = _check_pair(pred, gt)
+    B, _, H, W = pred.shape
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=pred.device)
+    totals = torch.zeros((9,), dtype=torch.int64, device=pred.device)
+    ws, nws = ops.normal_eval_workspace(pred.device)
+    ops.normal_eval_update(pred, gt, None, out, 0, totals, ws, nws)
+    return out
+
+
+@torch.no_grad()
+@ops.tensor_scoped
+def normal_metrics(pred, gt, mask=None):
+    """compute_normal_metrics(compute_normal_error(pred, gt)[mask]) (utils.py:150-178) -> dict (NORMAL_METRIC_NAMES + "n"); None when no pixel is valid"""
+    acc = NormalMetricAccumulator()
+    acc.update(pred, gt, mask)
+    return acc.result()
+
+
+class NormalMetricAccumulator:
+    """DSINE/projects/dsine/test.py:104-133 on the device: update() per image (batch) appends the errors of its valid pixels — to a dense buffer that
+    doubles when full, in the reference's order — and adds its totals on the device; result_tensor() finalizes (exact median) without a host read.
+    The host knows how many errors each update writes (B * H * W), so nothing is read back to grow the buffer; H x W may change between updates."""
+
+    def __init__(self, device=None, capacity=0):
+        self._device = torch.device(device) if device is not None else None
+        self._cap0 = int(capacity)
+        self._err = None
+        self._written = 0
+        self._totals = None
+        self._ws = None
+
+    def _ensure(self, device, need):
+        if self._totals is None:
+            self._device = device
+            self._totals = torch.zeros((9,), dtype=torch.int64, device=device)
+            self._ws, self._nws = ops.normal_eval_workspace(device)
+        elif device != self._totals.device:
+            raise RuntimeError("NormalMetricAccumulator lives on %s, got a tensor on %s" % (self._totals.device, device))
+        cap = 0 if self._err is None else self._err.numel()
+        if self._written + need > cap:
+            new = torch.empty((max(2 * cap, self._written + need, self._cap0),), dtype=torch.float32, device=device)
+            if self._written:
+                new[:self._written].copy_(self._err[:self._written])
+            self._err = new
+
+    def reset(self):
+        """forget every update (buffer and workspace are kept); capturable"""
+        self._written = 0
+        if self._totals is not None:
+            self._totals.zero_()
+
+    @torch.no_grad()
+    @ops.tensor_scoped
+    def update(self, pred, gt, mask=None):
+        """pred, gt: [B,3,H,W] or [3,H,W] device tensors (any strides); mask: [B,1,H,W] / [B,H,W] / [H,W] bool or uint8, None = all valid.
+        No host synchronisation."""
+        pred, gt = _check_pair(pred, gt)
+        B, _, H, W = pred.shape
+        mask = _normal_mask(mask, B, H, W)
+        n = B * H * W
+        self._ensure(pred.device, n)
+        ops.normal_eval_update(pred, gt, mask, self._err, self._written, self._totals, self._ws, self._nws)
+        self._written += n
+
+    @property
+    def pixels(self):
+        """pixels seen so far (valid or not): the number of entries of the error buffer in use"""
+        return self._written
+
+    def result_tensor(self):
+        """fp64 [9] device tensor: mean, median, rmse, a1..a5, n (NaN metrics when n == 0); no host read"""
+        if self._totals is None:
+            dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._ensure(dev, 0)
+        with ops.on_device_of(self._totals):
+            return ops.normal_eval_finalize(self._err, self._written, self._totals, self._ws, self._nws)
+
+    def result(self):
+        """dict of python floats (NORMAL_METRIC_NAMES) plus "n"; None when no valid pixel was seen (test.py's "No normal errors" branch)"""
+        r = self.result_tensor().cpu().tolist()
+        if r[8] == 0:
+            return None
+        out = dict(zip(NORMAL_METRIC_NAMES, r[:8]))
+        out["n"] = int(r[8])
+        return out
+
+    def errors(self):
+        """1-D fp32 device tensor of the valid pixels' errors in update order: the reference's total_normal_errors"""
+        if self._err is None:
+            return torch.empty((0,), dtype=torch.float32, device=self._device)
+        e = self._err[:self._written]
+        return e[e != float("inf")]
+
+
+def format_normal_metrics(m):
+    """the header line and the "%.3f" x 8 line test.py:117-120 prints (and writes to metrics.txt, :126-129)"""
+    return NORMAL_METRIC_HEADER + "\n" + "%.3f %.3f %.3f %.3f %.3f %.3f %.3f %.3f" % tuple(m[k] for k in NORMAL_METRIC_NAMES)

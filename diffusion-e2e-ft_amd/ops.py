@@ -1572,3 +1572,36 @@ def depth_eval(pred, gt, mask, disparity=False, align_max_res=0, min_depth=1e-3,
     check(lib.e2eft_depth_eval(B, H, W, _ptr(pred), _ptr(gt), _ptr(mask), 1 if disparity else 0, int(align_max_res or 0), float(min_depth), float(max_depth),
                                _ptr(out), _ptr(aligned), _ptr(ws), nws, _stream()))
     return (out, aligned) if return_aligned else out
+
+
+def normal_eval_workspace(device):
+    """one workspace for e2eft_normal_eval_update / _finalize (16-byte aligned, reused by every call of an accumulator)"""
+    n = _lib.load().e2eft_normal_eval_workspace_bytes()
+    return torch.empty(((n + 15) // 16 * 2,), dtype=torch.float64, device=device), n
+
+
+def normal_eval_update(pred, gt, mask, err, offset, totals, ws, nws):
+    """pred, gt fp32 [B,3,H,W] (any element strides), mask uint8 [B,H,W] (any strides) or None -> errors into err[offset : offset + B*H*W]
+    (+inf where the mask is 0); the update's totals are added to `totals` (int64 [9], see include/e2eft.h)"""
+    _check_cuda(pred, gt, mask, err, totals, ws)
+    assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and err.dtype == torch.float32 and totals.dtype == torch.int64
+    assert pred.dim() == 4 and pred.shape == gt.shape and pred.shape[1] == 3, (pred.shape, gt.shape)
+    B, _, H, W = pred.shape
+    d = _lib.NormalEvalDesc()
+    d.batch, d.height, d.width = B, H, W
+    d.pred_stride[:] = list(pred.stride())
+    d.gt_stride[:] = list(gt.stride())
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and tuple(mask.shape) == (B, H, W), (mask.dtype, mask.shape)
+        d.mask_stride[:] = list(mask.stride())
+    check(_lib.load().e2eft_normal_eval_update(C.byref(d), _ptr(pred), _ptr(gt), _ptr(mask), _ptr(err), int(offset), err.numel(), _ptr(totals),
+                                               _ptr(ws), nws, _stream()))
+
+
+def normal_eval_finalize(err, count, totals, ws, nws, out=None):
+    """-> fp64 [9]: mean, median, rmse, a1..a5, n over err[:count] and the totals (include/e2eft.h)"""
+    _check_cuda(err, totals, ws)
+    if out is None:
+        out = torch.empty((9,), dtype=torch.float64, device=totals.device)
+    check(_lib.load().e2eft_normal_eval_finalize(_ptr(err) if count else C.c_void_p(0), int(count), _ptr(totals), _ptr(out), _ptr(ws), nws, _stream()))
+    return out

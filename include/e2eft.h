@@ -499,6 +499,31 @@ size_t e2eft_depth_eval_workspace_bytes(int32_t batch);
 int e2eft_depth_eval(int32_t batch, int32_t height, int32_t width, const float* pred, const float* gt, const uint8_t* mask, int32_t disparity,
                      int32_t align_max_res, float min_depth, float max_depth, float* out_metrics, float* aligned_out, void* workspace,
                      size_t ws_bytes, void* stream);
+/* Surface-normal evaluation on the device: DSINE's benchmark arithmetic (/root/reference/DSINE/utils/utils.py:150-178, the accumulation loop of
+ * DSINE/projects/dsine/test.py:104-133).  pred / gt: fp32, logical shape [batch][3][height][width] with arbitrary non-negative element strides
+ * (batch, channel, row, column: a permuted [H][W][3] view needs no copy); mask: uint8 [batch][height][width] with strides (batch, row, column),
+ * non-zero = valid, NULL = every pixel valid.
+ *   _update    per pixel theta = acos(clamp(n_p . n_g, -1, 1)) * 180 / pi in fp32 with n = v / max(|v|, 1e-8) (torch.cosine_similarity); theta of
+ *              pixel (b, y, x) goes to err[err_offset + (b * height + y) * width + x], +inf where the mask is 0, so that the valid errors in
+ *              buffer order are the reference's torch.cat of pred_error[mask].  err_offset + batch * height * width <= err_capacity.  The update's
+ *              totals are reduced over fixed per-block partials (bit-reproducible) and added to `totals`: 9 8-byte device words
+ *              {int64 n, int64 nan, int64 count[5] (theta < 5, 7.5, 11.25, 22.5, 30), double sum theta, double sum theta^2}; zero them to start.
+ *   _finalize  over err[0 .. count) (count < 2^32, the sum of the updates' pixel counts; err 16-byte aligned) and the totals: the exact median
+ *              (np.median of float32: the middle value, or the float32 mean of the two middle values) by a radix select of the bit patterns, and
+ *              out[9] = mean, median, rmse, a1..a5 (100 * count_i / n), n, in fp64.  A NaN error among the valid pixels makes mean, median and rmse
+ *              NaN (numpy); n == 0 makes all eight metrics NaN.
+ * Neither reads device memory back to the host; both are capturable in a graph.  One workspace of e2eft_normal_eval_workspace_bytes() (16-byte
+ * aligned) serves both; calls that share it run on one stream. */
+typedef struct {
+    int32_t batch, height, width, reserved;
+    int64_t pred_stride[4], gt_stride[4]; /* elements: batch, channel, row, column */
+    int64_t mask_stride[3];               /* elements: batch, row, column */
+} e2eft_normal_eval_desc;
+size_t e2eft_normal_eval_workspace_bytes(void);
+int e2eft_normal_eval_update(const e2eft_normal_eval_desc* desc, const float* pred, const float* gt, const uint8_t* mask, float* err,
+                             int64_t err_offset, int64_t err_capacity, int64_t* totals, void* workspace, size_t ws_bytes, void* stream);
+int e2eft_normal_eval_finalize(const float* err, int64_t count, const int64_t* totals, double* out, void* workspace, size_t ws_bytes,
+                               void* stream);
 /* Test-time ensembling of the n_img (<= 32) predictions of ONE image, fp32, replacing
  *   ensemble_depths   /root/reference/Marigold/marigold/util/ensemble.py:40-132 (called from marigold_pipeline.py:293-297;
  *                     twin GeoWizard/geowizard/utils/depth_ensemble.py:21-115)
