@@ -47,6 +47,13 @@ class NormalEvalDesc(C.Structure):
         ("pred_stride", C.c_int64 * 4), ("gt_stride", C.c_int64 * 4), ("mask_stride", C.c_int64 * 3)]
 
 
+class D2ntDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "refine", "out_format")] + [("depth_scale", C.c_float)]
+
+
+D2NT_F32, D2NT_U16, D2NT_U8 = range(3)      # e2eft_d2nt_desc.out_format
+
+
 # e2eft_set_option keys (include/e2eft.h)
 OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT = range(15)
 
@@ -152,6 +159,7 @@ SIGNATURES = {
     "e2eft_normal_eval_workspace_bytes": (_Z, []),
     "e2eft_normal_eval_update": (_I, [C.POINTER(NormalEvalDesc), _P, _P, _P, _P, _L, _L, _P, _P, _Z, _P]),
     "e2eft_normal_eval_finalize": (_I, [_P, _L, _P, _P, _P, _Z, _P]),
+    "e2eft_depth_to_normals": (_I, [C.POINTER(D2ntDesc), _P, _P, _P, _P]),
     "e2eft_ensemble_workspace_bytes": (_Z, [_I]),
     "e2eft_ensemble_minmax": (_I, [_I, _L, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_gram": (_I, [_I, _L, _P, _P, _P, _P, _Z, _P]),

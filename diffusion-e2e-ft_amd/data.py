@@ -15,6 +15,9 @@
                     (the reference's index order), a thread pool that decodes ahead, pinned staging buffers, upload + device preparation on a side stream;
                     yields the batch dict train.py consumes (train.py:470-475).  `MixedDataLoader(DeviceLoader(hypersim), DeviceLoader(vkitti), 9, 1)` is
                     the reference's training input.
+  depth_to_normals_vkitti   the D2NT "v3" translator the fine-tuning authors ran offline to make Virtual KITTI 2's normals (depth-to-normal-translator/
+                    python/gen_vkitti_normals.py), on the device: `VirtualKITTI2(..., normals="d2nt")` synthesises them per batch instead of reading
+                    vkitti_DAG_normals/; `write_png16` writes the reference's file format (scripts/gen_vkitti_normals.py).
 File decoding itself is a callable (`decoder=`): the default uses Pillow when it is importable (every file of both datasets is a PNG / JPEG it reads,
 16-bit depth included — the reference's cv2.imread of the KITTI depth returns the same integers); the package does not import an image library otherwise."""
 import csv
@@ -260,10 +263,15 @@ class Hypersim(_DecodedDataset):
 
 
 class VirtualKITTI2(_DecodedDataset):
-    """load.py:285-375.  `__getitem__(i)` -> {"rgb_u8" uint8 [375,1242,3], "depth" fp32 [375,1242] metres (`.astype(np.float32) / 100.0`, :330), "normal_u8"}"""
+    """load.py:285-375.  `__getitem__(i)` -> {"rgb_u8" uint8 [375,1242,3], "depth" fp32 [375,1242] metres (`.astype(np.float32) / 100.0`, :330), "normal_u8"}.
+    normals="files" (default) reads vkitti_DAG_normals/ as the reference does (:332); normals="d2nt" opens no normal file and returns no "normal_u8":
+    DeviceLoader / finish_samples compute it on the device from the full-resolution depth (depth_to_normals_vkitti), so the folder need not exist."""
     name = "vkitti"
 
-    def __init__(self, root_dir, transform=None, near_plane=1e-5, far_plane=80.0, decoder=None):
+    def __init__(self, root_dir, transform=None, near_plane=1e-5, far_plane=80.0, decoder=None, normals="files"):
+        if normals not in ("files", "d2nt"):
+            raise ValueError("normals must be 'files' or 'd2nt', got %r" % (normals,))
+        self.normals = normals
         self.root_dir = root_dir
         self.near_plane, self.far_plane = near_plane, far_plane
         self.decoder = decoder or pil_decoder
@@ -286,8 +294,48 @@ class VirtualKITTI2(_DecodedDataset):
         return pairs
 
     def __getitem__(self, idx):
+        if self.normals == "d2nt":
+            rgb_path, depth_path, _ = self.pairs[idx]
+            rgb = np.ascontiguousarray(self.decoder(rgb_path, "rgb"))
+            return {"rgb_u8": rgb, "depth": np.ascontiguousarray(self.decoder(depth_path, "depth").astype(np.float32) / 100.0)}
         rgb, depth, normal = self._decode(*self.pairs[idx])
         return {"rgb_u8": rgb, "depth": np.ascontiguousarray(depth.astype(np.float32) / 100.0), "normal_u8": normal}
+
+
+VKITTI_INTRINSICS = (725.0087, 725.0087, 620.5, 187.0)     # gen_vkitti_normals.py:70-73 (fx, fy, cx, cy; vkitti_2.0.3_textgt)
+_VKITTI_K = {}
+
+
+@torch.no_grad()
+def depth_to_normals_vkitti(depth_m, refine=True, out_format="u8"):
+    """Virtual KITTI 2 normals as gen_vkitti_normals.py makes them (VERSION = 'd2nt_v3'; refine=False: 'd2nt_v2'): depth_m fp32 [B,H,W] or [H,W] metres
+    (VirtualKITTI2's "depth") on the device -> channels-last [.., H, W, 3]: "u8" what the training loader reads from the file (`Image.open(p).convert('RGB')`
+    of the 16-bit PNG keeps the high byte), "u16" the file's values, "f32" the normals themselves.  Centimetres (x 100 in fp32) and the dataset's one
+    camera, as the generator uses them."""
+    key = str(depth_m.device)
+    if key not in _VKITTI_K:
+        _VKITTI_K[key] = torch.tensor(VKITTI_INTRINSICS, dtype=torch.float32, device=depth_m.device)
+    return ops.depth_to_normals(depth_m, _VKITTI_K[key], refine=refine, out_format=out_format, depth_scale=100.0)
+
+
+def write_png16(path, rgb_u16, level=6):
+    """a 16-bit RGB PNG (colour type 2, big-endian samples, filter 0 on every row) of uint16 [H,W,3] — the file cv2.imwrite makes of the reference's
+    BGR-swapped array, without OpenCV: channel 0 is R"""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(rgb_u16, dtype=">u2")
+    H, W, C = a.shape
+    assert C == 3, a.shape
+    rows = np.empty((H, 1 + W * 6), dtype=np.uint8)
+    rows[:, 0] = 0
+    rows[:, 1:] = a.reshape(H, W * 3).view(np.uint8)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    blob = b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 16, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), level)) + chunk(b"IEND", b"")
+    with open(path, "wb") as f:
+        f.write(blob)
 
 
 @torch.no_grad()
@@ -295,7 +343,13 @@ class VirtualKITTI2(_DecodedDataset):
 def finish_samples(rgb_u8, depth, normal_u8, dataset, flip=None, transform=True, near_plane=None, far_plane=None, align=True):
     """everything `__getitem__` does after decoding (load.py:225-283 / :336-375), batched on the device: rgb_u8 / normal_u8 uint8 [B,H0,W0,3], depth fp32
     [B,H0,W0] metres, flip = per-sample booleans -> the batch dict.  Hypersim: normals turned towards the camera on the full-resolution image
-    (e2eft_align_normals_u8), then flip + Pillow-exact resize to 480 x 640; Virtual KITTI 2: flip + KITTI benchmark crop; then prepare_batch."""
+    (e2eft_align_normals_u8), then flip + Pillow-exact resize to 480 x 640; Virtual KITTI 2: flip + KITTI benchmark crop; then prepare_batch.
+    Virtual KITTI 2 with normal_u8=None: the normals the reference's offline generator would have stored, made from the full-resolution depth first
+    (depth_to_normals_vkitti), where the reference read them."""
+    if normal_u8 is None:
+        if dataset != "vkitti":
+            raise ValueError("finish_samples: normal_u8 is required for %s (only Virtual KITTI 2 normals can be synthesised from depth)" % dataset)
+        normal_u8 = depth_to_normals_vkitti(depth.float().contiguous(), refine=True, out_format="u8")
     if dataset == "hypersim":
         if align:
             H0, W0 = rgb_u8.shape[1:3]
@@ -349,6 +403,8 @@ class DeviceLoader:
         pin = self.device.type == "cuda"
         out = {}
         for key, dt in (("rgb_u8", torch.uint8), ("depth", torch.float32), ("normal_u8", torch.uint8)):
+            if key == "normal_u8" and key not in samples[0]:          # VirtualKITTI2(normals="d2nt"): synthesised on the device in _finish
+                continue
             first = samples[0][key]
             buf = torch.empty((len(samples),) + tuple(first.shape), dtype=dt, pin_memory=pin)
             for i, smp in enumerate(samples):
@@ -366,7 +422,7 @@ class DeviceLoader:
             self._stream = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self._stream):
             dev = {k: v.to(self.device, non_blocking=True) for k, v in staged.items()}
-            batch = finish_samples(dev["rgb_u8"], dev["depth"], dev["normal_u8"], ds.name, flip=flips if ds.transform else None,
+            batch = finish_samples(dev["rgb_u8"], dev["depth"], dev.get("normal_u8"), ds.name, flip=flips if ds.transform else None,
                                    transform=bool(ds.transform), near_plane=ds.near_plane, far_plane=ds.far_plane, align=getattr(ds, "align_cam_normal", False))
             ev = torch.cuda.Event()
             ev.record(self._stream)

@@ -1605,3 +1605,36 @@ def normal_eval_finalize(err, count, totals, ws, nws, out=None):
         out = torch.empty((9,), dtype=torch.float64, device=totals.device)
     check(_lib.load().e2eft_normal_eval_finalize(_ptr(err) if count else C.c_void_p(0), int(count), _ptr(totals), _ptr(out), _ptr(ws), nws, _stream()))
     return out
+
+
+_D2NT_FORMATS = {"f32": (_lib.D2NT_F32, torch.float32), "u16": (_lib.D2NT_U16, torch.uint16), "u8": (_lib.D2NT_U8, torch.uint8)}
+
+
+def depth_to_normals(depth, intrinsics, refine=True, out_format="f32", depth_scale=1.0, out=None):
+    """the D2NT translator (csrc/d2nt.hip, include/e2eft.h e2eft_depth_to_normals): depth fp32 [B,H,W] (or [H,W]), intrinsics fp32 (fx, fy, cx, cy)
+    as a device tensor [B,4] or [4] (one camera for the batch) -> channels-last [B,H,W,3] normals: "f32", the file's "u16" or the loader's "u8"
+    (its high byte).  refine: v3 (MRF refinement) / v2.  Z = depth * depth_scale in fp32 before anything else."""
+    if out_format not in _D2NT_FORMATS:
+        raise ValueError("out_format must be one of %s, got %r" % (sorted(_D2NT_FORMATS), out_format))
+    fmt, odt = _D2NT_FORMATS[out_format]
+    squeeze = depth.dim() == 2
+    d = depth[None] if squeeze else depth
+    assert d.dim() == 3 and d.dtype == torch.float32, (tuple(depth.shape), depth.dtype)
+    d = d.contiguous()
+    B, H, W = d.shape
+    if not isinstance(intrinsics, torch.Tensor):
+        intrinsics = torch.tensor([float(v) for v in intrinsics], dtype=torch.float32, device=d.device)
+    k = intrinsics.to(torch.float32)
+    if k.dim() == 1:
+        assert k.numel() == 4, tuple(k.shape)
+        k = k[None].expand(B, 4)
+    assert tuple(k.shape) == (B, 4), (tuple(k.shape), B)
+    k = k.contiguous()
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=odt, device=d.device)
+    assert out.dtype == odt and tuple(out.shape) == (B, H, W, 3) and out.is_contiguous(), (out.dtype, tuple(out.shape))
+    _check_cuda(d, k, out)
+    desc = _lib.D2ntDesc()
+    desc.batch, desc.height, desc.width, desc.refine, desc.out_format, desc.depth_scale = B, H, W, 1 if refine else 0, fmt, float(depth_scale)
+    check(_lib.load().e2eft_depth_to_normals(C.byref(desc), _ptr(d), _ptr(k), _ptr(out), _stream()))
+    return out[0] if squeeze else out

@@ -524,6 +524,29 @@ int e2eft_normal_eval_update(const e2eft_normal_eval_desc* desc, const float* pr
                              int64_t err_offset, int64_t err_capacity, int64_t* totals, void* workspace, size_t ws_bytes, void* stream);
 int e2eft_normal_eval_finalize(const float* err, int64_t count, const int64_t* totals, double* out, void* workspace, size_t ws_bytes,
                                void* stream);
+/* Surface normals from depth (the D2NT "v3" translator that generates Virtual KITTI 2's training normals offline:
+ * depth-to-normal-translator/python/gen_vkitti_normals.py:100-133 with VERSION = 'd2nt_v3', over utils/myApis.py:48-179 and
+ * utils/apis.py:38-41; the training loader reads the result at training/dataloaders/load.py:332).  depth: fp32 [batch][height][width], contiguous;
+ * intrinsics: fp32 [batch][4] = fx, fy, cx, cy per image, in DEVICE memory; out: channels-last [batch][height][width][3] of out_format.
+ *   Z = depth * depth_scale in fp32 (100: Virtual KITTI metres back to the generator's centimetres).  grad_l/r/u/d and |grad_l - grad_r|,
+ *   |grad_u - grad_d| in fp32 with reflect-101 borders (cv2.filter2D); P = powf(e32, -lap) in fp32 (np.power(np.e, float32) stays float32);
+ *   soft-min weights lambda1 = (P_left + eps / 2) / ((eps + P_left) + P_right) in fp64 with P = 0 beyond the image (myApis.py:48-70), the four
+ *   sequential snapping lines per direction (myApis.py:112-120, thresh e); Gu = l1 grad_l + l2 grad_r, Gv = l3 grad_u + l4 grad_d;
+ *   n = (Gu fx, Gv fy, -((Z + v Gv) + u Gu)) with 1-based u = x + 1 - cx, v = y + 1 - cy, divided by sqrt((nx2 + ny2) + nz2) + 1e-8 (fp64).
+ *   refine = 1 (v3, MRF_optim myApis.py:128-179 with 'DLF-alpha'): L = |filter2D(Z, [[0,-1,0],[-1,4,-1],[0,-1,0]])| (fp32, taps in row-major
+ *   order; OpenCV's own accumulation order may differ in the last bit of L), each pixel takes the normal of argmin(L(x-1), L(x+1), L(y-1), L(y+1),
+ *   L(self)) (+inf beyond the image, first index on ties, a NaN wins at its first occurrence), one pass; refine = 0: v2.  Then n *= -1.
+ *   out_format E2EFT_D2NT_F32: float n; E2EFT_D2NT_U16: the file's ((n + 1) * 32767.5) truncated to uint16, from the fp64 n;
+ *   E2EFT_D2NT_U8: its high byte (u16 >> 8: Image.open(p).convert('RGB') of the 48-bit PNG, what the training loader sees).
+ * height, width >= 2.  One kernel launch; no host synchronisation, no device read-back: capturable in a graph. */
+enum { E2EFT_D2NT_F32 = 0, E2EFT_D2NT_U16 = 1, E2EFT_D2NT_U8 = 2 };
+typedef struct {
+    int32_t batch, height, width;
+    int32_t refine;     /* 1: d2nt_v3 (MRF refinement), 0: d2nt_v2 */
+    int32_t out_format; /* E2EFT_D2NT_* */
+    float depth_scale;  /* Z = depth * depth_scale, fp32 */
+} e2eft_d2nt_desc;
+int e2eft_depth_to_normals(const e2eft_d2nt_desc* desc, const float* depth, const float* intrinsics, void* out, void* stream);
 /* Test-time ensembling of the n_img (<= 32) predictions of ONE image, fp32, replacing
  *   ensemble_depths   /root/reference/Marigold/marigold/util/ensemble.py:40-132 (called from marigold_pipeline.py:293-297;
  *                     twin GeoWizard/geowizard/utils/depth_ensemble.py:21-115)
