@@ -582,13 +582,13 @@ class _NormConvSplitFn(torch.autograd.Function):
         dt = x.dtype
         B, H, W, c1 = x.shape
         cout = conv.weight.shape[0]
-        planes, pscale, ws = ops.groupnorm_fwd_split_ws(x, _vec(gamma, dt), _vec(beta, dt), groups, eps, silu=silu, s1=s1)
-        out = ops.new_nhwc(B, H, W, cout, dt, x.device)
         if residual is not None:
-            assert tuple(residual.shape) == tuple(out.shape) and residual.dtype == dt
-        r = ops._conv2d_f32split(None, packed_conv_weight(conv, dt), _vec(conv.bias, dt), cout, residual, 1.0, out, gn_stats and ops.GN_STATS_ENABLED and cout % 8 == 0,
-                                 "conv3x3s1n B%d %dx%d %d->%d" % (B, H, W, c1, cout), planes=planes, scale=pscale)
-        assert r is not None, "norm_conv_split: the library declined a shape ops.f32split_shape_ok accepted"
+            assert tuple(residual.shape) == (B, H, W, cout) and residual.dtype == dt
+        r = ops.conv2d_norm_split(x, (_vec(gamma, dt), _vec(beta, dt), groups, eps, silu), packed_conv_weight(conv, dt), _vec(conv.bias, dt), cout, residual=residual,
+                                  gn_stats=gn_stats, s1=s1)
+        if r is None:
+            raise RuntimeError("norm_conv_split: the library declined a convolution ops.f32split_shape_ok accepted (nothing was launched)")
+        out, ws = r
         _stash_stats(out)
         ctx.save_for_backward(x, gamma, beta, ws)
         ctx.conv, ctx.meta, ctx.has_res = conv, (groups, eps, silu), residual is not None
@@ -642,10 +642,7 @@ def norm_conv_split(conv_mod, norm_mod, x, silu, residual=None, split=False, gn_
     B, H, W, c1 = x.shape
     if tuple(w.shape[2:]) != (3, 3) or stride != 1 or pad != 1 or w.shape[1] != c1 or not ops.f32split_shape_ok(B, H, W, c1, w.shape[0]):
         return None
-    try:
-        if ops._nhwc_ld(x) % 4 != 0 or x.data_ptr() % 16 != 0:
-            return None
-    except ValueError:
+    if not ops.f32split_operands_ok((x,)):
         return None
     sp = split and x.requires_grad
     out = _NormConvSplitFn.apply(x, norm_mod.weight, norm_mod.bias, residual, conv_mod, norm_mod.num_groups, norm_mod.eps, silu, getattr(x, "_e2eft_gn", None), sp, gn_stats)

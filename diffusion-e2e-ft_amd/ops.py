@@ -234,46 +234,48 @@ SPLITK_ENABLED = True     # tests flip this to cross-check split-K convolutions 
 UPCONV_PHASES_ENABLED = True     # tests / A-B: False keeps 2x-upsample convolutions on the fused-upsample 3x3 form
 
 
-def _gn_buffer(images, rows_per_image, cout, device):
-    nbytes = images * ((rows_per_image + 127) // 128) * cout * 12
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), nbytes
-
-
-def _attach_stats(out, buf, slab_rows, images, rows_per_image, cout):
-    if slab_rows > 0:
-        nslabs = rows_per_image // slab_rows
+def _launch_with_stats(launch, out, want, images, rows_per_image, cout):
+    """One library call that can emit the GroupNorm partial statistics of `out` from its epilogue.  launch(buf_ptr, nbytes, slab_ref) makes the call and returns its
+    status; with `want` it is handed the statistics buffer, and the statistics are attached to `out` when the kernel reports a slab height (0: it emitted none)."""
+    buf, nbytes = None, 0
+    if want:
+        nbytes = images * ((rows_per_image + 127) // 128) * cout * 12
+        buf = torch.empty(nbytes // 4, dtype=torch.float32, device=out.device)
+    slab = C.c_int32(0)
+    check(launch(_ptr(buf), nbytes, C.byref(slab)))
+    if want and slab.value > 0:
+        nslabs = rows_per_image // slab.value
         out._e2eft_gn = GnStats(buf[: images * nslabs * cout * 3], nslabs)
     return out
 
 
-F32_SPLIT_ENABLED = True      # tests / A-B: False keeps fp32 convolutions / GEMMs on the fp32 matrix instruction (igemm2)
-WGRAD_F32_SPLIT = True        # tests / A-B: False keeps fp32 weight gradients on wgrad32_kernel (v_mfma_f32_32x32x2_f32)
-
-
 def f32_split2(x, keep=False, x2=None):
-    """fp32 NHWC [B,H,W,C] (C % 8 == 0) -> (planes f16 [B,H,W,2C] = [x0 | x1] with x * s = x0 + x1 to 2^-22, scale workspace fp32 [4]: [1] = s, [2] = 1 / s).
+    """fp32 NHWC [B,H,W,C] or row view [M,C] (C % 8 == 0) -> (planes f16 [..., 2C] = [x0 | x1] with x * s = x0 + x1 to 2^-22, scale workspace fp32 [4]: [1] = s, [2] = 1 / s).
     s is the power of two that brings the tensor's maximum into [2^14, 2^15), found on the device (csrc/f32split.hip).
-    keep: park the result on the tensor object (per version) — a gradient dY is split once for its data-gradient convolution AND its weight-gradient launches; only for
-    short-lived tensors (the planes live as long as x does).  x2: a second source — the planes are then those of cat(x, x2) along the channels, under one scale."""
+    keep: park the result on the tensor object (per version) — a gradient dY is split once for its data-gradient convolution AND its weight-gradient launches, and once
+    for the backward calls of two convolutions that receive the same dY object (a convolution hands its residual's gradient on as dY itself); only for short-lived
+    tensors (the planes live as long as x does).  x2 (NHWC only): a second source — the planes are then those of cat(x, x2) along the channels, under one scale."""
     _check_cuda(x, x2)
-    B, H, W, Cc = x.shape
+    Cc = x.shape[-1]
     assert x.dtype == torch.float32 and Cc % 8 == 0
-    if x2 is not None:
-        c2 = x2.shape[3]
-        assert tuple(x2.shape[:3]) == (B, H, W) and x2.dtype == torch.float32 and c2 % 8 == 0 and not keep
-        planes = torch.empty((B, H, W, 2 * (Cc + c2)), dtype=torch.float16, device=x.device)
-        scale = torch.empty(4, dtype=torch.float32, device=x.device)
-        with _timed("f32split", 0.0, 12.0 * B * H * W * (Cc + c2), label="split2 B%d %dx%d C%d+%d" % (B, H, W, Cc, c2), launches=4):
-            check(_lib.load().e2eft_f32_split2_cat(_ptr(x), Cc, _nhwc_ld(x), _ptr(x2), c2, _nhwc_ld(x2), B * H * W, _ptr(planes), 2 * (Cc + c2), _ptr(scale), _stream()))
-        return planes, scale
-    if keep:
-        ent = getattr(x, "_e2eft_planes", None)
-        if ent is not None and ent[0] == x._version:
-            return ent[1], ent[2]
-    planes = torch.empty((B, H, W, 2 * Cc), dtype=torch.float16, device=x.device)
+    if x.dim() == 2:
+        pixels, ld, label = x.shape[0], _rows_ld(x), "split2 rows M%d K%d" % (x.shape[0], Cc)
+    else:
+        B, H, W, _ = x.shape
+        pixels, ld, label = B * H * W, _nhwc_ld(x), "split2 B%d %dx%d C%d" % (B, H, W, Cc)
+    ent = getattr(x, "_e2eft_planes", None) if keep else None
+    if ent is not None and ent[0] == x._version:
+        return ent[1], ent[2]
+    c2 = 0 if x2 is None else x2.shape[3]
+    planes = torch.empty(tuple(x.shape[:-1]) + (2 * (Cc + c2),), dtype=torch.float16, device=x.device)
     scale = torch.empty(4, dtype=torch.float32, device=x.device)
-    with _timed("f32split", 0.0, 12.0 * B * H * W * Cc, label="split2 B%d %dx%d C%d" % (B, H, W, Cc), launches=2):
-        check(_lib.load().e2eft_f32_split2(_ptr(x), B * H * W, Cc, _nhwc_ld(x), _ptr(planes), 2 * Cc, _ptr(scale), _stream()))
+    if x2 is not None:
+        assert tuple(x2.shape[:3]) == tuple(x.shape[:3]) and x2.dtype == torch.float32 and c2 % 8 == 0 and not keep
+        with _timed("f32split", 0.0, 12.0 * pixels * (Cc + c2), label="%s+%d" % (label, c2), launches=4):
+            check(_lib.load().e2eft_f32_split2_cat(_ptr(x), Cc, ld, _ptr(x2), c2, _nhwc_ld(x2), pixels, _ptr(planes), 2 * (Cc + c2), _ptr(scale), _stream()))
+    else:
+        with _timed("f32split", 0.0, 12.0 * pixels * Cc, label=label, launches=2):
+            check(_lib.load().e2eft_f32_split2(_ptr(x), pixels, Cc, ld, _ptr(planes), 2 * Cc, _ptr(scale), _stream()))
     if keep:
         x._e2eft_planes = (x._version, planes, scale)
     return planes, scale
@@ -297,26 +299,42 @@ def f32_split_weight(w_packed, taps, c):
     return wsp, inv
 
 
-def _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, ldo, ldr):
+def _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, ldo, ldr, up_to=None):
+    """descriptor of a launch that reads split planes of c1 fp32 channels (pixel stride 2 c1); up_to = (hl, wl): the fused 2x upsample of e2eft_upconv2x_fwd_f32split"""
     pt, pb, pl, pr = pad
+    hl, wl = (H, W) if up_to is None else up_to
     d = ConvDesc()
     d.dtype = _lib.F32
-    d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, H, W
+    d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, hl, wl
     d.c1, d.ldx1, d.c2, d.ldx2 = c1, 2 * c1, 0, 0
     d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-    d.hout = (H + pt + pb - kh) // stride + 1
-    d.wout = (W + pl + pr - kw) // stride + 1
+    d.hout = (hl + pt + pb - kh) // stride + 1
+    d.wout = (wl + pl + pr - kw) // stride + 1
     d.cout, d.ldo, d.ldr, d.ldw = cout, ldo, ldr, kh * kw * 3 * c1
     d.alpha = 1.0
     return d
 
 
 def f32split_shape_ok(B, H, W, c1, cout, kh=3, kw=3, stride=1, pad=(1, 1, 1, 1)):
-    """pure host arithmetic: would the library run this fp32 convolution [B,H,W,c1] -> cout from f16 split planes (e2eft_conv2d_fwd_f32split_supported)?"""
-    if not F32_SPLIT_ENABLED or c1 % 64 != 0 or cout % 8 != 0:
+    """pure host arithmetic: would the library run this fp32 convolution [B,H,W,c1] -> cout from f16 split planes (e2eft_conv2d_fwd_f32split_supported: 0 for every
+    shape while E2EFT_OPT_F32_SPLIT is off)?"""
+    if c1 % 64 != 0 or cout % 8 != 0:
         return False
     d = _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, cout, cout)
     return _lib.load().e2eft_conv2d_fwd_f32split_supported(C.byref(d)) == 1
+
+
+def f32split_operands_ok(sources, others=()):
+    """What every launch of the split route asks of its operands, beyond the shape its `*_supported` query judges.  sources: the fp32 tensors the split pass reads
+    (NHWC or row views, None skipped) — 16-byte aligned base, channels % 8, pixel stride % 4 (e2eft_f32_split2's requirements; a view that is not pixel-dense is not
+    eligible either).  others: bias / residual / output (None skipped) — 16-byte aligned base."""
+    try:
+        for t in sources:
+            if t is not None and (t.data_ptr() % 16 or t.shape[-1] % 8 or (_rows_ld(t) if t.dim() == 2 else _nhwc_ld(t)) % 4):
+                return False
+    except ValueError:
+        return False
+    return all(t is None or t.data_ptr() % 16 == 0 for t in others)
 
 
 def groupnorm_fwd_split_ws(x, gamma, beta, groups, eps, silu=False, s1=None):
@@ -342,37 +360,59 @@ def groupnorm_fwd_split_ws(x, gamma, beta, groups, eps, silu=False, s1=None):
     return planes, scale, ws
 
 
-def _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, planes=None, scale=None, geom=(3, 3, 1, (1, 1, 1, 1)), keep_planes=False, x2=None):
-    """An fp32 convolution (geom = kh, kw, stride, pads; no fused upsample) through e2eft_conv2d_fwd_f32split, or None when the library declines the
-    shape.  planes / scale: the input already split (groupnorm_fwd_split_ws) — x is then ignored."""
-    B, H, W, c1 = x.shape if planes is None else (planes.shape[0], planes.shape[1], planes.shape[2], planes.shape[3] // 2)
-    if x2 is not None:          # two sources: the convolution of their channel concatenation (one pair of planes, one scale)
-        c1 = c1 + x2.shape[3]
-    kh, kw, stride, pad = geom
-    d = _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, _nhwc_ld(out), _nhwc_ld(residual) if residual is not None else 0)
+def _f32split_conv_desc(B, H, W, c1, w_packed, bias, cout, residual, alpha, out, geom, sources):
+    """The descriptor of e2eft_conv2d_fwd_f32split for an fp32 convolution (geom = kh, kw, stride, pads; no fused upsample) of [B,H,W,c1], or None when the route does
+    not take it.  Host arithmetic only: nothing is launched.  sources: the fp32 tensors that will be split (none when the planes come from a producer)."""
+    d = _f32split_desc(B, H, W, c1, cout, *geom, _nhwc_ld(out), _nhwc_ld(residual) if residual is not None else 0)
     assert (d.hout, d.wout) == (out.shape[1], out.shape[2])
-    H, W = d.hout, d.wout          # (below: the OUTPUT grid)
     d.alpha = alpha
-    lib = _lib.load()
-    if (lib.e2eft_conv2d_fwd_f32split_supported(C.byref(d)) != 1 or out.data_ptr() % 16 or (residual is not None and residual.data_ptr() % 16)
-            or (bias is not None and bias.data_ptr() % 16) or not w_packed.is_contiguous() or (planes is None and (x.data_ptr() % 16 or _nhwc_ld(x) % 4))
-            or (x2 is not None and (x2.data_ptr() % 16 or _nhwc_ld(x2) % 4 or x2.shape[3] % 8 or x.shape[3] % 8))):
+    if (_lib.load().e2eft_conv2d_fwd_f32split_supported(C.byref(d)) != 1 or not w_packed.is_contiguous()
+            or not f32split_operands_ok(sources, (out, residual, bias))):
         return None
-    wsp, inv_sw = f32_split_weight(w_packed, kh * kw, c1)
-    d.alpha = alpha
-    if planes is None:
-        planes, scale = f32_split2(x, keep=keep_planes, x2=x2)
-    assert scale is not None
-    nb = (planes.numel() * 2 + B * H * W * cout * 4 * (2 if residual is not None else 1) + cout * kh * kw * 3 * c1 * 2)
+    return d
+
+
+def _f32split_conv_launch(d, planes, scale, wsplit, bias, residual, out, want, label):
+    B, H, W, cout, kk = d.batch, d.hout, d.wout, d.cout, d.kh * d.kw * d.c1          # (H, W: the OUTPUT grid)
+    wsp, inv_sw = wsplit
+    lib = _lib.load()
+    nb = (planes.numel() * 2 + B * H * W * cout * 4 * (2 if residual is not None else 1) + cout * 3 * kk * 2)
     # (flops: what the f16 pipe multiplies — three products per fp32 product; flops_nominal: the fp32 convolution)
-    with _timed("igemm", 6.0 * B * H * W * cout * kh * kw * c1, nb, label=label + " f32split", flops_nominal=2.0 * B * H * W * cout * kh * kw * c1):
-        buf, nbytes = _gn_buffer(B, H * W, cout, out.device) if want else (None, 0)
-        slab = C.c_int32(0)
-        check(lib.e2eft_conv2d_fwd_f32split(C.byref(d), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(residual), _ptr(out), _ptr(buf), nbytes,
-                                            C.byref(slab), _stream()))
-        if want:
-            _attach_stats(out, buf, slab.value, B, H * W, cout)
+    with _timed("igemm", 6.0 * B * H * W * cout * kk, nb, label=label + " f32split", flops_nominal=2.0 * B * H * W * cout * kk):
+        _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_f32split(
+            C.byref(d), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(residual), _ptr(out), buf, nbytes, slab, _stream()), out, want, B, H * W, cout)
     return out
+
+
+def _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, geom=(3, 3, 1, (1, 1, 1, 1)), x2=None, keep_planes=False):
+    """An fp32 convolution of x (x2: of cat(x, x2) — one pair of planes, one scale) through e2eft_conv2d_fwd_f32split, or None when the route does not take it.
+    keep_planes: see f32_split2."""
+    c1 = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
+    d = _f32split_conv_desc(*x.shape[:3], c1, w_packed, bias, cout, residual, alpha, out, geom, (x, x2))
+    if d is None:
+        return None
+    wsplit = f32_split_weight(w_packed, geom[0] * geom[1], c1)
+    planes, scale = f32_split2(x, keep=keep_planes, x2=x2)
+    return _f32split_conv_launch(d, planes, scale, wsplit, bias, residual, out, want, label)
+
+
+def conv2d_norm_split(x, norm, w_packed, bias, cout, residual=None, alpha=1.0, out=None, gn_stats=False, s1=None):
+    """The fp32 3x3 / stride-1 / pad-1 convolution of GroupNorm(+SiLU)(x), norm = (gamma, beta, groups, eps, silu): the norm's apply pass writes the f16 split planes the
+    convolution reads (csrc/f32split.hip) — no fp32 intermediate, no maximum pass.  s1: GnStats of x from its producer.  -> (out, the workspace groupnorm_bwd wants), or
+    None when the route does not take the convolution: that is known before anything is launched."""
+    B, H, W, c1 = x.shape
+    if x.dtype != torch.float32 or (alpha != 1.0 and bias is not None) or w_packed.shape[1] != 9 * c1 or cout % 8 != 0:
+        return None
+    _check_cuda(x, w_packed, bias, residual, out)
+    if out is None:
+        out = new_nhwc(B, H, W, cout, x.dtype, x.device)
+    d = _f32split_conv_desc(B, H, W, c1, w_packed, bias, cout, residual, alpha, out, (3, 3, 1, (1, 1, 1, 1)), ())
+    if d is None:
+        return None
+    gamma, beta, groups, eps, silu = norm
+    planes, scale, ws = groupnorm_fwd_split_ws(x, gamma, beta, groups, eps, silu=silu, s1=s1)
+    _f32split_conv_launch(d, planes, scale, f32_split_weight(w_packed, 9, c1), bias, residual, out, gn_stats and GN_STATS_ENABLED, "conv3x3s1n B%d %dx%d %d->%d" % (B, H, W, c1, cout))
+    return out, ws
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -415,15 +455,14 @@ def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None,
     if rowadd is not None:
         assert rowadd.dtype == x.dtype and tuple(rowadd.shape) == (B, cout) and rowadd.is_contiguous()
     want = gn_stats and GN_STATS_ENABLED and cout % 8 == 0
-    if (w_phase is not None and UPCONV_PHASES_ENABLED and F32_SPLIT_ENABLED and x.dtype == torch.float32 and up_to is not None and x2 is None and rowadd is None
-            and residual is None and norm is None and alpha == 1.0 and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1) and (hl, wl) == (2 * H, 2 * W)
-            and c1 % 64 == 0 and x.data_ptr() % 16 == 0 and d.ldx1 % 4 == 0 and out.data_ptr() % 16 == 0 and (bias is None or bias.data_ptr() % 16 == 0)):
+    # nearest-2x upsample + 3x3 / stride 1 / pad 1: four 2x2 phase convolutions of the low-resolution input (4/9 of the multiply-adds)
+    phases = (w_phase is not None and UPCONV_PHASES_ENABLED and up_to is not None and x2 is None and rowadd is None and residual is None and norm is None and alpha == 1.0
+              and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1) and (hl, wl) == (2 * H, 2 * W))
+    if phases and x.dtype == torch.float32 and c1 % 64 == 0 and f32split_operands_ok((x,), (out, bias)):
         # fp32: the four 2x2 phases on the f16 matrix pipe from split planes (csrc/f32split.hip)
         lib = _lib.load()
-        ldx_keep = d.ldx1
-        d.ldx1 = 2 * c1
-        ok = lib.e2eft_upconv2x_fwd_f32split_supported(C.byref(d)) == 1
-        if ok:
+        ds = _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, d.ldo, 0, up_to=up_to)
+        if lib.e2eft_upconv2x_fwd_f32split_supported(C.byref(ds)) == 1:
             wp = w_phase()
             assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.dtype == torch.float32
             wsp, inv_sw = f32_split_weight(wp, 4, c1)
@@ -431,29 +470,17 @@ def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None,
             nbp = planes.numel() * 2 + B * hout * wout * cout * 4 + wsp.numel() * 2
             with _timed("igemm", 6.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d f32split" % (B, hout, wout, c1, cout), launches=4,
                         flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
-                buf, nbytes = _gn_buffer(B, hout * wout, cout, x.device) if want else (None, 0)
-                slab = C.c_int32(0)
-                check(lib.e2eft_upconv2x_fwd_f32split(C.byref(d), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(out), _ptr(buf), nbytes,
-                                                      C.byref(slab), _stream()))
-                if want:
-                    _attach_stats(out, buf, slab.value, B, hout * wout, cout)
+                _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_upconv2x_fwd_f32split(
+                    C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(out), buf, nbytes, slab, _stream()), out, want, B, hout * wout, cout)
             return out
-        d.ldx1 = ldx_keep
-    if (w_phase is not None and UPCONV_PHASES_ENABLED and up_to is not None and x2 is None and rowadd is None and residual is None and norm is None and alpha == 1.0
-            and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1) and (hl, wl) == (2 * H, 2 * W)
-            and _lib.load().e2eft_upconv2x_fwd_supported(C.byref(d)) == 1):
+    if phases and _lib.load().e2eft_upconv2x_fwd_supported(C.byref(d)) == 1:
         wp = w_phase()
         assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.is_contiguous() and wp.dtype == x.dtype, (wp.shape, wp.dtype)
-        if bias is not None:
-            assert bias.dtype == x.dtype and bias.numel() == cout and bias.is_contiguous()
         nbp = (B * H * W * c1 + B * hout * wout * cout + 4 * cout * 4 * c1) * x.element_size()
         with _timed("igemm", 2.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d" % (B, hout, wout, c1, cout), launches=4,
                     flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
-            buf, nbytes = _gn_buffer(B, hout * wout, cout, x.device) if want else (None, 0)
-            slab = C.c_int32(0)
-            check(_lib.load().e2eft_upconv2x_fwd(C.byref(d), _ptr(x), _ptr(wp), _ptr(bias), _ptr(out), _ptr(buf), nbytes, C.byref(slab), _stream()))
-            if want:
-                _attach_stats(out, buf, slab.value, B, hout * wout, cout)
+            _launch_with_stats(lambda buf, nbytes, slab: _lib.load().e2eft_upconv2x_fwd(C.byref(d), _ptr(x), _ptr(wp), _ptr(bias), _ptr(out), buf, nbytes, slab, _stream()),
+                               out, want, B, hout * wout, cout)
         return out
     es = x.element_size()
     nb = (B * H * W * (d.c1 + d.c2) + B * hout * wout * cout * (2 if residual is not None else 1) + cout * kh * kw * (d.c1 + d.c2)) * es
@@ -466,23 +493,16 @@ def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None,
         narrow_ok = cout > 4 or (rowadd is None and residual is None and not want)
         if NORM_FUSION_ENABLED and x2 is None and not sk and narrow_ok and lib.e2eft_conv2d_fwd_normed_supported(C.byref(d)) == 1:
             ws, coeff = groupnorm_stats(x, gamma, groups, eps)     # (a, mean) pairs; the apply pass is the convolution's operand fetch
-        elif (x.dtype == torch.float32 and x2 is None and not sk and up_to is None and rowadd is None and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1)
-              and (alpha == 1.0 or bias is None)
-              and w_packed.shape[1] == 9 * c1 and f32split_shape_ok(B, H, W, c1, cout)):
-            # fp32: the norm's apply pass writes the f16 split planes the convolution reads (csrc/f32split.hip) — no fp32 intermediate, no maximum pass
-            planes, pscale, _ = groupnorm_fwd_split_ws(x, gamma, beta, groups, eps, silu=silu, s1=getattr(x, "_e2eft_gn", None))
-            r = _conv2d_f32split(None, w_packed, bias, cout, residual, alpha, out, want,
-                                 "conv3x3s1n B%d %dx%d %d->%d" % (B, hout, wout, c1, cout), planes=planes, scale=pscale)
-            if r is not None:
-                return r
-            x = groupnorm(x, gamma, beta, groups, eps, silu=silu)      # (the library declined after all: the two-pass route)
-            d.ldx1 = _nhwc_ld(x)
         else:
+            if x2 is None and not sk and up_to is None and rowadd is None and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1):
+                r = conv2d_norm_split(x, norm, w_packed, bias, cout, residual, alpha, out, gn_stats, s1=getattr(x, "_e2eft_gn", None))      # (fp32; None: nothing was launched)
+                if r is not None:
+                    return r[0]
             x = groupnorm(x, gamma, beta, groups, eps, silu=silu, x2=x2)      # the norm of the CONCATENATED input; its output is one tensor
             x2 = None
             d.c1, d.ldx1, d.c2, d.ldx2 = x.shape[3], _nhwc_ld(x), 0, 0
     label = _label or "conv%dx%ds%d%s%s B%d %dx%d %d->%d" % (kh, kw, stride, "u" if up_to else "", "n" if coeff is not None else "", B, hout, wout, d.c1 + d.c2, cout)
-    if (F32_SPLIT_ENABLED and x.dtype == torch.float32 and coeff is None and not sk and up_to is None and rowadd is None
+    if (x.dtype == torch.float32 and coeff is None and not sk and up_to is None and rowadd is None
             and (alpha == 1.0 or bias is None)
             and (d.c1 + d.c2) % 64 == 0 and w_packed.shape[1] == kh * kw * (d.c1 + d.c2)):
         r = _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, geom=(kh, kw, stride, tuple(pad)), x2=x2)
@@ -490,23 +510,17 @@ def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None,
             return r
     with _timed("igemm", 2.0 * B * hout * wout * cout * kh * kw * (d.c1 + d.c2), nb, label=label):
         if coeff is not None:
-            buf, nbytes = _gn_buffer(B, hout * wout, cout, x.device) if want else (None, 0)
-            slab = C.c_int32(0)
-            check(lib.e2eft_conv2d_fwd_normed(C.byref(d), _ptr(x), C.c_void_p(coeff), _ptr(beta), 1 if silu else 0, _ptr(w_packed), _ptr(bias), _ptr(rowadd),
-                                              _ptr(residual), _ptr(out), _ptr(buf), nbytes, C.byref(slab), _stream()))
-            if want:
-                _attach_stats(out, buf, slab.value, B, hout * wout, cout)
+            _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_normed(
+                C.byref(d), _ptr(x), C.c_void_p(coeff), _ptr(beta), 1 if silu else 0, _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out), buf, nbytes, slab,
+                _stream()), out, want, B, hout * wout, cout)
             out._e2eft_keep = ws            # (the coefficient workspace lives as long as the launch may: stream-ordered free after the output)
         elif sk:   # few output tiles, long reduction: split-K (the consumer GroupNorm computes its own statistics)
             ws = torch.empty(sk // x.element_size(), dtype=x.dtype, device=x.device)
             check(lib.e2eft_conv2d_fwd_splitk(C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out),
                                               _ptr(ws), sk, _stream()))
         elif want:
-            buf, nbytes = _gn_buffer(B, hout * wout, cout, x.device)
-            slab = C.c_int32(0)
-            check(_lib.load().e2eft_conv2d_fwd_gnstats(C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd),
-                                                       _ptr(residual), _ptr(out), _ptr(buf), nbytes, C.byref(slab), _stream()))
-            _attach_stats(out, buf, slab.value, B, hout * wout, cout)
+            _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_gnstats(
+                C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out), buf, nbytes, slab, _stream()), out, True, B, hout * wout, cout)
         else:
             check(_lib.load().e2eft_conv2d_fwd(C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd),
                                                _ptr(residual), _ptr(out), _stream()))
@@ -536,9 +550,8 @@ def gemm(a, w, bias=None, residual=None, out=None, alpha=1.0, bias_along_m=False
     if residual is not None:
         assert tuple(residual.shape) == (M, N) and residual.dtype == a.dtype
     want = gn_rows_per_image > 0 and GN_STATS_ENABLED and N % 8 == 0 and M % gn_rows_per_image == 0 and not bias_along_m
-    if (F32_SPLIT_ENABLED and a.dtype == torch.float32 and not want and not bias_along_m and (alpha == 1.0 or bias is None) and K % 64 == 0 and M > 256 and N % 8 == 0 and w.is_contiguous()
-            and a.data_ptr() % 16 == 0 and d.lda % 4 == 0 and out.data_ptr() % 16 == 0 and (residual is None or residual.data_ptr() % 16 == 0)
-            and (bias is None or bias.data_ptr() % 16 == 0)):
+    if (a.dtype == torch.float32 and not want and not bias_along_m and (alpha == 1.0 or bias is None) and K % 64 == 0 and M > 256 and N % 8 == 0 and w.is_contiguous()
+            and f32split_operands_ok((a,), (out, residual, bias))):
         # fp32 nn.Linear of whole 256-row tiles: two-term f16 split planes on the f16 matrix pipe (csrc/f32split.hip; igemm5's GEMM mode)
         ds = GemmDesc()
         ds.dtype = _lib.F32
@@ -550,21 +563,15 @@ def gemm(a, w, bias=None, residual=None, out=None, alpha=1.0, bias_along_m=False
         lib = _lib.load()
         if lib.e2eft_gemm_f32split_supported(C.byref(ds)) == 1:
             wsp, inv_sw = f32_split_weight(w, 1, K)
-            planes = torch.empty((M, 2 * K), dtype=torch.float16, device=a.device)
-            scale = torch.empty(4, dtype=torch.float32, device=a.device)
-            with _timed("f32split", 0.0, 12.0 * M * K, label="split2 rows M%d K%d" % (M, K), launches=2):
-                check(lib.e2eft_f32_split2(_ptr(a), M, K, d.lda, _ptr(planes), 2 * K, _ptr(scale), _stream()))
+            planes, scale = f32_split2(a)
             with _timed("igemm", 6.0 * M * N * K, (M * 2 * K * 2 + N * 3 * K * 2 + M * N * 4 * (2 if residual is not None else 1)), label="gemm M%d N%d K%d f32split" % (M, N, K),
                         flops_nominal=2.0 * M * N * K):
                 check(lib.e2eft_gemm_f32split(C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(residual), _ptr(out), _stream()))
             return out
     with _timed("igemm", 2.0 * M * N * K, (M * K + N * K + M * N * (2 if residual is not None else 1)) * a.element_size(), label="gemm M%d N%d K%d" % (M, N, K)):
         if want:
-            buf, nbytes = _gn_buffer(M // gn_rows_per_image, gn_rows_per_image, N, a.device)
-            slab = C.c_int32(0)
-            check(_lib.load().e2eft_gemm_gnstats(C.byref(d), _ptr(a), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), gn_rows_per_image,
-                                                 _ptr(buf), nbytes, C.byref(slab), _stream()))
-            _attach_stats(out, buf, slab.value, M // gn_rows_per_image, gn_rows_per_image, N)
+            _launch_with_stats(lambda buf, nbytes, slab: _lib.load().e2eft_gemm_gnstats(
+                C.byref(d), _ptr(a), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), gn_rows_per_image, buf, nbytes, slab, _stream()), out, True, M // gn_rows_per_image, gn_rows_per_image, N)
         else:
             check(_lib.load().e2eft_gemm(C.byref(d), _ptr(a), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), _stream()))
     return out
@@ -1050,15 +1057,14 @@ def conv2d_wgrad(dy, x, x2, cout, kh, kw, stride, pad, alpha, out=None):
     if not WGRAD_DIRECT or (dy.dtype == torch.float32 and not WGRAD_DIRECT_FP32):
         return None
     _check_cuda(dy, x, x2)
-    cin_all = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
-    if (dy.dtype == torch.float32 and F32_SPLIT_ENABLED and WGRAD_F32_SPLIT and cin_all % 64 == 0 and x.shape[3] % 8 == 0 and cout % 64 == 0 and dy.shape[3] % 8 == 0
-            and _lib.load().e2eft_get_option(_lib.OPT_F32_SPLIT) == 1 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
-            and (x2 is None or (x2.shape[3] % 8 == 0 and x2.data_ptr() % 16 == 0))):
+    cin = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
+    if (dy.dtype == torch.float32 and cin % 64 == 0 and cout % 64 == 0 and _lib.load().e2eft_get_option(_lib.OPT_F32_SPLIT) == 1
+            and f32split_operands_ok((dy, x, x2))):
         # fp32 on the f16 matrix pipe (csrc/f32split.hip): dy s_dy = d0 + d1, x s_x = x0 + x1 (two-term f16 splits, exact to 2^-22); the gradient is the sum of the
         # 16-bit kernel's results for (d0, x0), (d0, x1), (d1, x0), scaled back by the two device scalars — three launches at the f16 rate instead of one at the fp32 rate
         dyp, sdy = f32_split2(dy, keep=True)          # (the data-gradient convolution of the same dY has usually split it already: autograd._Conv2dFn.backward)
         xp, sx = f32_split2(x, x2=x2)                 # (two sources: the planes of their concatenation — the 16-bit kernel then sees ONE source of c1 + c2 channels)
-        c0, c1 = dy.shape[3], cin_all
+        c0, c1 = dy.shape[3], cin
         r = None
         for (a_, b_) in ((dyp[..., :c0], xp[..., :c1]), (dyp[..., :c0], xp[..., c1:]), (dyp[..., c0:], xp[..., :c1])):
             t = conv2d_wgrad(a_, b_, None, cout, kh, kw, stride, pad, alpha)
@@ -1080,7 +1086,6 @@ def conv2d_wgrad(dy, x, x2, cout, kh, kw, stride, pad, alpha, out=None):
     step = max(1, min(B, (0xFFFF0000 - 1) // max(per_img, 1), ((1 << 24) - 1) // pix_img))
     lib = _lib.load()
     parts = []
-    cin = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
     N = kh * kw * cin
     for b0 in range(0, B, step):
         b1 = min(B, b0 + step)
@@ -1143,14 +1148,12 @@ def conv2d_dgrad(dy, w_dgrad, x_shape, c2, kh, kw, stride, pad, up_to, alpha):
     cin = c1 + c2
     assert w_dgrad.shape == (cin, kh * kw * cop) and w_dgrad.is_contiguous() and w_dgrad.dtype == dy.dtype
     label = "dgrad%dx%ds%d B%d %dx%d %d->%d" % (kh, kw, stride, B, hl, wl, cop, cin)
-    if (F32_SPLIT_ENABLED and dy.dtype == torch.float32 and ((kh, kw, stride, tuple(pad)) == (3, 3, 1, (1, 1, 1, 1)) or (kh, kw, stride, tuple(pad)) == (1, 1, 1, (0, 0, 0, 0)))
+    dx = new_nhwc(B, hl, wl, cin, dy.dtype, dy.device)
+    if (dy.dtype == torch.float32 and ((kh, kw, stride, tuple(pad)) == (3, 3, 1, (1, 1, 1, 1)) or (kh, kw, stride, tuple(pad)) == (1, 1, 1, (0, 0, 0, 0)))
             and up_to is None and cop % 64 == 0 and cin % 8 == 0):
         # the data gradient of a 3x3 / stride-1 / pad-1 (or 1x1) convolution IS such a convolution of dY with the flipped, transposed weights: the f16-split route of conv2d
-        dx = new_nhwc(B, hl, wl, cin, dy.dtype, dy.device)
-        if _conv2d_f32split(dy, w_dgrad, None, cin, None, alpha, dx, False, label, keep_planes=True, geom=(kh, kw, 1, tuple(pad))) is not None:
+        if _conv2d_f32split(dy, w_dgrad, None, cin, None, alpha, dx, False, label, geom=(kh, kw, 1, tuple(pad)), keep_planes=True) is not None:
             return dx
-    else:
-        dx = new_nhwc(B, hl, wl, cin, dy.dtype, dy.device)
     with _timed("igemm", 2.0 * B * hl * wl * cin * kh * kw * cop, label=label):
         check(_lib.load().e2eft_conv2d_dgrad(C.byref(d), _ptr(dy), _nhwc_ld(dy), cop, _ptr(w_dgrad), w_dgrad.shape[1], _ptr(dx), _nhwc_ld(dx),
                                              _stream()))

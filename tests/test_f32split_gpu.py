@@ -80,17 +80,17 @@ for (B, H, W, Cc, Co, hb, rs, wide, (kh, kw, st, pd), kern) in cases:
     rd = None if r is None else nhwc(r, torch.float32, dev)
     if r is not None:
         ref = ref + r.double()
-    ops.F32_SPLIT_ENABLED = True
+    _lib.set_option(_lib.OPT_F32_SPLIT, 1)
     y1 = ops.conv2d(xd, wd, bd, Co, kh, kw, st, (pd, pd, pd, pd), residual=rd, gn_stats=True)
     torch.cuda.synchronize()
     k1 = lib.e2eft_debug_last_kernel().decode()
     assert "f32split" in k1 and kern in k1, k1
-    ops.F32_SPLIT_ENABLED = False
+    _lib.set_option(_lib.OPT_F32_SPLIT, 0)
     y2 = ops.conv2d(xd, wd, bd, Co, kh, kw, st, (pd, pd, pd, pd), residual=rd, gn_stats=True)
     torch.cuda.synchronize()
     k2 = lib.e2eft_debug_last_kernel().decode()
     assert "float" in k2 and "f32split" not in k2, k2
-    ops.F32_SPLIT_ENABLED = True
+    _lib.set_option(_lib.OPT_F32_SPLIT, 1)
     e1, e2 = rel_err(to_nchw(y1).double(), ref), rel_err(to_nchw(y2).double(), ref)
     rms1 = ((to_nchw(y1).double() - ref) ** 2).mean().sqrt().item() / ref.abs().max().item()
     rms2 = ((to_nchw(y2).double() - ref) ** 2).mean().sqrt().item() / ref.abs().max().item()
@@ -126,14 +126,14 @@ refw = w64.grad.permute(0, 2, 3, 1).reshape(Co, -1)
 xad, xbd, wd, gd = nhwc(xa, torch.float32, dev), nhwc(xb, torch.float32, dev), pack_conv_weight(w, torch.float32, dev), nhwc(gy, torch.float32, dev)
 res2 = {}
 for on in (True, False):
-    ops.F32_SPLIT_ENABLED = on
+    _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
     y = ops.conv2d(xad, wd, None, Co, 3, 3, 1, (1, 1, 1, 1), x2=xbd)
     torch.cuda.synchronize()
     assert ("f32split" in lib.e2eft_debug_last_kernel().decode()) == on, lib.e2eft_debug_last_kernel()
     dw = ops.conv2d_wgrad(gd, xad, xbd, Co, 3, 3, 1, (1, 1, 1, 1), 1.0)
     torch.cuda.synchronize()
     res2[on] = (to_nchw(y).double(), dw.double().cpu())
-ops.F32_SPLIT_ENABLED = True
+_lib.set_option(_lib.OPT_F32_SPLIT, 1)
 e1, e2 = rel_err(res2[True][0], y64.detach()), rel_err(res2[False][0], y64.detach())
 w1, w2 = rel_err(res2[True][1], refw), rel_err(res2[False][1], refw)
 # the small source's own contribution: the columns of dW that multiply xb
@@ -156,11 +156,11 @@ for (Mr, N, K, hb, rs) in [(1024, 320, 320, True, True), (2048, 1280, 64, False,
     ad, wd = a.to(dev), w.to(dev)
     ys = {}
     for on in (True, False):
-        ops.F32_SPLIT_ENABLED = on
+        _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
         ys[on] = ops.gemm(ad, wd, None if b is None else b.to(dev), None if r is None else r.to(dev))
         torch.cuda.synchronize()
         assert ("f32split" in lib.e2eft_debug_last_kernel().decode()) == on, lib.e2eft_debug_last_kernel()
-    ops.F32_SPLIT_ENABLED = True
+    _lib.set_option(_lib.OPT_F32_SPLIT, 1)
     e1, e2 = rel_err(ys[True].double().cpu(), ref), rel_err(ys[False].double().cpu(), ref)
     print("f32split gemm M%%d N%%d K%%d: max err %%.3e (fp32 MFMA %%.3e)" %% (Mr, N, K, e1, e2), flush=True)
     assert e1 <= max(1.5 * e2, 4e-7), (e1, e2)
@@ -177,13 +177,13 @@ for (B, H, W, Cc, Co, kern) in [(2, 16, 32, 128, 128, "igemm6"), (4, 16, 16, 128
         up.weight.copy_(w); up.bias.copy_(b)
     ys = {}
     for on in (True, False):
-        ops.F32_SPLIT_ENABLED = on
+        _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
         with torch.no_grad():
             ys[on] = ag.conv(up, nhwc(x, torch.float32, dev), up_to=(2 * H, 2 * W))
         torch.cuda.synchronize()
         kk = lib.e2eft_debug_last_kernel().decode()
         assert ("f32split" in kk) == on and (not on or kern in kk), kk
-    ops.F32_SPLIT_ENABLED = True
+    _lib.set_option(_lib.OPT_F32_SPLIT, 1)
     e1, e2 = rel_err(to_nchw(ys[True]).double(), ref), rel_err(to_nchw(ys[False]).double(), ref)
     print("f32split upconv2x %%s: max err %%.3e (fp32 MFMA %%.3e)" %% ((B, H, W, Cc, Co), e1, e2), flush=True)
     assert e1 <= max(1.5 * e2, 4e-7), (e1, e2)
@@ -199,11 +199,11 @@ for (B, H, W, Cc, Co, k) in [(2, 24, 24, 320, 320, 3), (4, 16, 32, 64, 128, 1), 
     xd, gd = nhwc(x, torch.float32, dev), nhwc(gy, torch.float32, dev)
     rs = {}
     for on in (True, False):
-        ops.WGRAD_F32_SPLIT = on
+        _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
         rs[on] = ops.conv2d_wgrad(gd, xd, None, Co, k, k, 1, (k // 2,) * 4, 1.0)
         torch.cuda.synchronize()
         assert rs[on] is not None
-    ops.WGRAD_F32_SPLIT = True
+    _lib.set_option(_lib.OPT_F32_SPLIT, 1)
     e1, e2 = rel_err(rs[True].double().cpu(), ref), rel_err(rs[False].double().cpu(), ref)
     print("f32split wgrad %%s: max err %%.3e (fp32 MFMA %%.3e)" %% ((B, H, W, Cc, Co, k), e1, e2), flush=True)
     assert e1 <= max(1.5 * e2, 4e-7), (e1, e2)
@@ -219,11 +219,11 @@ ref = F.conv2d(F.silu(F.group_norm(x.double(), 32, gamma.double(), beta.double()
 xd, wd = nhwc(x, torch.float32, dev), pack_conv_weight(w, torch.float32, dev)
 yn = {}
 for on in (True, False):
-    ops.F32_SPLIT_ENABLED = on
+    _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
     yn[on] = ops.conv2d(xd, wd, b.to(dev), Co, 3, 3, 1, (1, 1, 1, 1), norm=(gamma.to(dev), beta.to(dev), 32, 1e-5, True))
     torch.cuda.synchronize()
     assert ("f32split" in lib.e2eft_debug_last_kernel().decode()) == on
-ops.F32_SPLIT_ENABLED = True
+_lib.set_option(_lib.OPT_F32_SPLIT, 1)
 en1, en2 = rel_err(to_nchw(yn[True]).double(), ref), rel_err(to_nchw(yn[False]).double(), ref)
 print("norm -> planes -> conv: max err %%.3e (fp32 GroupNorm pass + fp32 MFMA %%.3e)" %% (en1, en2), flush=True)
 assert en1 <= max(1.5 * en2, 6e-7), (en1, en2)
@@ -242,13 +242,13 @@ with torch.no_grad():
 conv.weight.requires_grad_(False); conv.bias.requires_grad_(False)       # the frozen VAE: only the data gradient
 res = {}
 for on in (True, False):
-    ops.F32_SPLIT_ENABLED = on
+    _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
     xd = nhwc(x, torch.float32, dev).requires_grad_(True)
     y = ag.conv(conv, xd)
     y.backward(nhwc(gy, torch.float32, dev))
     torch.cuda.synchronize()
     res[on] = (to_nchw(y.detach()).double(), to_nchw(xd.grad).double(), lib.e2eft_debug_last_kernel().decode())
-ops.F32_SPLIT_ENABLED = True
+_lib.set_option(_lib.OPT_F32_SPLIT, 1)
 x64 = x.double().requires_grad_(True)
 y64 = F.conv2d(x64, w.double(), b.double(), padding=1)
 y64.backward(gy.double())
@@ -269,13 +269,13 @@ x = torch.randn(2, 128, 16, 64, generator=g) * 2.0
 gy = torch.randn(2, 128, 16, 64, generator=g)
 out = {}
 for on in (True, False):
-    ops.F32_SPLIT_ENABLED = on
+    _lib.set_option(_lib.OPT_F32_SPLIT, int(on))
     xd = nhwc(x, torch.float32, dev).requires_grad_(True)
     y = blk.nhwc(xd)
     y.backward(nhwc(gy, torch.float32, dev))
     torch.cuda.synchronize()
     out[on] = (to_nchw(y.detach()).double(), to_nchw(xd.grad).double())
-ops.F32_SPLIT_ENABLED = True
+_lib.set_option(_lib.OPT_F32_SPLIT, 1)
 b64 = torch.nn.Module()
 x64 = x.double().requires_grad_(True)
 sd = {k: v.detach().double().cpu() for k, v in blk.state_dict().items()}
