@@ -10,8 +10,7 @@
 // so running max / sum / rescale are lane-local (one cross-half exchange per tile for the max), and the P
 // operand of the second MFMA is exactly the register set the first MFMA produced (no LDS round trip):
 // the key -> MFMA-k-slot permutation this implies is applied to the V fragment addresses instead.
-#include "common.h"
-#include <type_traits>
+#include "gfx950.h"
 
 namespace e2eft {
 
@@ -33,50 +32,11 @@ struct AttnParams {
     float* lse;  // optional [batch][heads][nq]: log2-sum-exp of the scaled scores (saved for e2eft_attn_bwd)
 };
 
-template <typename T> struct MmaA;
-template <> struct MmaA<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaA<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bhalf2v __attribute__((ext_vector_type(2)));
-
-// pack two fp32 into one dword of T with a single v_cvt_pk_{f16,bf16}_f32
-template <typename T> struct Pk;
-template <> struct Pk<f16> {
-    __device__ static __forceinline__ uint32_t pack(float lo, float hi) {
-        const float2v f = {lo, hi};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, half2v));
-    }
-};
-template <> struct Pk<bf16> {
-    __device__ static __forceinline__ uint32_t pack(float lo, float hi) {
-        const float2v f = {lo, hi};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bhalf2v));
-    }
-};
-template <typename T> __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return Pk<T>::pack(lo, hi); }
-
-typedef short short4va __attribute__((ext_vector_type(4)));
-// ds_read_b64_tr_b16: lane i of a 16-lane group supplies the address of 4 consecutive 16-bit elements (row i >> 2, columns 4 (i & 3) .. + 3 of a
-// 4 x 16 block) and receives column i of the block, rows 0 .. 3 — V stays row-major in LDS and is transposed on the way to the MFMA's A operand
-__device__ __forceinline__ u32x2 tr_read(const char* p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4va*)p));
-}
-
 // 1-D grid of nqb * heads * batch workgroups (nqb = ceil(nq / (128 QB))).  JOINT: keys come from kv_nseg = 2 batch-strided segments
 // (GeoWizard), which costs an integer division per loaded row; the plain case indexes keys linearly.
 // QB = query blocks of 32 rows per wave (1).  (Round 3 measured QB = 2 — 64 rows per wave, every K / V^T fragment read and every loader store
 // serving two MFMAs: 742 against 726 TF/s at 9216 keys, +2 %: LDS / loader issue slots are not what binds; the per-score VALU work is — below.)
-// Block -> (image, head, query block): all query blocks of one (image, head) run on ONE XCD (block id mod 8 = XCD, MI355X_MICROARCH.md), so the
-// head's K / V (2.4 MB at 9216 keys) is fetched into one L2 instead of eight: PMC had 3.5x the algorithmic HBM bytes with the plain map.
+// Block -> (image, head, query block): xcd_pair_block_map (gfx950.h) — all query blocks of one (image, head) run on ONE XCD.
 // Measured dead ends: s_setprio(1) around the MFMA phases (771 -> 697 TF/s), v_dot2c row sums on the packed probabilities (717).
 // launch_bounds(256, 2): two workgroups per CU caps the wave at 256 registers, which makes the compiler keep the MFMA
 // accumulators in VGPRs — with the 512-register budget it parks O^T / S^T in AGPRs and pays a v_accvgpr_read + write per
@@ -96,23 +56,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * KVBUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
-    // ---- XCD-aware block map: pair = (image, head); pairs are dealt to the eight XCDs round-robin, each XCD walks its pairs' query blocks
     int b, head, qblk;
-    {
-        const int npair = p.batch * p.heads, nqb = p.nqb;
-        const int L = blockIdx.x, full = (npair >> 3) << 3;          // pairs covered by complete rounds of eight
-        if (L < full * nqb) {
-            const int xcd = L & 7, idx = L >> 3;
-            const int pr = (idx / nqb) * 8 + xcd;
-            qblk = idx - (idx / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        } else {                                                      // the remaining (< 8) pairs: plain order
-            const int r = L - full * nqb;
-            const int pr = full + r / nqb;
-            qblk = r - (r / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        }
-    }
+    xcd_pair_block_map(p.batch, p.heads, p.nqb, b, head, qblk);
     const int q0 = qblk * (128 * QB) + wave * (32 * QB);
 
     const T* __restrict__ Q = (const T*)p.q;
@@ -221,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     const char* vb = smem + KTILE + vfrag + (kt2 * 32 + 16 * s2) * VROW;
-                    const u32x2 v0 = tr_read(vb + dt * 64), v1 = tr_read(vb + 8 * VROW + dt * 64);
+                    const u32x2 v0 = lds_read_tr16(vb + dt * 64), v1 = lds_read_tr16(vb + 8 * VROW + dt * 64);
                     hv[kt2][s2][dt] = u32x4{v0[0], v0[1], v1[0], v1[1]};
                 }
         }
@@ -241,13 +186,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         for (int kt2 = 0; kt2 < 2; ++kt2) {     // (round 4: alternating the two blocks' MFMAs — no dependent neighbours — measured 781 against 795 TF/s this way round)
             const char* row = sk + (kt2 * 32 + l31) * KROW + hh * 16;
             if constexpr (PROBE_NOLDS) {
-                s[kt2] = MmaA<T>::run(hk[kt2][0], qf[0][0], cinit);
+                s[kt2] = Mma32x32x16<T>::run(hk[kt2][0], qf[0][0], cinit);
 #pragma unroll
-                for (int ds = 1; ds < 4; ++ds) s[kt2] = MmaA<T>::run(hk[kt2][ds], qf[0][ds], s[kt2]);
+                for (int ds = 1; ds < 4; ++ds) s[kt2] = Mma32x32x16<T>::run(hk[kt2][ds], qf[0][ds], s[kt2]);
             } else {
-                s[kt2] = MmaA<T>::run(*reinterpret_cast<const u32x4*>(row), qf[0][0], cinit);
+                s[kt2] = Mma32x32x16<T>::run(*reinterpret_cast<const u32x4*>(row), qf[0][0], cinit);
 #pragma unroll
-                for (int ds = 1; ds < 4; ++ds) s[kt2] = MmaA<T>::run(*reinterpret_cast<const u32x4*>(row + ds * 32), qf[0][ds], s[kt2]);
+                for (int ds = 1; ds < 4; ++ds) s[kt2] = Mma32x32x16<T>::run(*reinterpret_cast<const u32x4*>(row + ds * 32), qf[0][ds], s[kt2]);
             }
         }
         // ---- mask keys beyond nk_total (last tile only) ----
@@ -296,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
             for (int w = 0; w < 8; ++w)
-                pw[kt2][w] = Pk<T>::pack(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
+                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
         }
 
         // ---- O^T += V^T P^T and l^T += 1 P^T ----
@@ -310,15 +255,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     if constexpr (PROBE_NOLDS) {
-                        o[dt] = MmaA<T>::run(hv[kt2][s2][dt], pf, o[dt]);
+                        o[dt] = Mma32x32x16<T>::run(hv[kt2][s2][dt], pf, o[dt]);
                     } else {
-                        const u32x2 v0 = tr_read(vb + dt * 64);
-                        const u32x2 v1 = tr_read(vb + 8 * VROW + dt * 64);
+                        const u32x2 v0 = lds_read_tr16(vb + dt * 64);
+                        const u32x2 v1 = lds_read_tr16(vb + 8 * VROW + dt * 64);
                         const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
-                        o[dt] = MmaA<T>::run(vf, pf, o[dt]);
+                        o[dt] = Mma32x32x16<T>::run(vf, pf, o[dt]);
                     }
                 }
-                lacc = MmaA<T>::run(ones_v, pf, lacc);
+                lacc = Mma32x32x16<T>::run(ones_v, pf, lacc);
             }
         }
 
@@ -352,56 +297,33 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
 // attn_fwd_dma_kernel — the same arithmetic per (query, key) as attn_fwd_kernel, instruction for instruction (swapped MFMAs, the same accumulation chains, scores
 // relative to a reference maximum, row sums on the matrix pipe, deferred rescale: results are bit-identical), with another K / V delivery:
 //   * the 64-key tiles arrive by LDS-DMA (`buffer_load ... lds`: one wave instruction = 8 key rows of 128 data bytes = 1 KiB, two K and two V pieces per wave and
-//     tile) into a THREE-stage ring — no global -> VGPR -> ds_write staging (attn_fwd_kernel spends 4 global loads, 4 ds_write_b128 and 16 registers per thread and
-//     tile on it, and stalls on vmcnt(0) in front of the stores when a load is late); the pieces of tile t + 2 are requested before tile t multiplies;
+//     tile) into a TWO-stage ring (NSTAGE = 2) — no global -> VGPR -> ds_write staging (attn_fwd_kernel spends 4 global loads, 4 ds_write_b128 and 16 registers per thread and
+//     tile on it, and stalls on vmcnt(0) in front of the stores when a load is late); the pieces of tile t + 1 are requested before tile t multiplies;
 //   * LDS rows are the 128 data bytes (a DMA piece is lane-linear, there is no row padding), the bank spread comes from XOR swizzles on the SOURCE side, undone in
 //     the fragment addresses: K chunk ^ ((row >> 1) & 7) (conflict-free ds_read_b128, as igemm2.hip), V chunk ^ (((row >> 1) & 1) << 2) (the four key rows of a
 //     transpose read land on four different 64-byte windows, as wgrad.hip);
-//   * one counted wait (this wave's pieces of tile t + 1; those of tile t + 2 may still be in flight) and one barrier per tile, as before.
-// Still 4 waves and two workgroups per CU: the two waves of a SIMD belong to DIFFERENT workgroups, drift apart and overlap their MFMA and softmax phases — the
-// 8-wave form of this delivery (one workgroup, both waves of a SIMD in lockstep behind one barrier) measured 765 against 795 TF/s (profiles/r04_attention_experiments.md).
+//   * one wait (this wave's pieces of tile t + 1: nothing younger is in flight) and one barrier per tile, as before.
+// Still 4 waves and two workgroups per CU: the two waves of a SIMD belong to DIFFERENT workgroups, drift apart and overlap their MFMA and softmax phases.
+// Measured dead ends, the reason this kernel carries no switch for them: the 8-wave form of this delivery (one workgroup, both waves of a SIMD in lockstep behind
+// one barrier): 765 against 795 TF/s (profiles/r04_attention_experiments.md); two 64-key tiles per barrier (two stages of two tiles, 64 KiB, half the barriers —
+// asked for because the probe with the tile pinned in LDS, no loads AND no barrier, runs at 957 against 800 TF/s): not faster; three stages of one tile, tile
+// t + 2 requested while tile t multiplies: 749-755 against 772-776 TF/s with the two stages below.
 // K / V are addressed through one 32-bit buffer descriptor per tensor: the launcher takes this kernel only below 3.5 GB.
+// The body below repeats attn_fwd_kernel's and every edit goes into both (tests/test_attn_dma_gpu.py asserts the bit identity): shared inline functions change
+// the generated code of both kernels and raise attn_fwd_kernel's register count (profiles/gfx950_header_isa_compare.txt).
 namespace adma {
 constexpr int KT = 64, HALF = KT * 128, STAGE = 2 * HALF;      // one 64-key tile: 8 KiB of K rows, 8 KiB of V rows
-constexpr unsigned OOB = 0xF0000000u, RECORDS = 0xE0000000u;
+constexpr int NSTAGE = 2, LDS = NSTAGE * STAGE;                // 32 KiB
 }
-typedef __attribute__((address_space(3))) void* lptr_a_t;
-// one LDS-DMA piece (64 lanes x 16 B -> 1 KiB at m0) from asm: issued through the builtin the compiler would count it and drain vmcnt(0) in front of LDS reads it
-// cannot prove disjoint; the kernel counts its own pieces.  m0 is saved and restored.
-__device__ __forceinline__ void dma_piece_a(const __amdgpu_buffer_rsrc_t& rs, const unsigned voff, const unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rs), "s"(lds_addr) : "memory");
-}
-
-// TPB = 64-key tiles per barrier.  1: three stages of one tile (48 KiB), tile t + 2 requested while tile t multiplies; 2: two stages of two tiles (64 KiB), the next
-// pair requested while this pair multiplies — half the barriers (the measurement that asked for it: with TPB = 1 the DMA delivery runs exactly as fast as the
-// register-staged kernel, 802 against 800 TF/s, while the probe with the tile pinned in LDS — no loads AND no barrier — runs at 957: what costs is the
-// synchronisation of the four waves once per tile, not the instructions that move the data).
-template <typename T, bool JOINT, int TPB>
+template <typename T, bool JOINT>
 __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p) {
     using namespace adma;
-    constexpr int NSTAGE = 2, SSTAGE = TPB * STAGE, LDS = NSTAGE * SSTAGE;      // 32 KiB at TPB = 1: measured 772-776 against 749-752 TF/s (production) and 749-755 (three stages)
     __shared__ __attribute__((aligned(1024))) char smem[LDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
     int b, head, qblk;
-    {   // XCD-aware block map, as attn_fwd_kernel
-        const int npair = p.batch * p.heads, nqb = p.nqb;
-        const int L = blockIdx.x, full = (npair >> 3) << 3;
-        if (L < full * nqb) {
-            const int xcd = L & 7, idx = L >> 3;
-            const int pr = (idx / nqb) * 8 + xcd;
-            qblk = idx - (idx / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        } else {
-            const int r = L - full * nqb;
-            const int pr = full + r / nqb;
-            qblk = r - (r / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        }
-    }
+    xcd_pair_block_map(p.batch, p.heads, p.nqb, b, head, qblk);
     const int q0 = qblk * 128 + wave * 32;
     const T* __restrict__ Q = (const T*)p.q;
 
@@ -410,31 +332,28 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
     const int lrow = 8 * wave + (lane >> 3);
     const unsigned kch = (unsigned)(((lane & 7) ^ ((lrow >> 1) & 7)) * 16), vch = (unsigned)(((lane & 7) ^ (((lrow >> 1) & 1) << 2)) * 16);
     const int kvb0 = b % p.kv_bmod;
-    const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.k + head * 64), 0, RECORDS, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.v + head * 64), 0, RECORDS, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsk = whole_range_rsrc((const T*)p.k + head * 64);
+    const __amdgpu_buffer_rsrc_t rsv = whole_range_rsrc((const T*)p.v + head * 64);
     const unsigned ldkb = (unsigned)p.ldk * (unsigned)sizeof(T), ldvb = (unsigned)p.ldv * (unsigned)sizeof(T);
-    const unsigned lds0 = (unsigned)(uintptr_t)((lptr_a_t)smem);
-    auto fire = [&](const int G) {       // the 4 TPB pieces of tile group G this wave owns; keys beyond the last one fetch zeros (their scores are masked below)
+    const unsigned lds0 = (unsigned)(uintptr_t)((lds_ptr_t)smem);
+    auto fire = [&](const int t) {       // the 4 pieces of tile t this wave owns; keys beyond the last one fetch zeros (their scores are masked below)
+        const unsigned dst0 = lds0 + (unsigned)((t % NSTAGE) * STAGE + wave * 1024);
 #pragma unroll
-        for (int sub = 0; sub < TPB; ++sub) {
-            const unsigned dst0 = lds0 + (unsigned)((G % NSTAGE) * SSTAGE + sub * STAGE + wave * 1024);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int key = (G * TPB + sub) * KT + lrow + 32 * i;
-                unsigned row;
-                if (JOINT) {
-                    const int seg = key / p.nk_seg;
-                    row = (unsigned)((kvb0 + seg * p.kv_bmod) * p.nk_seg + (key - seg * p.nk_seg));
-                } else {
-                    row = (unsigned)(kvb0 * p.nk_seg + key);
-                }
-                const bool ok = key < p.nk_total;
-                dma_piece_a(rsk, ok ? row * ldkb + kch : OOB, dst0 + (unsigned)(i * 4096));
-                dma_piece_a(rsv, ok ? row * ldvb + vch : OOB, dst0 + (unsigned)(i * 4096 + HALF));
+        for (int i = 0; i < 2; ++i) {
+            const int key = t * KT + lrow + 32 * i;
+            unsigned row;
+            if (JOINT) {
+                const int seg = key / p.nk_seg;
+                row = (unsigned)((kvb0 + seg * p.kv_bmod) * p.nk_seg + (key - seg * p.nk_seg));
+            } else {
+                row = (unsigned)(kvb0 * p.nk_seg + key);
             }
+            const bool ok = key < p.nk_total;
+            lds_dma_piece(rsk, ok ? row * ldkb + kch : SRD_OOB, dst0 + (unsigned)(i * 4096));
+            lds_dma_piece(rsv, ok ? row * ldvb + vch : SRD_OOB, dst0 + (unsigned)(i * 4096 + HALF));
         }
     };
-    const int nt = (p.nk_total + KT - 1) / KT, ng = (nt + TPB - 1) / TPB;
+    const int nt = (p.nk_total + KT - 1) / KT;
     fire(0);
 
     // ---- Q'^T fragments (B operand), pre-multiplied by scale * log2(e)
@@ -474,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
     u32x4 ones_v = ones;
     asm volatile("" : "+v"(ones_v));
 
-    // group 0 (this wave's pieces; with TPB = 1 the four of tile 1 may still be in flight), then everybody's
+    // tile 0: this wave's pieces, then everybody's
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -485,9 +404,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2) {
             const char* row = st + kt2 * 32 * 128;
-            s[kt2] = MmaA<T>::run(*reinterpret_cast<const u32x4*>(row + kofs[0]), qf[0], cinit);
+            s[kt2] = Mma32x32x16<T>::run(*reinterpret_cast<const u32x4*>(row + kofs[0]), qf[0], cinit);
 #pragma unroll
-            for (int ds = 1; ds < 4; ++ds) s[kt2] = MmaA<T>::run(*reinterpret_cast<const u32x4*>(row + kofs[ds]), qf[ds], s[kt2]);
+            for (int ds = 1; ds < 4; ++ds) s[kt2] = Mma32x32x16<T>::run(*reinterpret_cast<const u32x4*>(row + kofs[ds]), qf[ds], s[kt2]);
         }
         if (t * 64 + 64 > p.nk_total) {
 #pragma unroll
@@ -524,7 +443,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
             for (int w = 0; w < 8; ++w)
-                pw[kt2][w] = Pk<T>::pack(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
+                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
 
         // ---- O^T += V^T P^T and l^T += 1 P^T ----
 #pragma unroll
@@ -535,26 +454,21 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
                 const char* vb = st + (kt2 * 32 + 16 * s2) * 128;
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const u32x2 v0 = tr_read(vb + vofs[dt]);
-                    const u32x2 v1 = tr_read(vb + 8 * 128 + vofs[dt]);
+                    const u32x2 v0 = lds_read_tr16(vb + vofs[dt]);
+                    const u32x2 v1 = lds_read_tr16(vb + 8 * 128 + vofs[dt]);
                     const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
-                    o[dt] = MmaA<T>::run(vf, pf, o[dt]);
+                    o[dt] = Mma32x32x16<T>::run(vf, pf, o[dt]);
                 }
-                lacc = MmaA<T>::run(ones_v, pf, lacc);
+                lacc = Mma32x32x16<T>::run(ones_v, pf, lacc);
             }
         }
     };
 
-    for (int G = 0; G < ng; ++G) {
-        // the stage being refilled held group G - 1 (TPB = 2) / G - 1 of three (TPB = 1): every wave finished reading it before the barrier that closed iteration G - 1
-        constexpr int AHEAD = 1;
-        if (G + AHEAD < ng) fire(G + AHEAD);
-        const char* st = smem + (G % NSTAGE) * SSTAGE;
-        tile(G * TPB, st);
-        if constexpr (TPB == 2) {
-            if (G * TPB + 1 < nt) tile(G * TPB + 1, st + STAGE);      // (uniform)
-        }
-        if (G + 1 < ng) {   // this wave's pieces of group G + 1 have landed (TPB = 1: those of G + 2 may fly); after the barrier everybody's have, and everybody is done with this stage
+    for (int t = 0; t < nt; ++t) {
+        // the stage being refilled held tile t - 1: every wave finished reading it before the barrier that closed iteration t - 1
+        if (t + 1 < nt) fire(t + 1);
+        tile(t, smem + (t % NSTAGE) * STAGE);
+        if (t + 1 < nt) {   // this wave's pieces of tile t + 1 have landed; after the barrier everybody's have, and everybody is done with this stage
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -619,7 +533,7 @@ extern "C" int e2eft_attn_fwd_lse(const E2eftAttnDesc* d, const void* q, const v
     // LDS-DMA delivery (E2EFT_OPT_ATTN_DMA): K / V addressed through one 32-bit buffer descriptor each
     const long kv_rows = (long)d->kv_bmod * d->kv_nseg * d->nk_seg;
     const bool dma = option(E2EFT_OPT_ATTN_DMA) != 0 && kv_rows * (d->ldk > d->ldv ? d->ldk : d->ldv) * 2 < 0xE0000000L;
-#define E2EFT_ATTN_LAUNCH(TT, JJ) do { if (dma) hipLaunchKernelGGL((attn_fwd_dma_kernel<TT, JJ, 1>), grid, dim3(256), 0, s, p); \
+#define E2EFT_ATTN_LAUNCH(TT, JJ) do { if (dma) hipLaunchKernelGGL((attn_fwd_dma_kernel<TT, JJ>), grid, dim3(256), 0, s, p); \
                                        else hipLaunchKernelGGL((attn_fwd_kernel<TT, JJ, 1>), grid, dim3(256), 0, s, p); } while (0)
     if (d->dtype == E2EFT_F16) {
         if (joint) E2EFT_ATTN_LAUNCH(f16, true); else E2EFT_ATTN_LAUNCH(f16, false);

@@ -15,7 +15,7 @@
 // owner-computes kernels (dK / dV with lane = key, dQ with lane = query), probabilities recomputed from q, k and the forward's base-2 log-sum-exp.
 // LDS tiles are [64 rows][68 floats]: 272-byte rows keep ds_read_b128 of 16 different rows conflict-free (row starts 4 dwords apart mod 64) and 16-byte alignment.
 // MFMA work per 32 x 32 (query, key) block: forward 2 x 32 instructions, backward 7 x 32; softmax VALU (one v_exp_f32 per score) is ~5 % beside them.
-#include "common.h"
+#include "gfx950.h"
 
 namespace e2eft {
 
@@ -89,21 +89,7 @@ __global__ __launch_bounds__(256, 2) void attn32_fwd_kernel(const Attn32Params p
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
     int b, head, qblk;
-    {   // XCD-aware block map (attn.hip): all query blocks of one (image, head) on one XCD
-        const int npair = p.batch * p.heads, nqb = p.nqb;
-        const int L = blockIdx.x, full = (npair >> 3) << 3;
-        if (L < full * nqb) {
-            const int xcd = L & 7, idx = L >> 3;
-            const int pr = (idx / nqb) * 8 + xcd;
-            qblk = idx - (idx / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        } else {
-            const int r = L - full * nqb;
-            const int pr = full + r / nqb;
-            qblk = r - (r / nqb) * nqb;
-            b = pr / p.heads; head = pr - b * p.heads;
-        }
-    }
+    xcd_pair_block_map(p.batch, p.heads, p.nqb, b, head, qblk);      // all query blocks of one (image, head) on one XCD
     const int qr = qblk * 128 + wave * 32 + l31;
     const bool qok = qr < p.nq;
 

@@ -28,7 +28,7 @@
 //     literal accumulation registers (attn512_regs.inc, generated).  Left to the register allocator the 16 blocks were rotated through
 //     ~200 v_accvgpr_mov / read / write per tile at the loop's phi nodes (and spilled 445 registers with an unfenced rescale).
 // Work per tile and wave: 32 + 32 MFMAs 32x32x16 (2048 cycles) against 16 exponentials per lane — MFMA-bound, unlike d = 64.
-#include "common.h"
+#include "gfx950.h"
 #include "attn512_regs.inc"
 #include <type_traits>
 
@@ -58,38 +58,6 @@ struct Attn5Params {
     float* part_o;    // [n_split blocks][128][512] fp32: O^T in the block's own reference frame
     float* part_ml;   // [n_split blocks][128][2]: (reference maximum in the exponent domain, row sum)
 };
-
-template <typename T> struct Mma512;
-template <> struct Mma512<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-    __device__ static __forceinline__ uint32_t pack(float lo, float hi) {
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 f = {lo, hi};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, half2v));
-    }
-};
-template <> struct Mma512<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-    __device__ static __forceinline__ uint32_t pack(float lo, float hi) {
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-        const f2 f = {lo, hi};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-    }
-};
-
-typedef __attribute__((address_space(3))) void* lptr512_t;
-typedef short short4v512 __attribute__((ext_vector_type(4)));
-template <int V> using IC512 = std::integral_constant<int, V>;
-// ds_read_b64_tr_b16: lane i of a 16-lane group supplies the address of 4 consecutive 16-bit elements (row i >> 2, columns 4 (i & 3) .. + 3
-// of a 4 x 16 block) and receives column i of the block: rows 0 .. 3
-__device__ __forceinline__ u32x2 tr_read512(const char* p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v512*)p));
-}
 
 // O^T block DT (rows 32 DT .. + 31 of d, this wave's 32 queries) += A (V^T fragment) x B (P^T fragment), accumulator a[16 DT : 16 DT + 15].
 // "s_nop 1": a VALU-written operand register needs two wait states in front of the MFMA that reads it, and inside an asm statement nobody
@@ -125,16 +93,6 @@ template <typename T> __device__ __forceinline__ void s_mma(floatx16& acc, const
     if constexpr (std::is_same<T, f16>::value) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
     else asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
 }
-// One row of a K / V tile by LDS-DMA, issued from asm: the compiler's waitcnt pass drains vmcnt in front of every LDS read it cannot prove
-// disjoint from a pending LDS-DMA it knows of (here: all of them, once per phase) — what it does not see it does not wait for; the wave
-// counts its own DMAs (one vmcnt(0) in front of the barrier that ends an iteration).  m0 = LDS byte address of the row (wave-uniform), the
-// lanes land at m0 + 16 lane; "s_nop 0": m0 written by SALU -> LDS-DMA needs one wait state.  m0 is saved and restored (compiler-reserved).
-__device__ __forceinline__ void dma_row512(const __amdgpu_buffer_rsrc_t& rs, const unsigned voff, const unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rs), "s"(lds_addr) : "memory");
-}
-
 // grid (ceil(nq / 128), batch), 256 threads = 4 waves x 32 queries, one wave per SIMD
 template <typename T>
 __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
@@ -173,19 +131,19 @@ __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
     const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.k + (long)b * p.nk * p.ldk), 0, kbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.v + (long)b * p.nk * p.ldv), 0, vbytes, 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
-    const unsigned lds0 = (unsigned)(uintptr_t)((lptr512_t)smem);
+    const unsigned lds0 = (unsigned)(uintptr_t)((lds_ptr_t)smem);
     const unsigned krow_b = (unsigned)(p.ldk * (int)sizeof(T)), vrow_b = (unsigned)(p.ldv * (int)sizeof(T));
     auto dma_k_row = [&](const int t, const int buf, const int i) {     // row wave + 4 i of K tile t
         const int r = wave + 4 * i;
         const unsigned key = (unsigned)(k_begin + t * KT + r);
         const unsigned off = key < (unsigned)p.nk ? key * krow_b + lane16 : 0xFFFFFFF0u;
-        dma_row512(rsk, off, lds0 + (unsigned)(buf * KTILE + r * KP));
+        lds_dma_piece(rsk, off, lds0 + (unsigned)(buf * KTILE + r * KP));
     };
     auto dma_v_row = [&](const int t, const int buf, const int i) {
         const int r = wave + 4 * i;
         const unsigned key = (unsigned)(k_begin + t * KT + r);
         const unsigned off = key < (unsigned)p.nk ? key * vrow_b + lane16 : 0xFFFFFFF0u;
-        dma_row512(rsv, off, lds0 + (unsigned)(2 * KTILE + buf * VTILE + r * VP));
+        lds_dma_piece(rsv, off, lds0 + (unsigned)(2 * KTILE + buf * VTILE + r * VP));
     };
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the Q loads: from here on the only VMEM operations in flight are the hand-counted DMA rows
@@ -236,14 +194,14 @@ __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
             const float e = __builtin_amdgcn_exp2f(fmaf(s[r], p.c, -mc));
             psum += e;
             if constexpr ((r & 1) == 0) e_lo = e;
-            else np[r >> 1] = Mma512<T>::pack(e_lo, e);
+            else np[r >> 1] = pack2<T>(e_lo, e);
         } else if constexpr (n == 26) l_run += psum;
     };
     auto softmax_plain = [&]() {
-        vslice(IC512<0>{}); vslice(IC512<1>{}); vslice(IC512<2>{}); vslice(IC512<3>{}); vslice(IC512<4>{}); vslice(IC512<5>{}); vslice(IC512<6>{});
-        vslice(IC512<7>{}); vslice(IC512<8>{}); vslice(IC512<9>{}); vslice(IC512<10>{}); vslice(IC512<11>{}); vslice(IC512<12>{}); vslice(IC512<13>{});
-        vslice(IC512<14>{}); vslice(IC512<15>{}); vslice(IC512<16>{}); vslice(IC512<17>{}); vslice(IC512<18>{}); vslice(IC512<19>{}); vslice(IC512<20>{});
-        vslice(IC512<21>{}); vslice(IC512<22>{}); vslice(IC512<23>{}); vslice(IC512<24>{}); vslice(IC512<25>{}); vslice(IC512<26>{});
+        vslice(IConst<0>{}); vslice(IConst<1>{}); vslice(IConst<2>{}); vslice(IConst<3>{}); vslice(IConst<4>{}); vslice(IConst<5>{}); vslice(IConst<6>{});
+        vslice(IConst<7>{}); vslice(IConst<8>{}); vslice(IConst<9>{}); vslice(IConst<10>{}); vslice(IConst<11>{}); vslice(IConst<12>{}); vslice(IConst<13>{});
+        vslice(IConst<14>{}); vslice(IConst<15>{}); vslice(IConst<16>{}); vslice(IConst<17>{}); vslice(IConst<18>{}); vslice(IConst<19>{}); vslice(IConst<20>{});
+        vslice(IConst<21>{}); vslice(IConst<22>{}); vslice(IConst<23>{}); vslice(IConst<24>{}); vslice(IConst<25>{}); vslice(IConst<26>{});
     };
 
     // ---- S^T[key, q] = K(t) Q^T over d = 512: 32 MFMAs on two alternating accumulators (a dependent chain pays for every filler); the 16 DMA
@@ -288,23 +246,23 @@ __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
         const u32x4 pf0 = {pw[0], pw[1], pw[2], pw[3]}, pf1 = {pw[4], pw[5], pw[6], pw[7]};
         auto frag = [&](auto nc) -> u32x4 {                       // block n = 16 s2 + dt
             constexpr int n = decltype(nc)::value, s2 = n >> 4, dt = n & 15;
-            const u32x2 v0 = tr_read512(sv + (16 * s2) * VP + dt * 64);
-            const u32x2 v1 = tr_read512(sv + (16 * s2 + 8) * VP + dt * 64);
+            const u32x2 v0 = lds_read_tr16(sv + (16 * s2) * VP + dt * 64);
+            const u32x2 v1 = lds_read_tr16(sv + (16 * s2 + 8) * VP + dt * 64);
             return u32x4{v0[0], v0[1], v1[0], v1[1]};
         };
-        u32x4 f0 = frag(IC512<0>{}), f1 = frag(IC512<1>{}), f2;
+        u32x4 f0 = frag(IConst<0>{}), f1 = frag(IConst<1>{}), f2;
         float idle = 0.f;
         auto step = [&](auto nc, u32x4& cur, u32x4& nxt2) {
             constexpr int n = decltype(nc)::value;
-            if constexpr (n + 2 < 32) nxt2 = frag(IC512<(n + 2 < 32 ? n + 2 : 0)>{});
+            if constexpr (n + 2 < 32) nxt2 = frag(IConst<(n + 2 < 32 ? n + 2 : 0)>{});
             // slices 0-8 carry the running tile maximum, slices 10-25 the probability sum: the value the slice behind this MFMA continues
             pv_block<T, (n & 15)>(cur, n < 16 ? pf0 : pf1, !SM ? idle : (n <= 9 ? mx : psum));
-            if constexpr (SM) vslice(IC512<n>{});
+            if constexpr (SM) vslice(IConst<n>{});
         };
         // three fragment registers rotate: block n in `cur`, n + 1 already requested, n + 2 requested now
-#define E2EFT_PV3(n) step(IC512<n>{}, f0, f2); step(IC512<n + 1>{}, f1, f0); step(IC512<n + 2>{}, f2, f1);
+#define E2EFT_PV3(n) step(IConst<n>{}, f0, f2); step(IConst<n + 1>{}, f1, f0); step(IConst<n + 2>{}, f2, f1);
         E2EFT_PV3(0) E2EFT_PV3(3) E2EFT_PV3(6) E2EFT_PV3(9) E2EFT_PV3(12) E2EFT_PV3(15) E2EFT_PV3(18) E2EFT_PV3(21) E2EFT_PV3(24) E2EFT_PV3(27)
-        step(IC512<30>{}, f0, f2); step(IC512<31>{}, f1, f0);
+        step(IConst<30>{}, f0, f2); step(IConst<31>{}, f1, f0);
 #undef E2EFT_PV3
     };
     auto end_iteration = [&]() {
@@ -326,10 +284,10 @@ __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
     // iterations 1 .. nt-1: S^T(t), then O^T update of tile t-1 with softmax(t) in its shadow.  Buffers: K(t) in kbuf[t & 1], V(t-1) in vbuf[(t-1) & 1]
     for (int t = 1; t < nt; ++t) {
         s_phase(t);
-        pv_phase((t - 1) & 1, IC512<1>{});
+        pv_phase((t - 1) & 1, IConst<1>{});
         end_iteration();
     }
-    pv_phase((nt - 1) & 1, IC512<0>{});
+    pv_phase((nt - 1) & 1, IConst<0>{});
 
     // ---- epilogue: O / l, 8-byte stores of 4 consecutive d ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -357,15 +315,15 @@ __global__ __launch_bounds__(256) void attn512_fwd_kernel(const Attn5Params p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 u32x2 w;
-                w[0] = Mma512<T>::pack(o[4 * g] * inv, o[4 * g + 1] * inv);
-                w[1] = Mma512<T>::pack(o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+                w[0] = pack2<T>(o[4 * g] * inv, o[4 * g + 1] * inv);
+                w[1] = pack2<T>(o[4 * g + 2] * inv, o[4 * g + 3] * inv);
                 *reinterpret_cast<u32x2*>(dst + dt * 32 + 8 * g + 4 * hh) = w;
             }
         }
     };
-    store_block(IC512<0>{}); store_block(IC512<1>{}); store_block(IC512<2>{}); store_block(IC512<3>{}); store_block(IC512<4>{}); store_block(IC512<5>{});
-    store_block(IC512<6>{}); store_block(IC512<7>{}); store_block(IC512<8>{}); store_block(IC512<9>{}); store_block(IC512<10>{}); store_block(IC512<11>{});
-    store_block(IC512<12>{}); store_block(IC512<13>{}); store_block(IC512<14>{}); store_block(IC512<15>{});
+    store_block(IConst<0>{}); store_block(IConst<1>{}); store_block(IConst<2>{}); store_block(IConst<3>{}); store_block(IConst<4>{}); store_block(IConst<5>{});
+    store_block(IConst<6>{}); store_block(IConst<7>{}); store_block(IConst<8>{}); store_block(IConst<9>{}); store_block(IConst<10>{}); store_block(IConst<11>{});
+    store_block(IConst<12>{}); store_block(IConst<13>{}); store_block(IConst<14>{}); store_block(IConst<15>{});
 }
 
 // merge of the key-split tail: out[q] = sum_j O_j 2^(m_j - M) / sum_j l_j 2^(m_j - M), M = max_j m_j.  One thread per (query, 8 d values).

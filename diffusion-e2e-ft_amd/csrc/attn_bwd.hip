@@ -18,7 +18,7 @@
 //       dS^T from registers and K^T from a transposed LDS image.
 // MFMA operand convention (v_mfma_f32_32x32x16): lane l supplies A[i = l&31][k = 8(l>>5)..+7] and B[k = 8(l>>5)..+7][j = l&31];
 // the result register r of lane l is D[i = (r&3) + 8(r>>2) + 4(l>>5)][j = l&31].
-#include "common.h"
+#include "gfx950.h"
 
 namespace e2eft {
 
@@ -41,30 +41,6 @@ struct AttnBwdParams {
     int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
     float c, scale;
 };
-
-template <typename T> struct MmaB;
-template <> struct MmaB<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaB<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
-typedef float float2w __attribute__((ext_vector_type(2)));
-typedef __bf16 bhalf2w __attribute__((ext_vector_type(2)));
-template <typename T> __device__ __forceinline__ uint32_t packb(float lo, float hi);
-template <> __device__ __forceinline__ uint32_t packb<f16>(float lo, float hi) {
-    const float2w f = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, half2v));
-}
-template <> __device__ __forceinline__ uint32_t packb<bf16>(float lo, float hi) {
-    const float2w f = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bhalf2w));
-}
 
 // D[b][h][q] = sum_d dO[b,q,h*64+d] * O[b,q,h*64+d]; one thread per (row, head)
 template <typename T>
@@ -206,12 +182,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
 #pragma unroll
             for (int ds = 0; ds < 4; ++ds) {
                 const u32x4 qa = *reinterpret_cast<const u32x4*>(qrow + ds * 32);
-                s = MmaB<T>::run(qa, kf[ds], s);
+                s = Mma32x32x16<T>::run(qa, kf[ds], s);
             }
 #pragma unroll
             for (int ds = 0; ds < 4; ++ds) {
                 const u32x4 da = *reinterpret_cast<const u32x4*>(drow + ds * 32);
-                dp = MmaB<T>::run(da, vf[ds], dp);
+                dp = Mma32x32x16<T>::run(da, vf[ds], dp);
             }
             // P = 2^(c s - lse2[q]), dS = P (dP - D[q]); register r <-> query 32 qt + (r&3) + 8 (r>>2) + 4 hh
             uint32_t pw[8], dw[8];
@@ -225,8 +201,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
                     pe[e] = __builtin_amdgcn_exp2f(s[4 * g + e] - l4[e]);
                     de[e] = pe[e] * (dp[4 * g + e] - d4[e]);
                 }
-                pw[2 * g] = packb<T>(pe[0], pe[1]); pw[2 * g + 1] = packb<T>(pe[2], pe[3]);
-                dw[2 * g] = packb<T>(de[0], de[1]); dw[2 * g + 1] = packb<T>(de[2], de[3]);
+                pw[2 * g] = pack2<T>(pe[0], pe[1]); pw[2 * g + 1] = pack2<T>(pe[2], pe[3]);
+                dw[2 * g] = pack2<T>(de[0], de[1]); dw[2 * g + 1] = pack2<T>(de[2], de[3]);
             }
             // dV^T[d][key] += dO^T[d][q] P[q][key],  dK^T[d][key] += Q^T[d][q] dS[q][key]  (two 16-query k-steps)
 #pragma unroll
@@ -239,11 +215,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
                     const char* r1 = sdt + (dt * 32 + l31) * BTROW + qb;
                     const u32x2 a0 = *reinterpret_cast<const u32x2*>(r1);
                     const u32x2 a1 = *reinterpret_cast<const u32x2*>(r1 + 16);
-                    dv[dt] = MmaB<T>::run(u32x4{a0[0], a0[1], a1[0], a1[1]}, pf, dv[dt]);
+                    dv[dt] = Mma32x32x16<T>::run(u32x4{a0[0], a0[1], a1[0], a1[1]}, pf, dv[dt]);
                     const char* r2 = sqt + (dt * 32 + l31) * BTROW + qb;
                     const u32x2 b0 = *reinterpret_cast<const u32x2*>(r2);
                     const u32x2 b1 = *reinterpret_cast<const u32x2*>(r2 + 16);
-                    dk[dt] = MmaB<T>::run(u32x4{b0[0], b0[1], b1[0], b1[1]}, df, dk[dt]);
+                    dk[dt] = Mma32x32x16<T>::run(u32x4{b0[0], b0[1], b1[0], b1[1]}, df, dk[dt]);
                 }
             }
         }
@@ -260,11 +236,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 u32x2 w;
-                w[0] = packb<T>(dk[dt][4 * g] * p.scale, dk[dt][4 * g + 1] * p.scale);
-                w[1] = packb<T>(dk[dt][4 * g + 2] * p.scale, dk[dt][4 * g + 3] * p.scale);
+                w[0] = pack2<T>(dk[dt][4 * g] * p.scale, dk[dt][4 * g + 1] * p.scale);
+                w[1] = pack2<T>(dk[dt][4 * g + 2] * p.scale, dk[dt][4 * g + 3] * p.scale);
                 *reinterpret_cast<u32x2*>(dkp + dt * 32 + 8 * g + 4 * hh) = w;
-                w[0] = packb<T>(dv[dt][4 * g], dv[dt][4 * g + 1]);
-                w[1] = packb<T>(dv[dt][4 * g + 2], dv[dt][4 * g + 3]);
+                w[0] = pack2<T>(dv[dt][4 * g], dv[dt][4 * g + 1]);
+                w[1] = pack2<T>(dv[dt][4 * g + 2], dv[dt][4 * g + 3]);
                 *reinterpret_cast<u32x2*>(dvp + dt * 32 + 8 * g + 4 * hh) = w;
             }
     }
@@ -370,12 +346,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
 #pragma unroll
             for (int ds = 0; ds < 4; ++ds) {
                 const u32x4 ka = *reinterpret_cast<const u32x4*>(krow + ds * 32);
-                s = MmaB<T>::run(ka, qf[ds], s);
+                s = Mma32x32x16<T>::run(ka, qf[ds], s);
             }
 #pragma unroll
             for (int ds = 0; ds < 4; ++ds) {
                 const u32x4 va = *reinterpret_cast<const u32x4*>(vrow + ds * 32);
-                dp = MmaB<T>::run(va, dof[ds], dp);
+                dp = Mma32x32x16<T>::run(va, dof[ds], dp);
             }
             // dS^T = P^T (dP^T - D[q]); register r <-> key 64 t + 32 kt2 + (r&3) + 8 (r>>2) + 4 hh
             if (t * 64 + 64 > p.nk) {   // last tile only: keys past the end get p = 0
@@ -388,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
             for (int w = 0; w < 8; ++w) {
                 const float p0 = __builtin_amdgcn_exp2f(s[2 * w] - lse2);
                 const float p1 = __builtin_amdgcn_exp2f(s[2 * w + 1] - lse2);
-                dw[w] = packb<T>(p0 * (dp[2 * w] - dsum), p1 * (dp[2 * w + 1] - dsum));
+                dw[w] = pack2<T>(p0 * (dp[2 * w] - dsum), p1 * (dp[2 * w + 1] - dsum));
             }
             // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
 #pragma unroll
@@ -400,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
                     const char* r1 = skt + (dt * 32 + l31) * BTROW + kb;
                     const u32x2 a0 = *reinterpret_cast<const u32x2*>(r1);
                     const u32x2 a1 = *reinterpret_cast<const u32x2*>(r1 + 16);
-                    dq[dt] = MmaB<T>::run(u32x4{a0[0], a0[1], a1[0], a1[1]}, df, dq[dt]);
+                    dq[dt] = Mma32x32x16<T>::run(u32x4{a0[0], a0[1], a1[0], a1[1]}, df, dq[dt]);
                 }
             }
         }
@@ -415,8 +391,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 u32x2 w;
-                w[0] = packb<T>(dq[dt][4 * g] * p.scale, dq[dt][4 * g + 1] * p.scale);
-                w[1] = packb<T>(dq[dt][4 * g + 2] * p.scale, dq[dt][4 * g + 3] * p.scale);
+                w[0] = pack2<T>(dq[dt][4 * g] * p.scale, dq[dt][4 * g + 1] * p.scale);
+                w[1] = pack2<T>(dq[dt][4 * g + 2] * p.scale, dq[dt][4 * g + 3] * p.scale);
                 *reinterpret_cast<u32x2*>(dst + dt * 32 + 8 * g + 4 * hh) = w;
             }
     }

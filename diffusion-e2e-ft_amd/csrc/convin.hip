@@ -25,29 +25,7 @@ constexpr int TH = 8, TW = 32;
 constexpr int WIN = NW * 4096;                 // the epilogue's per-wave windows
 constexpr int DEP = NW * 64 * 3 * 4;
 constexpr int LDS = WIN + DEP;
-constexpr unsigned int OOB = 0xF0000000u;
-constexpr unsigned int RECORDS = 0xE0000000u;
 }  // namespace thin
-
-template <typename T> struct MmaT;
-template <> struct MmaT<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaT<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ int fast_div_t(int n, int d) {
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) --q;
-    else if (r >= d) ++q;
-    return q;
-}
 
 template <typename T>
 __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, const int total_tiles) {
@@ -81,16 +59,16 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
     bool c_colok = false;
     (void)pre_res; (void)pre_bias; (void)pre_ra; (void)rowadd; (void)c_rrow; (void)c_ncl;
 
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x1, 0, RECORDS, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx = whole_range_rsrc(p.x1);
     // tile -> (M tile, N tile) with N fastest, M tile -> (image, 8 x 32 block)
     int t_mt = 0, t_n0 = 0, t_img = 0, t_oy0 = 0, t_ox0 = 0;
     auto coords = [&](const int v) {
         int mt = v, nt = 0;
-        if (p.ntiles > 1) { mt = fast_div_t(v, p.ntiles); nt = v - mt * p.ntiles; }
+        if (p.ntiles > 1) { mt = fast_div(v, p.ntiles); nt = v - mt * p.ntiles; }
         t_mt = mt; t_n0 = nt * BN;
-        t_img = fast_div_t(mt, tpi);
+        t_img = fast_div(mt, tpi);
         const int rem = mt - t_img * tpi;
-        const int ty = fast_div_t(rem, tw);
+        const int ty = fast_div(rem, tw);
         t_oy0 = ty * TH; t_ox0 = (rem - ty * tw) * TW;
     };
     // A fragments of tile (t_img, t_oy0, t_ox0): afr[i][j] = the eight channels of pixel (row 2 wm + i, column l31) shifted by tap 2 j + h
@@ -104,7 +82,7 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
                 const int ky = tap >= 6 ? 2 : (tap >= 3 ? 1 : 0), kx = tap - 3 * ky;
                 const int iy = t_oy0 + 2 * wm + i + ky - 1, ix = t_ox0 + l31 + kx - 1;
                 const bool ok = tap < 9 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                const unsigned off = ok ? (unsigned)(((t_img * H + iy) * W + ix) * 16) : OOB;
+                const unsigned off = ok ? (unsigned)(((t_img * H + iy) * W + ix) * 16) : SRD_OOB;
                 afr[i][j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0));
             }
     };
@@ -146,16 +124,16 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
         c_ncl = c_colok ? c_n0 + wn * 64 + ec * 8 : c_n0;
         c_orow = (((long)t_img * H + t_oy0 + 2 * wm) * W + t_ox0 + er) * p.ldo + c_ncl;
         const floatx16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        acc[0][0] = MmaT<T>::run(afr[0][0], bfr[0][0], z);
-        acc[0][1] = MmaT<T>::run(afr[0][0], bfr[1][0], z);
-        acc[1][0] = MmaT<T>::run(afr[1][0], bfr[0][0], z);
-        acc[1][1] = MmaT<T>::run(afr[1][0], bfr[1][0], z);
+        acc[0][0] = Mma32x32x16<T>::run(afr[0][0], bfr[0][0], z);
+        acc[0][1] = Mma32x32x16<T>::run(afr[0][0], bfr[1][0], z);
+        acc[1][0] = Mma32x32x16<T>::run(afr[1][0], bfr[0][0], z);
+        acc[1][1] = Mma32x32x16<T>::run(afr[1][0], bfr[1][0], z);
 #pragma unroll
         for (int j = 1; j < 5; ++j) {
-            acc[0][0] = MmaT<T>::run(afr[0][j], bfr[0][j], acc[0][0]);
-            acc[0][1] = MmaT<T>::run(afr[0][j], bfr[1][j], acc[0][1]);
-            acc[1][0] = MmaT<T>::run(afr[1][j], bfr[0][j], acc[1][0]);
-            acc[1][1] = MmaT<T>::run(afr[1][j], bfr[1][j], acc[1][1]);
+            acc[0][0] = Mma32x32x16<T>::run(afr[0][j], bfr[0][j], acc[0][0]);
+            acc[0][1] = Mma32x32x16<T>::run(afr[0][j], bfr[1][j], acc[0][1]);
+            acc[1][0] = Mma32x32x16<T>::run(afr[1][j], bfr[0][j], acc[1][0]);
+            acc[1][1] = Mma32x32x16<T>::run(afr[1][j], bfr[1][j], acc[1][1]);
         }
         // ---- the next tile's operand loads fly under this tile's epilogue
         u += nslots;

@@ -1,11 +1,8 @@
 // igemm.h — parameter block shared by the implicit-GEMM kernel variants.
 #pragma once
-#include "common.h"
-#include <type_traits>
+#include "gfx950.h"
 
 namespace e2eft {
-
-template <int V> using IConst = std::integral_constant<int, V>;
 
 // -DE2EFT_STAMPS (build.py build_stamps(): lib/libe2eft_stamps.so, scripts/stamp_bench.py): thread 0 of every workgroup records the
 // shader clock at the phase boundaries of igemm2_kernel — start, k-loop entry, k-loop exit, accumulators staged, end.

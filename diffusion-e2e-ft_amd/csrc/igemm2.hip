@@ -36,36 +36,7 @@ template <int NW> struct Geo {
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 
-template <typename T> struct Mma2;
-template <> struct Mma2<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma2<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
 typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-constexpr unsigned int OOB_SENTINEL = 0xF0000000u;   // byte offset beyond SRD_RECORDS: the load returns zeros
-constexpr unsigned int SRD_RECORDS = 0xE0000000u;
-
-template <int V> using IC = std::integral_constant<int, V>;
-
-// n / d for 0 <= n < 2^31, d >= 1 with a quotient below 2^22 (rows / image size, pixels / row length): float estimate (relative
-// error ~2^-22, so off by at most one) + one correction — 8 instructions instead of the ~25 of the generic unsigned division,
-// eight of which sit in front of the first DMA of every workgroup.
-__device__ __forceinline__ int fast_div(int n, int d) {
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) --q;
-    else if (r >= d) ++q;
-    return q;
-}
 
 // Tried and measured, not kept (conv 512->512 @192^2, B = 8, fp16; this kernel: 940-970 TF/s): a rotated loop that reads the next
 // tile's first fragments before the current tile's last MFMAs (820), a ping-pong schedule with the two waves of a SIMD in
@@ -167,10 +138,10 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 
     auto mma_group = [&](const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
         if constexpr (sizeof(T) == 2) {
-            acc[0][0] = Mma2<T>::run(a0, b0, acc[0][0]);
-            acc[0][1] = Mma2<T>::run(a0, b1, acc[0][1]);
-            acc[1][0] = Mma2<T>::run(a1, b0, acc[1][0]);
-            acc[1][1] = Mma2<T>::run(a1, b1, acc[1][1]);
+            acc[0][0] = Mma32x32x16<T>::run(a0, b0, acc[0][0]);
+            acc[0][1] = Mma32x32x16<T>::run(a0, b1, acc[0][1]);
+            acc[1][0] = Mma32x32x16<T>::run(a1, b0, acc[1][0]);
+            acc[1][1] = Mma32x32x16<T>::run(a1, b1, acc[1][1]);
         } else {
             // fp32: MFMA 32x32x2 step s pairs k-slot s of the lower half (lanes 0-31, chunks 0-3) with k-slot s of the upper
             // half (lanes 32-63, chunks 4-7); the same pairing is used for A and W, so the sum is the plain dot product.
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 
     if constexpr (FAST) {
         // ============================ FAST path =====================================================================
-        unsigned int off1[4], off2[4];          // per-row byte offsets of the current tap in x1 / x2 (OOB_SENTINEL if invalid)
+        unsigned int off1[4], off2[4];          // per-row byte offsets of the current tap in x1 / x2 (SRD_OOB if invalid)
         unsigned int cur_a[4], cur_b[4];        // byte offsets of the NEXT tile to issue (advanced by 128 B per tile)
         int brel[4] = {0, 0, 0, 0};
         int tile_c = 0;
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
             b1 = X1 + (long)m0 * p.ldx1;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                cur_a[i] = (a_ok[i] ? (unsigned)((lrow + RSTEP * i) * p.ldx1 + jc * EPC) * (unsigned)sizeof(T) : OOB_SENTINEL) - 128u;
+                cur_a[i] = (a_ok[i] ? (unsigned)((lrow + RSTEP * i) * p.ldx1 + jc * EPC) * (unsigned)sizeof(T) : SRD_OOB) - 128u;
         } else {
             const int hw = p.hout * p.wout;
             const int b0 = m0 / hw;             // first image touched by this tile (uniform)
@@ -216,13 +187,13 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { brel[i] = (int)a_base[i] - b0; cur_a[i] = 0; }
         }
-        const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)b1, 0, SRD_RECORDS, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(b2 ? b2 : b1), 0, SRD_RECORDS, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (long)n0 * p.ldw), 0, SRD_RECORDS, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs1 = whole_range_rsrc(b1);
+        const __amdgpu_buffer_rsrc_t rs2 = whole_range_rsrc((b2 ? b2 : b1));
+        const __amdgpu_buffer_rsrc_t rsw = whole_range_rsrc((W + (long)n0 * p.ldw));
         __amdgpu_buffer_rsrc_t rsa = rs1;       // descriptor of the A source in use (changes at tap / source boundaries)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            cur_b[i] = ((i < BPIECES && w_ok[i]) ? (unsigned)((lrow + RSTEP * i) * p.ldw + jc * EPC) * (unsigned)sizeof(T) : OOB_SENTINEL) - 128u;
+            cur_b[i] = ((i < BPIECES && w_ok[i]) ? (unsigned)((lrow + RSTEP * i) * p.ldw + jc * EPC) * (unsigned)sizeof(T) : SRD_OOB) - 128u;
 
         // plain convolutions (no fused upsample, no zero insertion): the source pixel of tap (ky, kx) is the tap-(0,0) pixel plus the
         // scalar (ky * win + kx), so a tap change costs two compares, one add and one select per row instead of the full index
@@ -245,8 +216,8 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool ok = a_ok[i] && (unsigned)(a_iy0[i] + ky) < (unsigned)p.hl && (unsigned)(a_ix0[i] + kx) < (unsigned)p.wl;
-                    off1[i] = ok ? base1[i] + d1 : OOB_SENTINEL;
-                    off2[i] = ok ? base2[i] + d2 : OOB_SENTINEL;
+                    off1[i] = ok ? base1[i] + d1 : SRD_OOB;
+                    off2[i] = ok ? base2[i] + d2 : SRD_OOB;
                 }
                 return;
             }
@@ -263,8 +234,8 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
                     if (p.wl != p.win) sx = min((int)floorf(ix * p.up_sw), p.win - 1);
                 }
                 const unsigned pix = (unsigned)((brel[i] * p.hin + sy) * p.win + sx);
-                off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB_SENTINEL;
-                off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB_SENTINEL;
+                off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
+                off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
             }
         };
         auto advance = [&]() {   // offsets / descriptor of the next tile to issue (tiles are issued in order 0,1,2,...)
@@ -297,13 +268,13 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
         auto fire = [&](auto stage_c, auto piece_c) {
             constexpr int S = decltype(stage_c)::value, Q = decltype(piece_c)::value;
             char* sa = smem + S * STAGE2 + wave * 1024;
-            if constexpr (Q < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(sa + Q * (RSTEP * 128)), 16, cur_a[Q], 0, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lptr_t)(sa + A_STAGE + (Q - 4) * (RSTEP * 128)), 16, cur_b[Q - 4], 0, 0, 0);
+            if constexpr (Q < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr_t)(sa + Q * (RSTEP * 128)), 16, cur_a[Q], 0, 0, 0);
+            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(sa + A_STAGE + (Q - 4) * (RSTEP * 128)), 16, cur_b[Q - 4], 0, 0, 0);
         };
         auto fire_all = [&](auto stage_c) {
-            fire(stage_c, IC<0>{}); fire(stage_c, IC<1>{}); fire(stage_c, IC<2>{}); fire(stage_c, IC<3>{});
-            fire(stage_c, IC<4>{}); fire(stage_c, IC<5>{});
-            if constexpr (NPIECES == 8) { fire(stage_c, IC<6>{}); fire(stage_c, IC<7>{}); }
+            fire(stage_c, IConst<0>{}); fire(stage_c, IConst<1>{}); fire(stage_c, IConst<2>{}); fire(stage_c, IConst<3>{});
+            fire(stage_c, IConst<4>{}); fire(stage_c, IConst<5>{});
+            if constexpr (NPIECES == 8) { fire(stage_c, IConst<6>{}); fire(stage_c, IConst<7>{}); }
         };
         // one k-tile: publish it (counted wait + barrier), then 4 MFMA groups with fragments fetched two groups ahead and
         // the DMA of tile kt+D (stage DS) spread between the groups
@@ -321,22 +292,22 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
                 b0[slot] = *reinterpret_cast<const u32x4*>(smem + bofs[S][g]);
                 b1[slot] = *reinterpret_cast<const u32x4*>(smem + bofs[S][g] + 32 * 128);
             };
-            rd(IC<0>{}, IC<0>{});
-            rd(IC<1>{}, IC<1>{});
+            rd(IConst<0>{}, IConst<0>{});
+            rd(IConst<1>{}, IConst<1>{});
             __builtin_amdgcn_sched_barrier(0);
-            rd(IC<2>{}, IC<2>{});
-            if (more) { fire(dc, IC<0>{}); fire(dc, IC<1>{}); }
+            rd(IConst<2>{}, IConst<2>{});
+            if (more) { fire(dc, IConst<0>{}); fire(dc, IConst<1>{}); }
             __builtin_amdgcn_sched_barrier(0);
             mma_group(a0[0], a1[0], b0[0], b1[0]);
             __builtin_amdgcn_sched_barrier(0);
-            rd(IC<3>{}, IC<0>{});
-            if (more) { fire(dc, IC<2>{}); fire(dc, IC<3>{}); }
+            rd(IConst<3>{}, IConst<0>{});
+            if (more) { fire(dc, IConst<2>{}); fire(dc, IConst<3>{}); }
             __builtin_amdgcn_sched_barrier(0);
             mma_group(a0[1], a1[1], b0[1], b1[1]);
             __builtin_amdgcn_sched_barrier(0);
             if (more) {
-                fire(dc, IC<4>{}); fire(dc, IC<5>{});
-                if constexpr (NPIECES == 8) { fire(dc, IC<6>{}); fire(dc, IC<7>{}); }
+                fire(dc, IConst<4>{}); fire(dc, IConst<5>{});
+                if constexpr (NPIECES == 8) { fire(dc, IConst<6>{}); fire(dc, IConst<7>{}); }
             }
             __builtin_amdgcn_sched_barrier(0);
             mma_group(a0[2], a1[2], b0[2], b1[2]);
@@ -346,38 +317,38 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 
         // prologue: tiles 0 .. D-1 in flight
         advance();
-        fire_all(IC<0>{});
+        fire_all(IConst<0>{});
         if constexpr (D == 2) {
-            if (nk > 1) { advance(); fire_all(IC<1>{}); }
+            if (nk > 1) { advance(); fire_all(IConst<1>{}); }
         }
         zero_acc();
         E2EFT_STAMP(1);
         int kt = 0;
         if constexpr (NSTAGE == 3) {
             for (; kt + 3 + D <= nk; kt += 3) {   // steady state: every prefetch exists, every stage index is static
-                tile(IC<0>{}, IC<2>{}, true, true);
+                tile(IConst<0>{}, IConst<2>{}, true, true);
 #ifdef E2EFT_STAMPS
                 if (kt == 0) E2EFT_STAMP(5);
 #endif
-                tile(IC<1>{}, IC<0>{}, true, true);
-                tile(IC<2>{}, IC<1>{}, true, true);
+                tile(IConst<1>{}, IConst<0>{}, true, true);
+                tile(IConst<2>{}, IConst<1>{}, true, true);
 #ifdef E2EFT_STAMPS
                 if (kt == 0) E2EFT_STAMP(6);
                 if (kt == 3) E2EFT_STAMP(7);
 #endif
             }
             // tail: at most 4 tiles left (kt is a multiple of 3)
-            if (kt < nk) { tile(IC<0>{}, IC<2>{}, kt + 1 < nk, kt + D < nk); ++kt; }
-            if (kt < nk) { tile(IC<1>{}, IC<0>{}, kt + 1 < nk, kt + D < nk); ++kt; }
-            if (kt < nk) { tile(IC<2>{}, IC<1>{}, kt + 1 < nk, kt + D < nk); ++kt; }
-            if (kt < nk) { tile(IC<0>{}, IC<2>{}, kt + 1 < nk, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<0>{}, IConst<2>{}, kt + 1 < nk, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<1>{}, IConst<0>{}, kt + 1 < nk, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<2>{}, IConst<1>{}, kt + 1 < nk, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<0>{}, IConst<2>{}, kt + 1 < nk, kt + D < nk); ++kt; }
         } else {
             for (; kt + 2 + D <= nk; kt += 2) {
-                tile(IC<0>{}, IC<1>{}, false, true);
-                tile(IC<1>{}, IC<0>{}, false, true);
+                tile(IConst<0>{}, IConst<1>{}, false, true);
+                tile(IConst<1>{}, IConst<0>{}, false, true);
             }
-            if (kt < nk) { tile(IC<0>{}, IC<1>{}, false, kt + D < nk); ++kt; }
-            if (kt < nk) { tile(IC<1>{}, IC<0>{}, false, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<0>{}, IConst<1>{}, false, kt + D < nk); ++kt; }
+            if (kt < nk) { tile(IConst<1>{}, IConst<0>{}, false, kt + D < nk); ++kt; }
         }
     } else {
         // ============================ general path: per-lane pointers, zero block for padding ========================
@@ -398,7 +369,7 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const T* src = (kok && a_ok[i]) ? X1 + a_base[i] + k_cur : zsrc;
-                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sa + i * (RSTEP * 128)), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(sa + i * (RSTEP * 128)), 16, 0, 0);
                 }
             } else {
                 const bool second = c_cur >= p.c1;
@@ -419,13 +390,13 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
                     }
                     const long pix = (a_base[i] * p.hin + sy) * p.win + sx;
                     const T* src = ok ? sbase + pix * ld + cc : zsrc;
-                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sa + i * (RSTEP * 128)), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(sa + i * (RSTEP * 128)), 16, 0, 0);
                 }
             }
 #pragma unroll
             for (int i = 0; i < BPIECES; ++i) {
                 const T* src = (kok && w_ok[i]) ? W + w_base[i] + k_cur : zsrc;
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sb + i * (RSTEP * 128)), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(sb + i * (RSTEP * 128)), 16, 0, 0);
             }
             k_cur += BK;
             if (MODE == 1) {

@@ -49,21 +49,7 @@ constexpr int RING = 3 * STAGE;                  // 147,456 B
 constexpr int DEP = NW * 64 * 3 * 4;             // per-wave GroupNorm deposits: (sum, sum of squares, pivot) per column
 constexpr int ROWTAB = BM * 16;                  // (image, iy0, ix0, pixel) of the 256 output rows of the loader's NEXT tile, one thread per row
 constexpr int LDS = RING + DEP + ROWTAB;
-constexpr unsigned int OOB = 0xF0000000u;        // byte offset beyond RECORDS: the buffer load returns zeros
-constexpr unsigned int RECORDS = 0xE0000000u;
 }  // namespace pers
-
-template <typename T> struct Mma5;
-template <> struct Mma5<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma5<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
 
 #ifdef E2EFT_STAMPS
 // instrumented build: thread 0 of every workgroup records, for its first 32 tiles, the shader clock at: k-loop entry, after the steady
@@ -73,17 +59,6 @@ static __device__ long long g_stamps5[512 * 32 * 8];
 #else
 #define STAMP5(t, i) do { } while (0)
 #endif
-
-typedef __attribute__((address_space(3))) void* lptr5_t;
-template <int V> using IC5 = std::integral_constant<int, V>;
-
-__device__ __forceinline__ int fast_div5(int n, int d) {   // as igemm2.hip: float estimate + one correction (quotients below 2^22)
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) --q;
-    else if (r >= d) ++q;
-    return q;
-}
 
 // RES: the launch has a residual operand (fp32 sliced epilogue); otherwise the packed epilogue — one of the two per instantiation, for the register budget
 // F32O (round 6, csrc/f32split.hip): an fp32 convolution / GEMM whose products are formed on the f16 matrix pipe.  A holds the two f16 planes [x0 | x1] of an fp32 operand
@@ -122,7 +97,7 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     const bool plain_taps = MODE == 1 && p.zins <= 1 && p.hl == p.hin && p.wl == p.win;
     const bool half_res = MODE == 1 && (p.zins == 2 || (p.zins <= 1 && p.hl == 2 * p.hin && p.wl == 2 * p.win));
 
-    unsigned int off1[4], off2[4];          // per-row byte offsets of the current tap in x1 / x2 (OOB if padded)
+    unsigned int off1[4], off2[4];          // per-row byte offsets of the current tap in x1 / x2 (SRD_OOB if padded)
     unsigned int cur_a[4], cur_b[2];        // byte offsets of the NEXT k-tile to issue (advanced by 128 B per k-tile)
     unsigned int base1[4], base2[4];
     int a_iy0[4], a_ix0[4], brel[4];
@@ -139,14 +114,14 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     int d_b0 = 0;
     auto tile_coords = [&](const int u) {
         int z = 0, lid = u;
-        if (nblk != total_tiles) { z = fast_div5(u, nblk); lid = u - z * nblk; }
+        if (nblk != total_tiles) { z = fast_div(u, nblk); lid = u - z * nblk; }
         int mt = lid, nt = 0;
-        if (p.ntiles > 1) { mt = fast_div5(lid, p.ntiles); nt = lid - mt * p.ntiles; }
+        if (p.ntiles > 1) { mt = fast_div(lid, p.ntiles); nt = lid - mt * p.ntiles; }
         d_m0 = mt * BM; d_n0 = nt * BN;
         d_zo = 0; d_zi = z;
-        if (p.nzi > 1 && z > 0) { d_zo = fast_div5(z, p.nzi); d_zi = z - d_zo * p.nzi; }
+        if (p.nzi > 1 && z > 0) { d_zo = fast_div(z, p.nzi); d_zi = z - d_zo * p.nzi; }
         else if (p.nzi == 1) { d_zo = z; d_zi = 0; }
-        if (MODE == 1) d_b0 = fast_div5(d_m0, p.hout * p.wout);   // first image touched by this tile
+        if (MODE == 1) d_b0 = fast_div(d_m0, p.hout * p.wout);   // first image touched by this tile
     };
     // (the row table is written / read with inline-asm DS instructions: in front of LDS accesses it can see, the compiler drains
     // vmcnt — it has to assume that a pending LDS-DMA may alias them — and here pieces / stores are in flight by design)
@@ -154,9 +129,9 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         if (MODE == 1 && tid < BM) {
             const int hw = p.hout * p.wout;
             const int m = d_m0 + tid;
-            const int b = fast_div5(m, hw);
+            const int b = fast_div(m, hw);
             const int rem = m - b * hw;
-            const int oy = fast_div5(rem, p.wout), ox = rem - oy * p.wout;
+            const int oy = fast_div(rem, p.wout), ox = rem - oy * p.wout;
             int iy0 = oy * p.stride - p.pad_t, ix0 = ox * p.stride - p.pad_l;
             if (F32O && m >= p.M) iy0 = -0x4000;      // a row beyond the problem (ragged last tile, F32O only): every tap is padding
             const u32x4 v = {(unsigned)(b - d_b0), (unsigned)iy0, (unsigned)ix0, (unsigned)(((b - d_b0) * p.hin + iy0) * p.win + ix0)};
@@ -172,7 +147,7 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         if (MODE == 0) {
             b1 = X1 + (long)d_m0 * p.ldx1;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) cur_a[i] = ((F32O && d_m0 + lrow + RSTEP * i >= p.M) ? OOB : (unsigned)((lrow + RSTEP * i) * p.ldx1 + jc * EPC) * (unsigned)sizeof(T)) - 128u;
+            for (int i = 0; i < 4; ++i) cur_a[i] = ((F32O && d_m0 + lrow + RSTEP * i >= p.M) ? SRD_OOB : (unsigned)((lrow + RSTEP * i) * p.ldx1 + jc * EPC) * (unsigned)sizeof(T)) - 128u;
         } else {
             b1 = X1 + (long)d_b0 * p.hin * p.win * p.ldx1;
             if (b2) b2 += (long)d_b0 * p.hin * p.win * p.ldx2;
@@ -193,14 +168,14 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
                 }
             }
         }
-        rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)b1, 0, RECORDS, 0x00020000);
-        rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(b2 ? b2 : b1), 0, RECORDS, 0x00020000);
-        rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (long)d_n0 * p.ldw), 0, RECORDS, 0x00020000);
+        rs1 = whole_range_rsrc(b1);
+        rs2 = whole_range_rsrc((b2 ? b2 : b1));
+        rsw = whole_range_rsrc((W + (long)d_n0 * p.ldw));
         rsa = rs1;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int n = d_n0 + lrow + RSTEP * i;
-            cur_b[i] = (n < p.N ? (unsigned)((lrow + RSTEP * i) * p.ldw + jc * EPC) * (unsigned)sizeof(T) : OOB) - 128u;
+            cur_b[i] = (n < p.N ? (unsigned)((lrow + RSTEP * i) * p.ldw + jc * EPC) * (unsigned)sizeof(T) : SRD_OOB) - 128u;
         }
         tile_c = 0; ky = 0; kx = 0;
     };
@@ -211,8 +186,8 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bool ok = (unsigned)(a_iy0[i] + ky) < (unsigned)p.hl && (unsigned)(a_ix0[i] + kx) < (unsigned)p.wl;
-                off1[i] = ok ? base1[i] + d1 : OOB;
-                off2[i] = ok ? base2[i] + d2 : OOB;
+                off1[i] = ok ? base1[i] + d1 : SRD_OOB;
+                off2[i] = ok ? base2[i] + d2 : SRD_OOB;
             }
             return;
         }
@@ -223,8 +198,8 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
                 bool ok = (unsigned)iy < (unsigned)p.hl && (unsigned)ix < (unsigned)p.wl;
                 if (p.zins == 2) ok = ok && (((iy | ix) & 1) == 0);
                 const unsigned pix = (unsigned)((brel[i] * p.hin + (iy >> 1)) * p.win + (ix >> 1));
-                off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB;
-                off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB;
+                off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
+                off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
             }
             return;
         }
@@ -241,8 +216,8 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
                 if (p.wl != p.win) sx = min((int)floorf(ix * p.up_sw), p.win - 1);
             }
             const unsigned pix = (unsigned)((brel[i] * p.hin + sy) * p.win + sx);
-            off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB;
-            off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : OOB;
+            off1[i] = ok ? (pix * (unsigned)p.ldx1 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
+            off2[i] = ok ? (pix * (unsigned)p.ldx2 + (unsigned)(jc * EPC)) * (unsigned)sizeof(T) : SRD_OOB;
         }
     };
 #ifdef E2EFT_STAMPS
@@ -297,12 +272,12 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
 #ifdef E2EFT_STAMPS
         if (Q < 4 && !fire_a) return;
 #endif
-        if constexpr (Q < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr5_t)(sa + Q * (RSTEP * 128)), 16, cur_a[Q], 0, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lptr5_t)(sa + A_STAGE + (Q - 4) * (RSTEP * 128)), 16, cur_b[Q - 4], 0, 0, 0);
+        if constexpr (Q < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr_t)(sa + Q * (RSTEP * 128)), 16, cur_a[Q], 0, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(sa + A_STAGE + (Q - 4) * (RSTEP * 128)), 16, cur_b[Q - 4], 0, 0, 0);
     };
     auto fire_all = [&](const int stage) {
-        fire(stage, IC5<0>{}); fire(stage, IC5<1>{}); fire(stage, IC5<2>{}); fire(stage, IC5<3>{});
-        fire(stage, IC5<4>{}); fire(stage, IC5<5>{});
+        fire(stage, IConst<0>{}); fire(stage, IConst<1>{}); fire(stage, IConst<2>{}); fire(stage, IConst<3>{});
+        fire(stage, IConst<4>{}); fire(stage, IConst<5>{});
     };
 
     int tseq = 0;
@@ -318,10 +293,10 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         bofs[g] = A_STAGE + (wn * 64 + l31) * 128 + ((chunk ^ sw) * 16);
     }
     auto mma_group = [&](const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
-        acc[0][0] = Mma5<T>::run(a0, b0, acc[0][0]);
-        acc[0][1] = Mma5<T>::run(a0, b1, acc[0][1]);
-        acc[1][0] = Mma5<T>::run(a1, b0, acc[1][0]);
-        acc[1][1] = Mma5<T>::run(a1, b1, acc[1][1]);
+        acc[0][0] = Mma32x32x16<T>::run(a0, b0, acc[0][0]);
+        acc[0][1] = Mma32x32x16<T>::run(a0, b1, acc[0][1]);
+        acc[1][0] = Mma32x32x16<T>::run(a1, b0, acc[1][0]);
+        acc[1][1] = Mma32x32x16<T>::run(a1, b1, acc[1][1]);
     };
 
     // ---- epilogue operands requested ahead of their use
@@ -356,10 +331,10 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         const long zoff_r = d_zo * p.sr_o + d_zi * p.sr_i;
         c_colok = c_n0 + wn * 64 + ec * 8 < p.N;
         c_ncl = c_colok ? c_n0 + wn * 64 + ec * 8 : c_n0;
-        c_img = has_ra ? fast_div5(c_m0, p.rows_per_img) : 0;
+        c_img = has_ra ? fast_div(c_m0, p.rows_per_img) : 0;
         const int m = c_m0 + wm * 64 + er;          // slice s adds 8 * s rows
         c_mb = c_m0 + wm * 64;
-        c_seg0 = p.out_seg > 0 ? fast_div5(c_mb, p.out_seg) : 0;      // (segmented output: er < 8 <= out_seg / 2 keeps row `er` in the block's first segment)
+        c_seg0 = p.out_seg > 0 ? fast_div(c_mb, p.out_seg) : 0;      // (segmented output: er < 8 <= out_seg / 2 keeps row `er` in the block's first segment)
         c_orow = ((long)m + (long)c_seg0 * p.out_seg) * p.ldo + c_ncl;
         c_rrow = zoff_r + (long)m * p.ldr + c_ncl;
         nxt = u_dma + nslots < cend;
@@ -377,18 +352,18 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
             b0[slot] = *reinterpret_cast<const u32x4*>(smem + sc + bofs[g]);
             b1[slot] = *reinterpret_cast<const u32x4*>(smem + sc + bofs[g] + 32 * 128);
         };
-        rd(IC5<0>{}, IC5<0>{});
-        rd(IC5<1>{}, IC5<1>{});
+        rd(IConst<0>{}, IConst<0>{});
+        rd(IConst<1>{}, IConst<1>{});
         __builtin_amdgcn_sched_barrier(0);
-        rd(IC5<2>{}, IC5<2>{});
-        if constexpr (KIND != 1) { fire(sd, IC5<0>{}); fire(sd, IC5<1>{}); }
+        rd(IConst<2>{}, IConst<2>{});
+        if constexpr (KIND != 1) { fire(sd, IConst<0>{}); fire(sd, IConst<1>{}); }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (KIND == 3) {   // first k-tile of a tile: the accumulators start from the constant 0 (no 64 v_mov per tile)
             const floatx16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[0][0] = Mma5<T>::run(a0[0], b0[0], z);
-            acc[0][1] = Mma5<T>::run(a0[0], b1[0], z);
-            acc[1][0] = Mma5<T>::run(a1[0], b0[0], z);
-            acc[1][1] = Mma5<T>::run(a1[0], b1[0], z);
+            acc[0][0] = Mma32x32x16<T>::run(a0[0], b0[0], z);
+            acc[0][1] = Mma32x32x16<T>::run(a0[0], b1[0], z);
+            acc[1][0] = Mma32x32x16<T>::run(a1[0], b0[0], z);
+            acc[1][1] = Mma32x32x16<T>::run(a1[0], b1[0], z);
         } else {
             mma_group(a0[0], a1[0], b0[0], b1[0]);
         }
@@ -415,18 +390,18 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
             } else {
                 dma_done = true;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) cur_a[i] = OOB;
-                cur_b[0] = cur_b[1] = OOB;
+                for (int i = 0; i < 4; ++i) cur_a[i] = SRD_OOB;
+                cur_b[0] = cur_b[1] = SRD_OOB;
             }
             __builtin_amdgcn_sched_barrier(0);
-            fire(sd, IC5<0>{}); fire(sd, IC5<1>{});
+            fire(sd, IConst<0>{}); fire(sd, IConst<1>{});
         }
-        rd(IC5<3>{}, IC5<0>{});
-        fire(sd, IC5<2>{}); fire(sd, IC5<3>{});
+        rd(IConst<3>{}, IConst<0>{});
+        fire(sd, IConst<2>{}); fire(sd, IConst<3>{});
         __builtin_amdgcn_sched_barrier(0);
         mma_group(a0[1], a1[1], b0[1], b1[1]);
         __builtin_amdgcn_sched_barrier(0);
-        fire(sd, IC5<4>{}); fire(sd, IC5<5>{});
+        fire(sd, IConst<4>{}); fire(sd, IConst<5>{});
         if constexpr (KIND == 3) {
             if (nxt) fill_rowtab();   // consumed in this tile's last-but-one k-tile
         }
@@ -456,7 +431,7 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     auto epi_rows_left = [&]() -> int { return F32O ? p.M - (c_m0 + wm * 64 + er) : 0x40000000; };   // (epilogue_f32: rows of this lane's column of slices that exist)
     auto epi_rofs = [&](const int r) -> long {
         if (p.out_seg <= 0) return (long)r;
-        return (long)r + (long)(fast_div5(c_mb + r, p.out_seg) - c_seg0) * p.out_seg;
+        return (long)r + (long)(fast_div(c_mb + r, p.out_seg) - c_seg0) * p.out_seg;
     };
     constexpr int EPI_DEP = RING;
 #define EPI_STAMP(i) STAMP5(tseq, i)
@@ -477,12 +452,12 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     for (;;) {
         STAMP5(tseq, 0);
         // embedded sync of k-tile kt opens k-tile kt + 1: after an epilogue the first two k-tiles are known to have landed
-        ktile(IC5<3>{}, first ? 2 : 0);
-        for (int kt = 1; kt < nk - 2; ++kt) ktile(IC5<0>{}, 2);
+        ktile(IConst<3>{}, first ? 2 : 0);
+        for (int kt = 1; kt < nk - 2; ++kt) ktile(IConst<0>{}, 2);
         STAMP5(tseq, 1);
-        ktile(IC5<1>{}, 3);    // opens the last k-tile: younger = this k-tile's operand requests + the next tile's first pieces
+        ktile(IConst<1>{}, 3);    // opens the last k-tile: younger = this k-tile's operand requests + the next tile's first pieces
         STAMP5(tseq, 4);
-        ktile(IC5<2>{}, 0);    // opens the epilogue: barrier only
+        ktile(IConst<2>{}, 0);    // opens the epilogue: barrier only
         STAMP5(tseq, 2);
         // after the rotation of the last k-tile its stage is s_dst (the next DMA destination): scratch until the next barrier
         if constexpr (F32O) epilogue_f32(s_dst, al_f32);

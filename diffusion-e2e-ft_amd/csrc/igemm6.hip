@@ -43,8 +43,6 @@ constexpr int TH = 8, TW = 32;
 constexpr int B_STAGE = BN * 128;
 constexpr int DEP = NW * 64 * 3 * 4;
 constexpr int NORM_CMAX = 640;                                          // NORM: input channels the (a, mean, beta) table of one image holds
-constexpr unsigned int OOB = 0xF0000000u;
-constexpr unsigned int RECORDS = 0xE0000000u;
 // KT x KT taps (3: the 3x3 / pad-1 convolutions; 2: round 6, the 2x2 parity phases of the 2x-upsampler convolutions, e2eft_upconv2x_fwd)
 template <int KT> struct Geo {
     static constexpr int NT = KT * KT;                                      // k-tiles per 64-channel chunk
@@ -64,29 +62,6 @@ template <int KT> struct Geo {
     static constexpr int a_first(int t) { return KT == 3 ? t : 2 * t; }
 };
 }  // namespace patchk
-
-template <typename T> struct Mma6;
-template <> struct Mma6<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma6<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
-typedef __attribute__((address_space(3))) void* lptr6_t;
-template <int V> using IC6 = std::integral_constant<int, V>;
-
-__device__ __forceinline__ int fast_div6(int n, int d) {   // float estimate + one correction (quotients below 2^22)
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) --q;
-    else if (r >= d) ++q;
-    return q;
-}
 
 // NORM: the input is read through GroupNorm(+SiLU) — the statistics exist (e2eft_groupnorm_fwd_stats), the apply pass does not: every lane normalises, in
 // place in LDS, exactly the 16-byte units of the patch it fetched itself (k-tile t of a chunk: piece t - 2, landed since the previous k-tile's wait), with the
@@ -147,15 +122,15 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     __amdgpu_buffer_rsrc_t rs1, rs2, rsw, rsa;
     unsigned int a_ldb = 0, a_coff = 0;       // A pieces of the chunk being fetched: pixel pitch in bytes, channel + swizzle offset
     int n_c0 = 0, tab_img = -1;               // NORM: first of this lane's eight channels in the chunk being fetched; image whose coefficients are in LDS
-    const unsigned lds_base = (unsigned)(uintptr_t)((lptr6_t)smem);
+    const unsigned lds_base = (unsigned)(uintptr_t)((lds_ptr_t)smem);
 
     auto tile_coords = [&](const int u) {
         int mt = u, nt = 0;
-        if (p.ntiles > 1) { mt = fast_div6(u, p.ntiles); nt = u - mt * p.ntiles; }
+        if (p.ntiles > 1) { mt = fast_div(u, p.ntiles); nt = u - mt * p.ntiles; }
         d_mt = mt; d_n0 = nt * BN;
-        d_img = fast_div6(mt, tpi);
+        d_img = fast_div(mt, tpi);
         const int rem = mt - d_img * tpi;
-        const int ty = fast_div6(rem, tw);
+        const int ty = fast_div(rem, tw);
         d_oy0 = ty * TH; d_ox0 = (rem - ty * tw) * TW;
     };
     auto set_a = [&](const bool valid) {      // A address state of the loader's tile (d_*): pixel indices of the six rows, image descriptors
@@ -167,8 +142,8 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         }
         const T* b1 = (const T*)p.x1 + (long)d_img * Hs * Ws * p.ldx1;
         const T* b2 = p.x2 ? (const T*)p.x2 + (long)d_img * Hs * Ws * p.ldx2 : b1;
-        rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)b1, 0, RECORDS, 0x00020000);
-        rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)b2, 0, RECORDS, 0x00020000);
+        rs1 = whole_range_rsrc(b1);
+        rs2 = whole_range_rsrc(b2);
         if constexpr (NORM) {
             if (valid && d_img != tab_img) {   // (uniform, once per image and workgroup) nobody reads the table between k-tile 8 of a chunk and k-tile 2 of the next
                 tab_img = d_img;
@@ -184,11 +159,11 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         }
     };
     auto set_b = [&](const bool valid) {      // B address state of the loader's tile
-        rsw = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.w + (long)d_n0 * p.ldw), 0, RECORDS, 0x00020000);
+        rsw = whole_range_rsrc(((const T*)p.w + (long)d_n0 * p.ldw));
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int n = d_n0 + lrow + 64 * i;
-            brow[i] = (valid && n < p.N) ? (unsigned)((lrow + 64 * i) * p.ldw + jcb * 8) * (unsigned)sizeof(T) : OOB;
+            brow[i] = (valid && n < p.N) ? (unsigned)((lrow + 64 * i) * p.ldw + jcb * 8) * (unsigned)sizeof(T) : SRD_OOB;
         }
     };
     auto set_chunk = [&](const int cn) {      // source of chunk cn's patch: x1 for channels below c1, x2 above (concat)
@@ -202,19 +177,19 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     int bs_cur = OFF_B, bs_nxt = OFF_B + B_STAGE, bs_dst = OFF_B + 2 * B_STAGE;
     auto fire_a = [&](auto ic, const int pdst) {   // piece i (0 .. NPI-1) of the patch being fetched (pieces beyond the last: zeros into the dump kilobyte)
         constexpr int i = decltype(ic)::value;
-        unsigned off = OOB;
+        unsigned off = SRD_OOB;
         int dst = OFF_DUMP + wave * 1024;
         if constexpr (i < NPI) {
-            off = pix[i] < 0 ? OOB : (unsigned)pix[i] * a_ldb + a_coff;
+            off = pix[i] < 0 ? SRD_OOB : (unsigned)pix[i] * a_ldb + a_coff;
             const int j = wave + 8 * i;
             if (j < PPIECES) dst = pdst + j * 1024;   // (wave-uniform)
         }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr6_t)(smem + dst), 16, off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr_t)(smem + dst), 16, off, 0, 0, 0);
     };
     auto fire_b = [&](const int stage, const unsigned kofs) {
         char* sb = smem + stage + wave * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lptr6_t)sb, 16, brow[0] + kofs, 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lptr6_t)(sb + 64 * 128), 16, brow[1] + kofs, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)sb, 16, brow[0] + kofs, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(sb + 64 * 128), 16, brow[1] + kofs, 0, 0, 0);
     };
 
     // NORM: piece i of the patch in buffer `pbuf` (fetched by this wave, landed): x -> act((x - mean) * a + beta) in place, in three steps that a
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         }
         n_o[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, T2));
     };
-    auto norm_half = [&](auto hc) { norm_pair(hc, IC6<0>{}); norm_pair(hc, IC6<1>{}); };   // (prologue only: nothing to hide behind)
+    auto norm_half = [&](auto hc) { norm_pair(hc, IConst<0>{}); norm_pair(hc, IConst<1>{}); };   // (prologue only: nothing to hide behind)
     // one MFMA group with one value pair's arithmetic in its shadow: the matrix pipe takes 32 cycles per MFMA, the wave's VALU issues meanwhile — as long as
     // the instructions alternate.  (Round 3 placed each half behind a whole group: the pipe idled while 30 VALU instructions ran, 806-861 TF/s against 1160-1190.)
     auto interleave4 = [&]() {
@@ -330,10 +305,10 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     for (int g = 0; g < 4; ++g) bofs[g] = (wn * 64 + l31) * 128 + (((g * 2 + h) ^ ((l31 >> 1) & 7)) * 16);
     const int rbase = 2 * wm * PW + l31;      // patch row of this lane's first output pixel at tap (0, 0)
     auto mma_group = [&](const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
-        acc[0][0] = Mma6<T>::run(a0, b0, acc[0][0]);
-        acc[0][1] = Mma6<T>::run(a0, b1, acc[0][1]);
-        acc[1][0] = Mma6<T>::run(a1, b0, acc[1][0]);
-        acc[1][1] = Mma6<T>::run(a1, b1, acc[1][1]);
+        acc[0][0] = Mma32x32x16<T>::run(a0, b0, acc[0][0]);
+        acc[0][1] = Mma32x32x16<T>::run(a0, b1, acc[0][1]);
+        acc[1][0] = Mma32x32x16<T>::run(a1, b0, acc[1][0]);
+        acc[1][1] = Mma32x32x16<T>::run(a1, b1, acc[1][1]);
     };
 
     // ---- epilogue operands requested ahead of their use (as igemm5)
@@ -388,24 +363,24 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         constexpr bool NRM = NORM && t >= 2 && t <= 7;      // this k-tile normalises piece t - 2 of the next patch (landed since the previous k-tile's wait)
         // the unit and the coefficients of its first four channels are requested FIRST: LDS returns in order, so the wait the compiler puts in front of group 0's
         // first MFMA (for fragments requested after these) covers them
-        if constexpr (NRM) norm_issue(IC6<t - 2>{}, pnext);
-        rd(IC6<0>{}, IC6<0>{});
-        rd(IC6<1>{}, IC6<1>{});
+        if constexpr (NRM) norm_issue(IConst<t - 2>{}, pnext);
+        rd(IConst<0>{}, IConst<0>{});
+        rd(IConst<1>{}, IConst<1>{});
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NRM) norm_ready();
-        rd(IC6<2>{}, IC6<2>{});
+        rd(IConst<2>{}, IConst<2>{});
         if constexpr (!(CK == 2 && t == NT - 2)) fire_b(bs_dst, kofs);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (CK == 1 && t == 0) {
             const floatx16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[0][0] = Mma6<T>::run(a0[0], b0[0], z);
-            acc[0][1] = Mma6<T>::run(a0[0], b1[0], z);
-            acc[1][0] = Mma6<T>::run(a1[0], b0[0], z);
-            acc[1][1] = Mma6<T>::run(a1[0], b1[0], z);
+            acc[0][0] = Mma32x32x16<T>::run(a0[0], b0[0], z);
+            acc[0][1] = Mma32x32x16<T>::run(a0[0], b1[0], z);
+            acc[1][0] = Mma32x32x16<T>::run(a1[0], b0[0], z);
+            acc[1][1] = Mma32x32x16<T>::run(a1[0], b1[0], z);
         } else {
             mma_group(a0[0], a1[0], b0[0], b1[0]);
         }
-        if constexpr (NRM) { norm_pair(IC6<0>{}, IC6<0>{}); interleave4(); }
+        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<0>{}); interleave4(); }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (CK == 1 && t == 0) enter_tile();
         if constexpr (t == 0) {
@@ -432,12 +407,12 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             __builtin_amdgcn_sched_barrier(0);
             fire_b(bs_dst, kofs);
         }
-        rd(IC6<3>{}, IC6<0>{});
-        if constexpr (AN >= 1) fire_a(IC6<AF>{}, pnext);   // (3x3: k-tiles 6-8 of a chunk issue the two weight pieces only)
-        if constexpr (AN >= 2) fire_a(IC6<AF + 1>{}, pnext);
+        rd(IConst<3>{}, IConst<0>{});
+        if constexpr (AN >= 1) fire_a(IConst<AF>{}, pnext);   // (3x3: k-tiles 6-8 of a chunk issue the two weight pieces only)
+        if constexpr (AN >= 2) fire_a(IConst<AF + 1>{}, pnext);
         __builtin_amdgcn_sched_barrier(0);
         mma_group(a0[1], a1[1], b0[1], b1[1]);
-        if constexpr (NRM) { norm_pair(IC6<0>{}, IC6<1>{}); interleave4(); }
+        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<1>{}); interleave4(); }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NRM) norm_issue2();                // coefficients of the last four channels: back before the barrier (its lgkmcnt(0))
         // lgkmcnt(0): this wave's reads of the current stage have RETURNED before the barrier lets others overwrite it
@@ -449,17 +424,17 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         if constexpr (NRM) norm_mark();
         __builtin_amdgcn_sched_barrier(0);
         mma_group(a0[2], a1[2], b0[2], b1[2]);
-        if constexpr (NRM) { norm_pair(IC6<1>{}, IC6<0>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); }
+        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<0>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); }
         mma_group(a0[0], a1[0], b0[0], b1[0]);
-        if constexpr (NRM) { norm_pair(IC6<1>{}, IC6<1>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); norm_store(IC6<t - 2>{}); }
+        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<1>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); norm_store(IConst<t - 2>{}); }
         asm volatile("" ::: "memory");
         { const int x = bs_cur; bs_cur = bs_nxt; bs_nxt = bs_dst; bs_dst = x; }
         if constexpr (t == NT - 1) { const int x = pcur; pcur = pnext; pnext = x; }
     };
     auto chunk = [&](auto ckc, const int c) {
-        ktile(IC6<0>{}, ckc, c); ktile(IC6<1>{}, ckc, c); ktile(IC6<2>{}, ckc, c); ktile(IC6<3>{}, ckc, c);
+        ktile(IConst<0>{}, ckc, c); ktile(IConst<1>{}, ckc, c); ktile(IConst<2>{}, ckc, c); ktile(IConst<3>{}, ckc, c);
         if constexpr (KT == 3) {
-            ktile(IC6<4>{}, ckc, c); ktile(IC6<5>{}, ckc, c); ktile(IC6<6>{}, ckc, c); ktile(IC6<7>{}, ckc, c); ktile(IC6<8>{}, ckc, c);
+            ktile(IConst<4>{}, ckc, c); ktile(IConst<5>{}, ckc, c); ktile(IConst<6>{}, ckc, c); ktile(IConst<7>{}, ckc, c); ktile(IConst<8>{}, ckc, c);
         }
     };
 
@@ -477,24 +452,24 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     set_a(true);
     set_b(true);
     set_chunk(0);
-    fire_a(IC6<0>{}, pcur); fire_a(IC6<1>{}, pcur); fire_a(IC6<2>{}, pcur);
-    fire_a(IC6<3>{}, pcur); fire_a(IC6<4>{}, pcur);
-    if constexpr (NPI > 5) fire_a(IC6<5>{}, pcur);
+    fire_a(IConst<0>{}, pcur); fire_a(IConst<1>{}, pcur); fire_a(IConst<2>{}, pcur);
+    fire_a(IConst<3>{}, pcur); fire_a(IConst<4>{}, pcur);
+    if constexpr (NPI > 5) fire_a(IConst<5>{}, pcur);
     fire_b(bs_cur, 0u);
     fire_b(bs_nxt, (unsigned)p.cin * (unsigned)sizeof(T));
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // the first patch and k-tile 0's weights
     if constexpr (NORM) {
         __syncthreads();                                      // the coefficient table (written in set_a) is visible
-        auto whole = [&](auto ic) { norm_issue(ic, pcur); norm_wait(); norm_half(IC6<0>{}); norm_issue2(); norm_wait(); norm_half(IC6<1>{}); norm_store(ic); };
-        whole(IC6<0>{}); whole(IC6<1>{}); whole(IC6<2>{}); whole(IC6<3>{}); whole(IC6<4>{}); whole(IC6<5>{});
+        auto whole = [&](auto ic) { norm_issue(ic, pcur); norm_wait(); norm_half(IConst<0>{}); norm_issue2(); norm_wait(); norm_half(IConst<1>{}); norm_store(ic); };
+        whole(IConst<0>{}); whole(IConst<1>{}); whole(IConst<2>{}); whole(IConst<3>{}); whole(IConst<4>{}); whole(IConst<5>{});
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     for (;;) {
-        chunk(IC6<1>{}, 0);
-        for (int c = 1; c < nch - 1; ++c) chunk(IC6<0>{}, c);
-        chunk(IC6<2>{}, nch - 1);
+        chunk(IConst<1>{}, 0);
+        for (int c = 1; c < nch - 1; ++c) chunk(IConst<0>{}, c);
+        chunk(IConst<2>{}, nch - 1);
         // the patch buffer of the last chunk (pnext after the swap) is scratch until the next tile's second patch is requested
         if constexpr (F32O) epilogue_f32(pnext, al_f32);
         else if constexpr (RES) epilogue(pnext, 0L);

@@ -20,8 +20,7 @@
 //   * partial sums leave as fp32 [split][Co][kh kw cin]; e2eft_colsum (the reduction the split-K NT path already used) adds the splits.
 // Eligibility is decided here (returns E2EFT_ERR_UNSUPPORTED and the caller keeps the transpose + im2col_t + GEMM path): cin and c1 multiples
 // of 64, no fused upsample, tensors below 4 GB.  fp32 (round 6): wgrad32_kernel below, the same decomposition on v_mfma_f32_32x32x2_f32.
-#include "common.h"
-#include <type_traits>
+#include "gfx950.h"
 
 namespace e2eft {
 
@@ -45,37 +44,6 @@ struct WgradParams {
     float alpha;
 };
 
-template <typename T> struct MmaW;
-template <> struct MmaW<f16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaW<bf16> {
-    __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
-typedef short short4vw __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 tr_read_w(const char* p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4vw*)p));
-}
-// one LDS-DMA piece (64 lanes x 16 B -> 1 KiB at m0) from asm: the compiler must not count it (it would drain vmcnt in front of LDS reads it cannot
-// prove disjoint); the kernel counts its own pieces — six per wave and k-tile, always.  m0 is saved and restored (compiler-reserved).
-__device__ __forceinline__ void dma_piece_w(const __amdgpu_buffer_rsrc_t& rs, const unsigned voff, const unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rs), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ int fdiv_w(int n, int d) {   // float estimate + one correction (quotients below 2^22)
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    if (r < 0) --q;
-    else if (r >= d) ++q;
-    return q;
-}
-
 // grid (ceil(N / 256), ceil(M / 128), nsplit), 512 threads.  Round 3, second version: the first one (128 x 128 tiles, 4 waves, two stages, two
 // workgroups per CU) waited for k-tile t + 1 at the end of k-tile t — 16 MFMAs = 0.25 us of cover for a 1-2 us L2 round trip — and paid two float
 // divisions + 64-bit multiplies per piece: 340-670 TF/s, latency-bound.  Now: three stages (the pieces of k-tile t + 2 are in flight while t multiplies,
@@ -89,7 +57,6 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
     using namespace wg;
     constexpr int NB = 6 - NA, BM = 64 * NA, BN = 64 * NB;
     __shared__ __attribute__((aligned(16))) char smem[LDS];
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = NA == 2 ? wave >> 2 : wave >> 1, wn = NA == 2 ? wave & 3 : wave & 1;
@@ -116,7 +83,7 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.x1, 0, (unsigned)(((xpix - 1) * p.ldx1 + p.c1) * (long)sizeof(T)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x1), 0,
                                                                          (unsigned)(((xpix - 1) * (p.x2 ? p.ldx2 : p.ldx1) + (p.x2 ? p.cin - p.c1 : p.c1)) * (long)sizeof(T)), 0x00020000);
-    const unsigned lds0 = (unsigned)(uintptr_t)((lptr_t)smem);
+    const unsigned lds0 = (unsigned)(uintptr_t)((lds_ptr_t)smem);
 
     // ---- loader: wave w moves piece w (pixel rows 8 w .. 8 w + 7 of the k-tile) of all six panels.  Lane l: pixel row r = 8 w + (l >> 3), LDS slot
     // l & 7 of that row = source chunk (l & 7) ^ key(r).  The lane's output pixel advances by 64 per k-tile: (image, position inside the image) are
@@ -125,7 +92,7 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
     const int sc8 = ((lane & 7) ^ (((r_kt >> 1) & 1) << 2)) * 8;      // first channel (of 64) of this lane's 16 bytes
     const int hw_out = p.hout * p.wout;
     int pix = k_begin + r_kt;                                          // this lane's output pixel in the NEXT k-tile to issue
-    int bimg = fdiv_w(pix, hw_out);
+    int bimg = fast_div(pix, hw_out);
     int rem = pix - bimg * hw_out;
     unsigned ycol[NA];                                                 // dY byte offsets of the lane's columns (OOB beyond M)
 #pragma unroll
@@ -139,8 +106,8 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
         const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(stage * STAGE + wave * 1024)));
         const unsigned yrow = (unsigned)pix * ldyb;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) dma_piece_w(rsy, (pok && ycol[a] != OOB) ? yrow + ycol[a] : OOB, dst + (unsigned)(a * PANEL));
-        const int oy = fdiv_w(rem, p.wout), ox = rem - oy * p.wout;
+        for (int a = 0; a < NA; ++a) lds_dma_piece(rsy, (pok && ycol[a] != OOB) ? yrow + ycol[a] : OOB, dst + (unsigned)(a * PANEL));
+        const int oy = fast_div(rem, p.wout), ox = rem - oy * p.wout;
         const int iy0 = oy * p.stride - p.pad_t, ix0 = ox * p.stride - p.pad_l;
         const int irow0 = bimg * p.hin;
 #pragma unroll
@@ -149,9 +116,9 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
             const bool ok = pok && cok[c] && (unsigned)iy < (unsigned)p.hin && (unsigned)ix < (unsigned)p.win;
             const unsigned ipix = (unsigned)((irow0 + iy) * p.win + ix);
             if (src2[c]) {      // (uniform branch: a descriptor select would leave the SGPRs)
-                dma_piece_w(rs2, ok ? (ipix * (unsigned)p.ldx2 + (unsigned)(ci0[c] - p.c1 + sc8)) * (unsigned)sizeof(T) : OOB, dst + (unsigned)((NA + c) * PANEL));
+                lds_dma_piece(rs2, ok ? (ipix * (unsigned)p.ldx2 + (unsigned)(ci0[c] - p.c1 + sc8)) * (unsigned)sizeof(T) : OOB, dst + (unsigned)((NA + c) * PANEL));
             } else {
-                dma_piece_w(rs1, ok ? (ipix * (unsigned)p.ldx1 + (unsigned)(ci0[c] + sc8)) * (unsigned)sizeof(T) : OOB, dst + (unsigned)((NA + c) * PANEL));
+                lds_dma_piece(rs1, ok ? (ipix * (unsigned)p.ldx1 + (unsigned)(ci0[c] + sc8)) * (unsigned)sizeof(T) : OOB, dst + (unsigned)((NA + c) * PANEL));
             }
         }
         pix += BK;
@@ -171,8 +138,8 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
     const int fo[2] = {frag_off(0), frag_off(1)};
     auto frag = [&](const char* panel, const int blk, const int ks) -> u32x4 {
         const char* a = panel + fo[blk] + ks * (16 * 128);
-        const u32x2 v0 = tr_read_w(a);
-        const u32x2 v1 = tr_read_w(a + 4 * 128);
+        const u32x2 v0 = lds_read_tr16(a);
+        const u32x2 v1 = lds_read_tr16(a + 4 * 128);
         return u32x4{v0[0], v0[1], v1[0], v1[1]};
     };
 
@@ -211,10 +178,10 @@ __global__ __launch_bounds__(512) void wgrad_kernel(const WgradParams p) {
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                acc[0][0] = MmaW<T>::run(fa[c][0], fb[c][0], acc[0][0]);
-                acc[0][1] = MmaW<T>::run(fa[c][0], fb[c][1], acc[0][1]);
-                acc[1][0] = MmaW<T>::run(fa[c][1], fb[c][0], acc[1][0]);
-                acc[1][1] = MmaW<T>::run(fa[c][1], fb[c][1], acc[1][1]);
+                acc[0][0] = Mma32x32x16<T>::run(fa[c][0], fb[c][0], acc[0][0]);
+                acc[0][1] = Mma32x32x16<T>::run(fa[c][0], fb[c][1], acc[0][1]);
+                acc[1][0] = Mma32x32x16<T>::run(fa[c][1], fb[c][0], acc[1][0]);
+                acc[1][1] = Mma32x32x16<T>::run(fa[c][1], fb[c][1], acc[1][1]);
             }
             asm volatile("" ::: "memory");
             st2 = st;
@@ -260,7 +227,6 @@ __global__ __launch_bounds__(512) void wgrad32_kernel(const WgradParams p) {
     using namespace wg32;
     constexpr int NB = 6 - NA, BM = 64 * NA, BN = 64 * NB;
     __shared__ __attribute__((aligned(16))) char smem[LDS];
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = NA == 2 ? wave >> 2 : wave >> 1, wn = NA == 2 ? wave & 3 : wave & 1;
@@ -286,14 +252,14 @@ __global__ __launch_bounds__(512) void wgrad32_kernel(const WgradParams p) {
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.x1, 0, (unsigned)(((xpix - 1) * p.ldx1 + p.c1) * 4L), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x1), 0,
                                                                          (unsigned)(((xpix - 1) * (p.x2 ? p.ldx2 : p.ldx1) + (p.x2 ? p.cin - p.c1 : p.c1)) * 4L), 0x00020000);
-    const unsigned lds0 = (unsigned)(uintptr_t)((lptr_t)smem);
+    const unsigned lds0 = (unsigned)(uintptr_t)((lds_ptr_t)smem);
 
     // ---- loader: wave w moves piece w (pixel rows 4 w .. 4 w + 3 of the k-tile) of all six panels; lane l: row 4 w + (l >> 4), channels 4 (l & 15) .. + 3 of the chunk
     const int r_kt = 4 * wave + (lane >> 4);
     const int sc4 = (lane & 15) * 4;
     const int hw_out = p.hout * p.wout;
     int pix = k_begin + r_kt;
-    int bimg = fdiv_w(pix, hw_out);
+    int bimg = fast_div(pix, hw_out);
     int rem = pix - bimg * hw_out;
     unsigned ycol[NA];
 #pragma unroll
@@ -307,8 +273,8 @@ __global__ __launch_bounds__(512) void wgrad32_kernel(const WgradParams p) {
         const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(stage * STAGE + wave * 1024)));
         const unsigned yrow = (unsigned)pix * ldyb;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) dma_piece_w(rsy, (pok && ycol[a] != OOB) ? yrow + ycol[a] : OOB, dst + (unsigned)(a * PANEL));
-        const int oy = fdiv_w(rem, p.wout), ox = rem - oy * p.wout;
+        for (int a = 0; a < NA; ++a) lds_dma_piece(rsy, (pok && ycol[a] != OOB) ? yrow + ycol[a] : OOB, dst + (unsigned)(a * PANEL));
+        const int oy = fast_div(rem, p.wout), ox = rem - oy * p.wout;
         const int iy0 = oy * p.stride - p.pad_t, ix0 = ox * p.stride - p.pad_l;
         const int irow0 = bimg * p.hin;
 #pragma unroll
@@ -317,9 +283,9 @@ __global__ __launch_bounds__(512) void wgrad32_kernel(const WgradParams p) {
             const bool ok = pok && cok[c] && (unsigned)iy < (unsigned)p.hin && (unsigned)ix < (unsigned)p.win;
             const unsigned ipix = (unsigned)((irow0 + iy) * p.win + ix);
             if (src2[c]) {      // (uniform branch)
-                dma_piece_w(rs2, ok ? (ipix * (unsigned)p.ldx2 + (unsigned)(ci0[c] - p.c1 + sc4)) * 4u : OOB, dst + (unsigned)((NA + c) * PANEL));
+                lds_dma_piece(rs2, ok ? (ipix * (unsigned)p.ldx2 + (unsigned)(ci0[c] - p.c1 + sc4)) * 4u : OOB, dst + (unsigned)((NA + c) * PANEL));
             } else {
-                dma_piece_w(rs1, ok ? (ipix * (unsigned)p.ldx1 + (unsigned)(ci0[c] + sc4)) * 4u : OOB, dst + (unsigned)((NA + c) * PANEL));
+                lds_dma_piece(rs1, ok ? (ipix * (unsigned)p.ldx1 + (unsigned)(ci0[c] + sc4)) * 4u : OOB, dst + (unsigned)((NA + c) * PANEL));
             }
         }
         pix += BK;
