@@ -384,7 +384,6 @@ static void attn512_plan(const E2eftAttnDesc* d, int cus, int& nqb, int& n_main,
     n_main = (int)(blocks - rem);
 }
 
-int device_cus();   // api.hip
 
 }  // namespace e2eft
 

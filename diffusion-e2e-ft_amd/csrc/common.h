@@ -14,6 +14,8 @@ char* err_buf();
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
 int option(int key);   // process-wide tuning options (e2eft_set_option), api.hip
+int device_cus();      // api.hip: CU count of the CURRENT device (the one the caller's stream belongs to), a multiple of 8; 0 on failure
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 void tag_kernel(const char* fmt, ...);   // thread-local name of the kernel a launcher just enqueued (e2eft_debug_last_kernel: bench.py --detail)
 
 #define E2EFT_REQUIRE(cond, ...)                                     \

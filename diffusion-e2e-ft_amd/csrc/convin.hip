@@ -153,35 +153,30 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
 }
 
 static std::atomic<long> g_thin_launches{0};
-int device_cus();   // api.hip
+
+static bool thin_eligible(int dtype, int mode, const IgemmParams& p, int nz, TilePlan& t) {
+    using namespace thin;
+    if (!option(E2EFT_OPT_PERSISTENT) || !option(E2EFT_OPT_THIN_INPUT_CONV)) return false;
+    if (mode != 1 || nz != 1 || (dtype != E2EFT_F16 && dtype != E2EFT_BF16)) return false;
+    if (p.ksplit_taps > 0 || p.bias_along_m || p.residual || p.rowadd || p.x2) return false;
+    if (p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.zins > 1) return false;
+    if (p.hl != p.hin || p.wl != p.win || p.hout != p.hin || p.wout != p.win) return false;
+    if (p.cin != 8 || p.c1 != 8 || p.ldx1 != 8 || p.K != 72 || p.ldw % 8 != 0) return false;
+    if (p.win % TW != 0 || p.hin % TH != 0) return false;
+    if (p.N % 8 != 0 || p.ldo % 8 != 0 || !al16(p.out) || !al16(p.x1) || !al16(p.w)) return false;   // (the bias is read per column: no vector, no alignment rule)
+    if ((long)p.M * 16 >= SRD_SPAN_MAX || p.M % (p.hin * p.win) != 0) return false;
+    const int cus = persistent_grid();
+    if (!plan_tiles(p, 1, BM, BN, cus, 4 * 2L * cus, t)) return false;                                // two tiles per CU
+    return !p.gn_partial || p.rows_per_img == p.hin * p.win;
+}
 
 int launch_conv_thin_in(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s) {
-    using namespace thin;
-    if (!option(E2EFT_OPT_PERSISTENT) || !option(E2EFT_OPT_THIN_INPUT_CONV)) return -1;
-    if (mode != 1 || nz != 1 || (dtype != E2EFT_F16 && dtype != E2EFT_BF16)) return -1;
-    if (p.ksplit_taps > 0 || p.bias_along_m || p.residual || p.rowadd || p.x2) return -1;
-    if (p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.zins > 1) return -1;
-    if (p.hl != p.hin || p.wl != p.win || p.hout != p.hin || p.wout != p.win) return -1;
-    if (p.cin != 8 || p.c1 != 8 || p.ldx1 != 8 || p.K != 72 || p.ldw % 8 != 0) return -1;
-    if (p.win % TW != 0 || p.hin % TH != 0) return -1;
-    if (p.N % 8 != 0 || p.ldo % 8 != 0 || (((uintptr_t)p.out) & 15) != 0 || (((uintptr_t)p.x1) & 15) != 0 || (((uintptr_t)p.w) & 15) != 0) return -1;
-    if ((long)p.M * 16 >= 0xD0000000L || p.M % (p.hin * p.win) != 0) return -1;
-    int cus = device_cus();
-    if (cus == 0) return -1;
-    const int gopt = option(E2EFT_OPT_PERSISTENT_GRID);
-    if (gopt >= 8 && gopt < cus) cus = gopt;
-    const int mtiles = p.M / BM, ntiles = cdiv(p.N, BN);
-    const long total = (long)mtiles * ntiles;
-    if (total < 2L * cus || total > 2000000000L || mtiles >= (1 << 22)) return -1;
-    if (p.gn_partial) {
-        if (p.rows_per_img != p.hin * p.win) return -1;
-        p.gn_nslabs = p.rows_per_img / BM;
-    }
-    p.mtiles = mtiles;
-    p.ntiles = ntiles;
+    TilePlan t;
+    if (!thin_eligible(dtype, mode, p, nz, t)) return -1;
+    apply_plan(p, t);
     g_thin_launches.fetch_add(1, std::memory_order_relaxed);
-    if (dtype == E2EFT_F16) hipLaunchKernelGGL((conv_thin_in_kernel<f16>), dim3(cus), dim3(512), 0, s, p, (int)total);
-    else hipLaunchKernelGGL((conv_thin_in_kernel<bf16>), dim3(cus), dim3(512), 0, s, p, (int)total);
+    if (dtype == E2EFT_F16) hipLaunchKernelGGL((conv_thin_in_kernel<f16>), dim3(t.grid), dim3(512), 0, s, p, (int)t.total);
+    else hipLaunchKernelGGL((conv_thin_in_kernel<bf16>), dim3(t.grid), dim3(512), 0, s, p, (int)t.total);
     tag_kernel("conv_thin_in_kernel<%s>", dtype == E2EFT_F16 ? "_Float16" : "__bf16");
     return check_launch("conv_thin_in");
 }

@@ -87,11 +87,6 @@ __global__ __launch_bounds__(256) void split2_f16_kernel(long pixels, int c, int
     }
 }
 
-bool igemm_patch_eligible(int dtype, int mode, IgemmParams& p, int nz);              // igemm6.hip
-int launch_igemm_patch(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
-bool igemm_persistent_eligible(int dtype, int mode, IgemmParams& p, int nz);        // igemm5.hip
-int launch_igemm_persistent(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
-
 // the implicit-GEMM parameter block of an fp32 convolution whose input arrives as split planes: any filter / stride / padding of e2eft_conv2d_fwd without a second
 // source and without a fused upsample; K = taps * 3 * c1
 static bool f32split_params(const E2eftConvDesc* d, IgemmParams& p) {
@@ -101,17 +96,9 @@ static bool f32split_params(const E2eftConvDesc* d, IgemmParams& p) {
     if ((d->hout - 1) * d->stride - d->pad_t >= d->hl || (d->wout - 1) * d->stride - d->pad_l >= d->wl) return false;
     const int taps = d->kh * d->kw;
     if (d->c1 % 64 != 0 || d->ldx1 < 2 * d->c1 || d->ldx1 % 8 != 0 || d->ldw < taps * 3 * d->c1 || d->ldw % 8 != 0 || (long)d->batch * d->hout * d->wout >= 2147483647L) return false;
-    p = IgemmParams{};
-    p.M = d->batch * d->hout * d->wout; p.N = d->cout; p.K = taps * 3 * d->c1;
-    p.ldx1 = d->ldx1; p.c1 = 3 * d->c1; p.cin = 3 * d->c1; p.split_c = d->c1;
-    p.hin = d->hin; p.win = d->win; p.hl = d->hl; p.wl = d->wl;
-    p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.hout = d->hout; p.wout = d->wout;
-    p.up_sh = p.up_sw = 1.f;
-    p.ldw = d->ldw; p.ldr = d->ldr > 0 ? d->ldr : d->ldo; p.ldo = d->ldo;
-    p.rows_per_img = d->hout * d->wout;
-    p.alpha = d->alpha;
-    p.nzi = 1;
+    p = conv_params(d);
+    p.c1 = p.cin = 3 * d->c1; p.split_c = d->c1; p.K = taps * 3 * d->c1;   // the split form
+    if (d->ldr <= 0) p.ldr = d->ldo;
     return true;
 }
 
@@ -122,7 +109,7 @@ using namespace e2eft;
 extern "C" int e2eft_f32_split2(const float* x, int64_t pixels, int32_t c, int32_t ldx, void* planes, int32_t ldp, float* scale, void* stream) {
     E2EFT_REQUIRE(x && planes && scale && pixels > 0, "f32_split2: null pointer / empty tensor");
     E2EFT_REQUIRE(c > 0 && c % 8 == 0 && ldx >= c && ldx % 4 == 0 && ldp >= 2 * c && ldp % 8 == 0, "f32_split2: c=%d ldx=%d ldp=%d (c %% 8, ldx %% 4, ldp %% 8, ldp >= 2 c)", c, ldx, ldp);
-    E2EFT_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)planes & 15) == 0 && ((uintptr_t)scale & 3) == 0, "f32_split2: alignment");
+    E2EFT_REQUIRE(al16(x) && al16(planes) && ((uintptr_t)scale & 3) == 0, "f32_split2: alignment");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2: memset failed");
     const long units = pixels * (c / 8);
@@ -141,7 +128,7 @@ extern "C" int e2eft_f32_split2(const float* x, int64_t pixels, int32_t c, int32
 extern "C" int e2eft_f32_split_weight(const float* w, int64_t rows, int32_t c, void* w_split, float* scale, void* stream) {
     E2EFT_REQUIRE(w && w_split && scale && rows > 0, "f32_split_weight: null pointer / empty weight");
     E2EFT_REQUIRE(c > 0 && c % 8 == 0, "f32_split_weight: c=%d must be a multiple of 8", c);
-    E2EFT_REQUIRE(((uintptr_t)w & 15) == 0 && ((uintptr_t)w_split & 15) == 0 && ((uintptr_t)scale & 3) == 0, "f32_split_weight: alignment");
+    E2EFT_REQUIRE(al16(w) && al16(w_split) && ((uintptr_t)scale & 3) == 0, "f32_split_weight: alignment");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split_weight: memset failed");
     const long units = rows * (c / 8);
@@ -160,7 +147,7 @@ extern "C" int e2eft_f32_split2_cat(const float* x1, int32_t c1, int32_t ldx1, c
     E2EFT_REQUIRE(x1 && x2 && planes && scale && pixels > 0, "f32_split2_cat: null pointer / empty tensor");
     E2EFT_REQUIRE(c1 > 0 && c1 % 8 == 0 && c2 > 0 && c2 % 8 == 0 && ldx1 >= c1 && ldx1 % 4 == 0 && ldx2 >= c2 && ldx2 % 4 == 0 && ldp >= 2 * (c1 + c2) && ldp % 8 == 0,
                   "f32_split2_cat: c1=%d c2=%d ldx1=%d ldx2=%d ldp=%d", c1, c2, ldx1, ldx2, ldp);
-    E2EFT_REQUIRE(((uintptr_t)x1 & 15) == 0 && ((uintptr_t)x2 & 15) == 0 && ((uintptr_t)planes & 15) == 0 && ((uintptr_t)scale & 3) == 0, "f32_split2_cat: alignment");
+    E2EFT_REQUIRE(al16(x1) && al16(x2) && al16(planes) && ((uintptr_t)scale & 3) == 0, "f32_split2_cat: alignment");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2_cat: memset failed");
     const float* xs[2] = {x1, x2};
@@ -184,13 +171,7 @@ extern "C" int e2eft_f32_split2_cat(const float* x1, int32_t c1, int32_t ldx1, c
 // tensor, ldx1 = pixel stride of the PLANES in f16 elements (>= 2 c1), ldw = weight row length in f16 elements (>= kh kw 3 c1), ldo / ldr in fp32 elements
 extern "C" int e2eft_conv2d_fwd_f32split_supported(const E2eftConvDesc* d) {
     IgemmParams p;
-    if (!f32split_params(d, p)) return 0;
-    void* const al = (void*)(uintptr_t)256;
-    p.x1 = al; p.w = al; p.out = al;
-    IgemmParams q = p;
-    if (igemm_patch_eligible(E2EFT_F16, 1, q, 1)) return 1;
-    q = p;
-    return igemm_persistent_eligible(E2EFT_F16, 1, q, 1) ? 1 : 0;
+    return f32split_params(d, p) && persistent_family_eligible(E2EFT_F16, 1, p, 1) ? 1 : 0;
 }
 
 extern "C" int e2eft_conv2d_fwd_f32split(const E2eftConvDesc* d, const void* planes, const float* scale, const void* w_split, const float* w_inv_scale, const float* bias,
@@ -199,18 +180,16 @@ extern "C" int e2eft_conv2d_fwd_f32split(const E2eftConvDesc* d, const void* pla
     E2EFT_REQUIRE(d && planes && w_split && out, "conv2d_fwd_f32split: null pointer");
     IgemmParams p;
     if (!f32split_params(d, p)) return fail(E2EFT_ERR_UNSUPPORTED, "conv2d_fwd_f32split: not an fp32 convolution of 64-channel multiples from split planes (ask e2eft_conv2d_fwd_f32split_supported)");
-    E2EFT_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)w_split & 15) == 0 && ((uintptr_t)out & 15) == 0, "conv2d_fwd_f32split: pointers must be 16-byte aligned");
+    E2EFT_REQUIRE(al16(planes) && al16(w_split) && al16(out), "conv2d_fwd_f32split: pointers must be 16-byte aligned");
     p.x1 = planes; p.w = w_split; p.bias = bias; p.residual = residual; p.out = out;
     p.alpha_dev = scale ? scale + 2 : nullptr;
     p.alpha_dev2 = w_inv_scale;
     if (gn_partial && slab_rows) {
-        const size_t need = (size_t)d->batch * (size_t)cdiv(p.rows_per_img, 128) * (size_t)d->cout * 3 * sizeof(float);
-        if (gn_partial_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "conv2d_fwd_f32split: gn_partial %zu < %zu bytes", gn_partial_bytes, need);
+        if (const int rcw = check_gn_partial("conv2d_fwd_f32split", gn_partial_bytes, d->batch, p.rows_per_img, d->cout)) return rcw;
         p.gn_partial = gn_partial;
     }
     hipStream_t s = (hipStream_t)stream;
-    int rc = launch_igemm_patch(E2EFT_F16, 1, p, 1, s);                         // 3x3 / stride 1 / pad 1 on a 32 x 8 grid: the halo-patch kernel
-    if (rc < 0) rc = launch_igemm_persistent(E2EFT_F16, 1, p, 1, s);            // everything else in whole 256-row tiles: igemm5
+    int rc = launch_persistent_family(E2EFT_F16, 1, p, 1, s);                   // 3x3 / stride 1 / pad 1 on a 32 x 8 grid: the halo-patch kernel; else whole 256-row tiles on igemm5
     if (rc < 0 && p.gn_partial) {                                               // statistics need whole tiles inside one image: without them (the consumer runs its own pass)
         p.gn_partial = nullptr;
         rc = launch_igemm_persistent(E2EFT_F16, 1, p, 1, s);
@@ -238,10 +217,7 @@ static bool f32split_gemm_params(const E2eftGemmDesc* d, IgemmParams& p) {
 
 extern "C" int e2eft_gemm_f32split_supported(const E2eftGemmDesc* d) {
     IgemmParams p;
-    if (!f32split_gemm_params(d, p)) return 0;
-    void* const al = (void*)(uintptr_t)256;
-    p.x1 = al; p.w = al; p.out = al;
-    return igemm_persistent_eligible(E2EFT_F16, 0, p, 1) ? 1 : 0;
+    return f32split_gemm_params(d, p) && persistent_family_eligible(E2EFT_F16, 0, p, 1) ? 1 : 0;   // (GEMM mode: igemm5)
 }
 
 extern "C" int e2eft_gemm_f32split(const E2eftGemmDesc* d, const void* planes, const float* scale, const void* w_split, const float* w_inv_scale, const float* bias,
@@ -249,7 +225,7 @@ extern "C" int e2eft_gemm_f32split(const E2eftGemmDesc* d, const void* planes, c
     E2EFT_REQUIRE(d && planes && w_split && out, "gemm_f32split: null pointer");
     IgemmParams p;
     if (!f32split_gemm_params(d, p)) return fail(E2EFT_ERR_UNSUPPORTED, "gemm_f32split: not an fp32 GEMM of 64-column multiples from split planes (ask e2eft_gemm_f32split_supported)");
-    E2EFT_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)w_split & 15) == 0 && ((uintptr_t)out & 15) == 0, "gemm_f32split: pointers must be 16-byte aligned");
+    E2EFT_REQUIRE(al16(planes) && al16(w_split) && al16(out), "gemm_f32split: pointers must be 16-byte aligned");
     p.x1 = planes; p.w = w_split; p.bias = bias; p.residual = residual; p.out = out;
     p.alpha_dev = scale ? scale + 2 : nullptr;
     p.alpha_dev2 = w_inv_scale;
@@ -261,37 +237,15 @@ extern "C" int e2eft_gemm_f32split(const E2eftGemmDesc* d, const void* planes, c
 // ---- nearest-2x upsample + 3x3 / stride-1 / pad-1 convolution in fp32 as four 2x2 phase convolutions of the split planes (e2eft_upconv2x_fwd's algebra, igemm.hip).
 // `d` as e2eft_upconv2x_fwd's (dtype E2EFT_F32, hl = 2 hin, ...) with ldx1 = the planes' pixel stride in f16 elements; w_phase_split: f16 [4][cout][2][2][w0 | w1 | w0]
 // (the fp32 phase weights of autograd.phase_conv_weight split as ONE tensor: one scale).  The halo-patch kernel's 2x2-tap variant where the grid allows, else igemm5.
-static bool f32split_upconv_params(const E2eftConvDesc* d, int ph, IgemmParams& p) {
+static bool f32split_upconv_ok(const E2eftConvDesc* d) {
     if (!d || d->dtype != E2EFT_F32 || d->c2 != 0 || !option(E2EFT_OPT_F32_SPLIT) || !option(E2EFT_OPT_UPCONV_PHASES)) return false;
     if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->hl != 2 * d->hin || d->wl != 2 * d->win || d->hout != d->hl || d->wout != d->wl) return false;
     if (d->batch <= 0 || d->hin <= 0 || d->win <= 0 || d->c1 <= 0 || d->c1 % 64 != 0 || d->cout % 8 != 0 || d->ldo % 8 != 0 || d->alpha != 1.0f) return false;
-    if (d->ldx1 < 2 * d->c1 || d->ldx1 % 8 != 0 || d->win % 16 != 0 || ((long)d->hin * d->win) % 256 != 0 || (long)d->batch * d->hin * d->win >= 2147483647L) return false;
-    const int py = ph >> 1, px = ph & 1;
-    const int rows_img = d->hin * d->win;
-    p = IgemmParams{};
-    p.M = d->batch * rows_img; p.N = d->cout; p.K = 4 * 3 * d->c1;
-    p.ldx1 = d->ldx1; p.c1 = 3 * d->c1; p.cin = 3 * d->c1; p.split_c = d->c1;
-    p.hin = d->hin; p.win = d->win; p.hl = d->hin; p.wl = d->win;
-    p.kh = 2; p.kw = 2; p.stride = 1; p.pad_t = 1 - py; p.pad_l = 1 - px;
-    p.hout = d->hin; p.wout = d->win;
-    p.up_sh = p.up_sw = 1.f;
-    p.ldw = 12 * d->c1; p.ldo = 2 * d->ldo; p.ldr = p.ldo;
-    p.out_seg = d->win;
-    p.rows_per_img = rows_img;
-    p.alpha = 1.f;
-    p.nzi = 1;
-    return true;
+    return !(d->ldx1 < 2 * d->c1 || d->ldx1 % 8 != 0 || d->win % 16 != 0 || ((long)d->hin * d->win) % 256 != 0 || (long)d->batch * d->hin * d->win >= 2147483647L);
 }
 
 extern "C" int e2eft_upconv2x_fwd_f32split_supported(const E2eftConvDesc* d) {
-    IgemmParams p;
-    if (!f32split_upconv_params(d, 0, p)) return 0;
-    void* const al = (void*)(uintptr_t)256;
-    p.x1 = al; p.w = al; p.out = al;
-    IgemmParams q = p;
-    if (igemm_patch_eligible(E2EFT_F16, 1, q, 1)) return 1;
-    q = p;
-    return igemm_persistent_eligible(E2EFT_F16, 1, q, 1) ? 1 : 0;
+    return f32split_upconv_ok(d) && persistent_family_eligible(E2EFT_F16, 1, upconv2x_phase_params(d, 0, 3), 1) ? 1 : 0;
 }
 
 extern "C" int e2eft_upconv2x_fwd_f32split(const E2eftConvDesc* d, const void* planes, const float* scale, const void* w_phase_split, const float* w_inv_scale,
@@ -299,31 +253,14 @@ extern "C" int e2eft_upconv2x_fwd_f32split(const E2eftConvDesc* d, const void* p
     if (slab_rows) *slab_rows = 0;
     E2EFT_REQUIRE(d && planes && w_phase_split && out, "upconv2x_f32split: null pointer");
     if (!e2eft_upconv2x_fwd_f32split_supported(d)) return fail(E2EFT_ERR_UNSUPPORTED, "upconv2x_f32split: this launch is not eligible (ask e2eft_upconv2x_fwd_f32split_supported)");
-    E2EFT_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)w_phase_split & 15) == 0 && ((uintptr_t)out & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0), "upconv2x_f32split: pointers must be 16-byte aligned");
-    const int rows_img = d->hin * d->win, slabs = rows_img / 256;
-    const bool stats = gn_partial && slab_rows;
-    if (stats) {
-        const size_t need = (size_t)d->batch * (size_t)cdiv(4 * rows_img, 128) * (size_t)d->cout * 3 * sizeof(float);
-        if (gn_partial_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "upconv2x_f32split: gn_partial %zu < %zu bytes", gn_partial_bytes, need);
+    E2EFT_REQUIRE(al16(planes) && al16(w_phase_split) && al16(out) && (!bias || al16(bias)), "upconv2x_f32split: pointers must be 16-byte aligned");
+    IgemmParams io = {};
+    io.x1 = planes; io.w = w_phase_split; io.bias = bias; io.out = out;
+    io.alpha_dev = scale ? scale + 2 : nullptr;
+    io.alpha_dev2 = w_inv_scale;
+    if (gn_partial && slab_rows) {
+        if (const int rcw = check_gn_partial("upconv2x_f32split", gn_partial_bytes, d->batch, 4L * d->hin * d->win, d->cout)) return rcw;
+        io.gn_partial = gn_partial;
     }
-    for (int ph = 0; ph < 4; ++ph) {
-        IgemmParams p;
-        f32split_upconv_params(d, ph, p);
-        const int py = ph >> 1, px = ph & 1;
-        p.x1 = planes; p.w = (const char*)w_phase_split + (size_t)ph * d->cout * 12 * d->c1 * 2; p.bias = bias;
-        p.out = (char*)out + ((size_t)py * d->wl + px) * d->ldo * 4;
-        p.alpha_dev = scale ? scale + 2 : nullptr;
-        p.alpha_dev2 = w_inv_scale;
-        if (stats) {
-            p.gn_partial = gn_partial + (size_t)ph * slabs * d->cout * 3;
-            p.gn_islabs = 4 * slabs;
-        }
-        p.mtiles = p.M / 256; p.ntiles = cdiv(p.N, 128);
-        int rc = launch_igemm_patch(E2EFT_F16, 1, p, 1, (hipStream_t)stream);
-        if (rc < 0) rc = launch_igemm_persistent(E2EFT_F16, 1, p, 1, (hipStream_t)stream);
-        if (rc < 0) return fail(E2EFT_ERR_UNSUPPORTED, "upconv2x_f32split: the persistent kernels declined phase %d", ph);
-        if (rc) return rc;
-    }
-    if (stats) *slab_rows = 256;
-    return E2EFT_OK;
+    return run_upconv2x_phases(d, E2EFT_F16, 3, io, true, slab_rows, "upconv2x_f32split", (hipStream_t)stream);
 }

@@ -62,6 +62,9 @@ __device__ __forceinline__ u32x2 lds_read_tr16(const char* p) {
 // check itself does the masking.)
 constexpr unsigned int SRD_RECORDS = 0xE0000000u;
 constexpr unsigned int SRD_OOB = 0xF0000000u;
+// what the launchers hold the kernels' offsets to (host side): everything one descriptor addresses from its base — the images a tile's rows may touch —
+// below SRD_SPAN_MAX, and the rows of one tile, whose offsets are formed in 32 bits before the k-loop advances them, below SRD_TILE_MAX
+constexpr long SRD_SPAN_MAX = 0xD0000000L, SRD_TILE_MAX = 0x40000000L;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t whole_range_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, SRD_RECORDS, 0x00020000);
 }

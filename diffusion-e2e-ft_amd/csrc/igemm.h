@@ -371,14 +371,55 @@ __device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, char* 
     }
 }
 
+// ---- host side: one planner for the family (definitions and the dispatch order: igemm.hip) ---------------------------------------------------------------
+// Eligibility tests READ the parameter block and fill a TilePlan; only the launcher that takes the launch applies the plan to the block it launches.
+struct TilePlan { int grid; long total; int mtiles, ntiles, gn_nslabs; };
+inline void apply_plan(IgemmParams& p, const TilePlan& t) {
+    p.mtiles = t.mtiles;
+    p.ntiles = t.ntiles;
+    if (p.gn_partial) p.gn_nslabs = t.gn_nslabs;
+}
+// workgroups of a persistent launch: the CUs of the current device, or the grid option when that is smaller (tests: a small grid sends small problems through
+// the persistent kernels); 0 = no device.  The only reader of that option outside api.hip.
+int persistent_grid();
+// the common tail of the persistent kernels' tests: bm x bn tiles on `grid` workgroups, at least min_tiles4 / 4 of them (the caller's bar), tile and row indices within
+// the kernels' float-reciprocal splits (quotients below 2^22), one statistics slab per M tile
+bool plan_tiles(const IgemmParams& p, int nz, int bm, int bn, int grid, long min_tiles4, TilePlan& t);
+// the 16-bit vector epilogue (igemm_persistent_epilogue.inc): whole 16-byte units of output, residual and bias
+inline bool vec_epilogue_ok(const IgemmParams& p) {
+    return p.N % 8 == 0 && p.ldo % 8 == 0 && al16(p.out) && (!p.residual || (p.ldr % 8 == 0 && al16(p.residual))) && (!p.bias || al16(p.bias));
+}
+// FAST operand path (LDS-DMA through whole_range_rsrc, es = element size): do all valid offsets stay inside the descriptor?  The 256 rows of a convolution's tile may
+// lie in several images, all addressed from the first one's base.
+inline bool conv_window_in_range(long hin, long win, long ldx, long rows_per_img, long es) { return hin * win * ldx * es * (256 / rows_per_img + 2) < SRD_SPAN_MAX; }
+inline bool fast_operands_in_range(int mode, const IgemmParams& p, long es) {
+    if (128L * p.ldw * es >= SRD_TILE_MAX) return false;
+    return mode == 0 ? 256L * p.ldx1 * es < SRD_TILE_MAX : conv_window_in_range(p.hin, p.win, p.ldx1 > p.ldx2 ? p.ldx1 : p.ldx2, (long)p.hout * p.wout, es);
+}
+
 // v2: 256x128 tile, 8 waves, LDS-DMA (global_load_lds) 3-stage ring — igemm2.hip
 int launch_igemm_v2(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
 // igemm5.hip: persistent workgroups walking a tile sequence (16-bit FAST path, M % 256 == 0, >= 2 tiles per CU); -1 when not eligible
 int launch_igemm_persistent(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
+bool igemm_persistent_eligible(int dtype, int mode, const IgemmParams& p, int nz, TilePlan& t);   // its host-side test alone: pure arithmetic
 // igemm6.hip: persistent, the A operand of a 3x3 / stride-1 / pad-1 convolution as a 2-D halo patch in LDS; -1 when not eligible
 int launch_igemm_patch(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
-bool igemm_patch_eligible(int dtype, int mode, IgemmParams& p, int nz);   // the host-side test of launch_igemm_patch alone (fills p.mtiles / ntiles / gn_nslabs)
+bool igemm_patch_eligible(int dtype, int mode, const IgemmParams& p, int nz, TilePlan& t);
 // convin.hip: 3x3 / stride-1 / pad-1 convolutions with eight input channels (operands straight from global memory, persistent); -1 when not eligible
 int launch_conv_thin_in(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
+// the persistent family in its one order — halo patch, else persistent tiles (a fused normalisation exists on the patch kernel alone); -1 when neither takes the launch
+int launch_persistent_family(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s);
+// ... and its const twin: would the family take this geometry with 16-byte aligned operands (normed: read through a fused GroupNorm)?
+bool persistent_family_eligible(int dtype, int mode, const IgemmParams& geometry, int nz, bool normed = false);
+
+// E2eftConvDesc -> the geometry of its implicit GEMM (no pointers); phase ph of a 2x-upsampler convolution as the 2x2 convolution of e2eft_upconv2x_fwd (split = 3: the
+// operands are f16 split planes of an fp32 tensor, three K blocks per tap)
+IgemmParams conv_params(const E2eftConvDesc* d);
+IgemmParams upconv2x_phase_params(const E2eftConvDesc* d, int ph, int split);
+// the four phases of one upsampler convolution.  io carries x1, w (all four phase weights), bias, out (the full-resolution image), alpha_dev / alpha_dev2 and gn_partial
+// (null: no statistics); persistent = false sends the phases to igemm2.  `who` opens the error messages.
+int run_upconv2x_phases(const E2eftConvDesc* d, int dtype, int split, const IgemmParams& io, bool persistent, int32_t* slab_rows, const char* who, hipStream_t s);
+// the GroupNorm statistics buffer [images][128-row slabs][n][3] fp32: E2EFT_OK, or E2EFT_ERR_WORKSPACE when `have` bytes do not hold it
+int check_gn_partial(const char* who, size_t have, long images, long rows_per_img, long n);
 
 }  // namespace e2eft

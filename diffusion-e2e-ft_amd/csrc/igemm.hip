@@ -67,33 +67,76 @@ static int conv_splitk_plan(const E2eftConvDesc* d) {
     const long tiles = ((M + 127) / 128) * ((d->cout + 127) / 128);
     if (d->kh < 2 || tiles >= 160 || (long)d->kh * d->kw * cin < 2304) return 0;
     if (cin % bk != 0 || d->c1 % bk != 0 || d->cout % epc != 0) return 0;          // FAST path + vector finish
-    const long img_bytes = (long)d->hin * d->win * (d->ldx1 > d->ldx2 ? d->ldx1 : d->ldx2) * (long)dtype_size(d->dtype);
-    if (img_bytes * (256 / ((long)d->hout * d->wout) + 2) >= 0xD0000000L) return 0;
+    if (!conv_window_in_range(d->hin, d->win, d->ldx1 > d->ldx2 ? d->ldx1 : d->ldx2, (long)d->hout * d->wout, (long)dtype_size(d->dtype))) return 0;
     return d->kh;
 }
 
+int persistent_grid() {
+    const int cus = device_cus(), gopt = option(E2EFT_OPT_PERSISTENT_GRID);
+    return gopt >= 8 && gopt < cus ? gopt : cus;
+}
+
+bool plan_tiles(const IgemmParams& p, int nz, int bm, int bn, int grid, long min_tiles4, TilePlan& t) {
+    t.grid = grid;
+    t.mtiles = cdiv(p.M, bm);
+    t.ntiles = cdiv(p.N, bn);
+    t.total = (long)t.mtiles * t.ntiles * nz;
+    t.gn_nslabs = p.rows_per_img / bm;
+    return grid > 0 && 4 * t.total >= min_tiles4 && t.total <= 2000000000L && t.mtiles < (1 << 22);
+}
+
+int launch_persistent_family(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s) {
+    const int rc = launch_igemm_patch(dtype, mode, p, nz, s);                          // big 16-bit 3x3 convolutions: halo patch in LDS (igemm6.hip)
+    return rc >= 0 || p.nrm_ad ? rc : launch_igemm_persistent(dtype, mode, p, nz, s);   // big 16-bit problems: persistent workgroups (igemm5.hip)
+}
+
+bool persistent_family_eligible(int dtype, int mode, const IgemmParams& geometry, int nz, bool normed) {
+    IgemmParams p = geometry;
+    void* const al = (void*)(uintptr_t)256;
+    p.x1 = al; p.w = al; p.out = al;
+    if (normed) p.nrm_ad = (const float*)al;
+    TilePlan t;
+    return igemm_patch_eligible(dtype, mode, p, nz, t) || (!normed && igemm_persistent_eligible(dtype, mode, p, nz, t));
+}
+
+int check_gn_partial(const char* who, size_t have, long images, long rows_per_img, long n) {
+    const size_t need = (size_t)images * (size_t)cdiv(rows_per_img, 128) * (size_t)n * 3 * sizeof(float);
+    return have < need ? fail(E2EFT_ERR_WORKSPACE, "%s: gn_partial %zu < %zu bytes", who, have, need) : E2EFT_OK;
+}
+
+IgemmParams conv_params(const E2eftConvDesc* d) {
+    IgemmParams p = {};
+    const int cin = d->c1 + d->c2;
+    p.M = d->batch * d->hout * d->wout; p.N = d->cout; p.K = d->kh * d->kw * cin;
+    p.ldx1 = d->ldx1; p.ldx2 = d->ldx2; p.c1 = d->c1; p.cin = cin;
+    p.hin = d->hin; p.win = d->win; p.hl = d->hl; p.wl = d->wl;
+    p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+    p.hout = d->hout; p.wout = d->wout;
+    p.up_sh = (float)d->hin / (float)d->hl;
+    p.up_sw = (float)d->win / (float)d->wl;
+    p.ldw = d->ldw; p.ldr = d->ldr; p.ldo = d->ldo;
+    p.rows_per_img = d->hout * d->wout;
+    p.alpha = d->alpha;
+    p.nzi = 1;
+    return p;
+}
+
 static int run_igemm(int dtype, int mode, IgemmParams& p, int nz, void* stream) {
-    p.mtiles = cdiv(p.M, BM);
-    p.ntiles = cdiv(p.N, BN);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return fail(E2EFT_ERR_BAD_ARG, "igemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
-    if ((long)p.mtiles * p.ntiles > 2000000000L) return fail(E2EFT_ERR_BAD_ARG, "igemm: grid too large");
+    if ((long)cdiv(p.M, BM) * cdiv(p.N, BN) > 2000000000L) return fail(E2EFT_ERR_BAD_ARG, "igemm: grid too large");
     if (nz > 65535) return fail(E2EFT_ERR_BAD_ARG, "igemm: batch %d > 65535", nz);
     hipStream_t s = (hipStream_t)stream;
     if (dtype < 0 || dtype > 2) return fail(E2EFT_ERR_BAD_ARG, "igemm: bad dtype %d", dtype);
     if (p.nrm_ad) {   // the fused-normalisation route exists on igemm6 only: the caller asked e2eft_conv2d_fwd_normed_supported first
-        const int rcn = launch_igemm_patch(dtype, mode, p, nz, s);
+        const int rcn = launch_persistent_family(dtype, mode, p, nz, s);
         return rcn >= 0 ? rcn : fail(E2EFT_ERR_UNSUPPORTED, "conv2d_fwd_normed: this launch is not eligible for the fused-normalisation kernel");
     }
     const int rc7 = launch_conv_thin_in(dtype, mode, p, nz, s);      // conv_in: eight input channels (convin.hip)
     if (rc7 >= 0) return rc7;
-    const int rc6 = launch_igemm_patch(dtype, mode, p, nz, s);        // big 16-bit 3x3 convolutions: halo patch in LDS (igemm6.hip)
-    if (rc6 >= 0) return rc6;
-    const int rc5 = launch_igemm_persistent(dtype, mode, p, nz, s);   // big 16-bit problems: persistent workgroups (igemm5.hip)
-    if (rc5 >= 0) return rc5;
+    const int rcp = launch_persistent_family(dtype, mode, p, nz, s);  // big 16-bit problems: igemm6.hip, else igemm5.hip
+    if (rcp >= 0) return rcp;
     return launch_igemm_v2(dtype, mode, p, nz, s);                    // everything else: igemm2.hip (256- or 128-row tiles)
 }
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int launch_conv3x3_narrow(const E2eftConvDesc* d, const void* x1, const void* w, const void* bias, void* out, void* stream, const float* nrm_ad = nullptr,
                           const void* nrm_beta = nullptr, int nrm_silu = 0);   // narrow.hip
@@ -125,7 +168,7 @@ extern "C" int e2eft_conv2d_fwd_splitk(const E2eftConvDesc* d, const void* x1, c
     const size_t need = e2eft_conv2d_splitk_workspace_bytes(d);
     E2EFT_REQUIRE(need > 0, "conv2d_splitk: this problem is not split (e2eft_conv2d_splitk_workspace_bytes == 0)");
     if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "conv2d_splitk: workspace %zu < %zu", ws_bytes, need);
-    E2EFT_REQUIRE(((uintptr_t)workspace & 15) == 0, "conv2d_splitk: workspace must be 16-byte aligned");
+    E2EFT_REQUIRE(al16(workspace), "conv2d_splitk: workspace must be 16-byte aligned");
     return conv2d_core(d, x1, x2, w, bias, rowadd, residual, out, nullptr, 0, nullptr, workspace, ws_bytes, stream);
 }
 
@@ -149,18 +192,7 @@ extern "C" int e2eft_conv2d_fwd_normed_supported(const E2eftConvDesc* d) {
     if (!d || d->c2 != 0 || d->dtype < 1 || d->dtype > 2 || !option(E2EFT_OPT_FUSED_NORM)) return 0;
     if (d->batch <= 0 || d->hin <= 0 || d->win <= 0 || d->cout <= 0 || d->c1 <= 0) return 0;
     if (conv3x3_narrow_eligible(d, true)) return 1;   // conv_norm_out -> conv_out
-    IgemmParams p = {};
-    void* const al = (void*)(uintptr_t)256;
-    p.x1 = al; p.w = al; p.out = al; p.nrm_ad = (const float*)al;
-    p.M = d->batch * d->hout * d->wout; p.N = d->cout; p.K = d->kh * d->kw * d->c1;
-    p.ldx1 = d->ldx1; p.c1 = d->c1; p.cin = d->c1;
-    p.hin = d->hin; p.win = d->win; p.hl = d->hl; p.wl = d->wl;
-    p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.hout = d->hout; p.wout = d->wout;
-    p.ldw = d->ldw; p.ldr = d->ldr > 0 ? d->ldr : d->ldo; p.ldo = d->ldo;
-    p.rows_per_img = d->hout * d->wout;
-    p.nzi = 1;
-    return igemm_patch_eligible(d->dtype, 1, p, 1) ? 1 : 0;
+    return persistent_family_eligible(d->dtype, 1, conv_params(d), 1, true) ? 1 : 0;
 }
 
 static int conv2d_core(const E2eftConvDesc* d, const void* x1, const void* x2, const void* w, const void* bias, const void* rowadd,
@@ -189,36 +221,21 @@ static int conv2d_core(const E2eftConvDesc* d, const void* x1, const void* x2, c
         if (rn >= 0) return rn;
     }
 
-    IgemmParams p = {};
+    IgemmParams p = conv_params(d);
     p.x1 = x1; p.x2 = x2; p.w = w; p.bias = bias; p.rowadd = rowadd; p.residual = residual; p.out = out;
-    p.M = d->batch * d->hout * d->wout;
-    p.N = d->cout;
-    p.K = d->kh * d->kw * cin;
-    p.ldx1 = d->ldx1; p.ldx2 = d->ldx2; p.c1 = d->c1; p.cin = cin;
-    p.hin = d->hin; p.win = d->win; p.hl = d->hl; p.wl = d->wl;
-    p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-    p.hout = d->hout; p.wout = d->wout;
-    p.up_sh = (float)d->hin / (float)d->hl;
-    p.up_sw = (float)d->win / (float)d->wl;
-    p.ldw = d->ldw; p.ldr = d->ldr; p.ldo = d->ldo;
-    p.bias_along_m = 0;
-    p.rows_per_img = d->hout * d->wout;
-    p.alpha = d->alpha;
-    p.nzi = 1;
     if (norm) { p.nrm_ad = norm->ad; p.nrm_beta = norm->beta; p.nrm_silu = norm->silu; }
     const bool plain = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->c2 == 0 &&
                        d->hl == d->hin && d->wl == d->win && d->hout == d->hin && d->wout == d->win;
     if (gn_partial && slab_rows) {
-        const size_t need = (size_t)d->batch * (size_t)cdiv(p.rows_per_img, 128) * (size_t)d->cout * 3 * sizeof(float);
-        if (gn_partial_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "conv2d: gn_partial %zu < %zu bytes", gn_partial_bytes, need);
+        if (const int rcw = check_gn_partial("conv2d", gn_partial_bytes, d->batch, p.rows_per_img, d->cout)) return rcw;
         p.gn_partial = gn_partial;
     }
     if (workspace) {   // split-K over rows of filter taps: partial sums in the workspace, then one finish pass with the whole epilogue
         const int ns = conv_splitk_plan(d);
         const int epc2 = 16 / (int)dtype_size(d->dtype);
         E2EFT_REQUIRE(ns > 0 && !plain, "conv2d_splitk: not a split problem");
-        E2EFT_REQUIRE(d->ldo % epc2 == 0 && ((uintptr_t)out & 15) == 0 && (!residual || (d->ldr % epc2 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-                          (!bias || ((uintptr_t)bias & 15) == 0) && (!rowadd || ((uintptr_t)rowadd & 15) == 0), "conv2d_splitk: vector alignment");
+        E2EFT_REQUIRE(d->ldo % epc2 == 0 && al16(out) && (!residual || (d->ldr % epc2 == 0 && al16(residual))) && (!bias || al16(bias)) && (!rowadd || al16(rowadd)),
+                      "conv2d_splitk: vector alignment");
         IgemmParams q = p;
         q.bias = nullptr; q.rowadd = nullptr; q.residual = nullptr; q.gn_partial = nullptr;
         q.out = workspace; q.ldo = d->cout; q.alpha = 1.f;
@@ -247,34 +264,74 @@ static int conv2d_core(const E2eftConvDesc* d, const void* x1, const void* x2, c
 // rows, the 3x3 taps that fall on the same source pixel can be added up front.  Per parity phase (py, px) the layer is a 2x2 convolution (pad_t = 1 - py, pad_l = 1 - px)
 // with weights w_phase[2 py + px][co][(i, j, ci)] = sum of the 3x3 taps that map to source offset (i, j) — 4/9 of the multiply-adds of the fused-upsample form, same
 // zero padding (the upsampled image's border IS the source's border).  The phases write interleaved pixels of the full-resolution output: IgemmParams.out_seg.
-namespace e2eft { int device_cus(); }   // api.hip
 static bool upconv2x_shape_ok(const E2eftConvDesc* d) {     // the layer is a 2x-upsample + 3x3 / stride-1 / pad-1 convolution whose phases any igemm kernel can run
     if (!d || d->dtype < 0 || d->dtype > 2) return false;
     const int bk = 128 / (int)dtype_size(d->dtype);          // one k-tile of the FAST operand path
     return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->c2 == 0 && d->hl == 2 * d->hin && d->wl == 2 * d->win &&
            d->hout == d->hl && d->wout == d->wl && d->batch > 0 && d->hin > 0 && d->win > 0 && d->c1 > 0 && d->c1 % bk == 0 && d->cout % (bk / 8) == 0 &&
            d->ldo % (bk / 8) == 0 && d->alpha == 1.0f && (long)d->batch * d->hin * d->win < 2147483647L &&
-           (long)d->hin * d->win * d->ldx1 * (long)dtype_size(d->dtype) * 3 < 0xD0000000L && (long)128 * 4 * d->c1 * (long)dtype_size(d->dtype) < 0x40000000L;
+           (long)d->hin * d->win * d->ldx1 * (long)dtype_size(d->dtype) * 3 < SRD_SPAN_MAX && (long)128 * 4 * d->c1 * (long)dtype_size(d->dtype) < SRD_TILE_MAX;
 }
 // the persistent kernel takes the phases (and emits GroupNorm statistics): 16-bit, whole 256-row tiles inside one image, segments of a multiple of 16 rows, >= 2 tiles per CU
 static bool upconv2x_persistent(const E2eftConvDesc* d) {
     if (d->dtype == E2EFT_F32 || !option(E2EFT_OPT_PERSISTENT)) return false;
     if (d->c1 % 64 != 0 || d->win % 16 != 0 || ((long)d->batch * d->hin * d->win) % 256 != 0 || ((long)d->hin * d->win) % 256 != 0) return false;
-    int cus = device_cus();
-    const int gopt = option(E2EFT_OPT_PERSISTENT_GRID);
-    if (gopt >= 8 && gopt < cus) cus = gopt;
-    if (cus <= 0) return false;
-    return ((long)d->batch * d->hin * d->win / 256) * cdiv(d->cout, 128) >= 2L * cus;
+    const int cus = persistent_grid();
+    return cus > 0 && ((long)d->batch * d->hin * d->win / 256) * cdiv(d->cout, 128) >= 2L * cus;
 }
+
+namespace e2eft {
+
+IgemmParams upconv2x_phase_params(const E2eftConvDesc* d, int ph, int split) {
+    const int py = ph >> 1, px = ph & 1, cs = split * d->c1;   // cs: channels of one tap in K
+    IgemmParams p = {};
+    p.M = d->batch * d->hin * d->win; p.N = d->cout; p.K = 4 * cs;
+    p.ldx1 = d->ldx1; p.c1 = cs; p.cin = cs; p.split_c = split > 1 ? d->c1 : 0;
+    p.hin = d->hin; p.win = d->win; p.hl = d->hin; p.wl = d->win;
+    p.kh = 2; p.kw = 2; p.stride = 1; p.pad_t = 1 - py; p.pad_l = 1 - px;
+    p.hout = d->hin; p.wout = d->win;
+    p.up_sh = p.up_sw = 1.f;
+    p.ldw = 4 * cs; p.ldo = 2 * d->ldo; p.ldr = p.ldo;
+    p.out_seg = d->win;
+    p.rows_per_img = d->hin * d->win;          // GEMM rows of one image in ONE phase
+    p.alpha = 1.f;
+    p.nzi = 1;
+    return p;
+}
+
+int run_upconv2x_phases(const E2eftConvDesc* d, int dtype, int split, const IgemmParams& io, bool persistent, int32_t* slab_rows, const char* who, hipStream_t s) {
+    const size_t es = dtype_size(dtype), eso = split > 1 ? sizeof(float) : es;      // operand / output element
+    const int slabs = d->hin * d->win / 256;
+    for (int ph = 0; ph < 4; ++ph) {                          // all four phases take the same kernel: the statistics slabs must agree
+        IgemmParams p = upconv2x_phase_params(d, ph, split);
+        p.x1 = io.x1; p.w = (const char*)io.w + (size_t)ph * d->cout * p.ldw * es; p.bias = io.bias;
+        p.out = (char*)io.out + ((size_t)(ph >> 1) * d->wl + (ph & 1)) * d->ldo * eso;
+        p.alpha_dev = io.alpha_dev; p.alpha_dev2 = io.alpha_dev2;
+        if (io.gn_partial) {   // the four phases deposit into disjoint slab ranges of one [image][4 * slabs][cout][3] buffer
+            p.gn_partial = io.gn_partial + (size_t)ph * slabs * d->cout * 3;
+            p.gn_islabs = 4 * slabs;
+        }
+        int rc;
+        if (persistent) {      // round 6: the 2x2-tap halo-patch kernel where the grid allows (8 x 32-pixel tiles; same 256-row statistics slabs), else igemm5
+            rc = launch_persistent_family(dtype, 1, p, 1, s);
+            if (rc < 0) return fail(E2EFT_ERR_UNSUPPORTED, "%s: the persistent %s declined phase %d", who, split > 1 ? "kernels" : "kernel", ph);
+        } else {
+            rc = launch_igemm_v2(dtype, 1, p, 1, s);
+        }
+        if (rc) return rc;
+    }
+    if (io.gn_partial) *slab_rows = 256;
+    return E2EFT_OK;
+}
+
+}  // namespace e2eft
 
 extern "C" int e2eft_upconv2x_fwd_supported(const E2eftConvDesc* d) {
     if (!upconv2x_shape_ok(d) || !option(E2EFT_OPT_UPCONV_PHASES)) return 0;
     if (upconv2x_persistent(d)) return 1;
     // igemm2 runs the phases as four plain launches: that only beats ONE fused-upsample launch (on igemm6 / igemm5 for 16-bit) when every phase fills the machine —
     // at 12^2 -> 24^2 with 8 images a phase is 90 workgroups and four of them cost 0.34 ms against 0.14 ms (r05c); same bar as the persistent kernel: two tiles per CU
-    int cus = device_cus();
-    const int gopt = option(E2EFT_OPT_PERSISTENT_GRID);
-    if (gopt >= 8 && gopt < cus) cus = gopt;
+    const int cus = persistent_grid();
     return cus > 0 && cdiv((long)d->batch * d->hin * d->win, 256) * cdiv(d->cout, 128) >= 2L * cus ? 1 : 0;
 }
 
@@ -284,48 +341,14 @@ extern "C" int e2eft_upconv2x_fwd(const E2eftConvDesc* d, const void* x, const v
     E2EFT_REQUIRE(d && x && w_phase && out, "upconv2x: null pointer");
     if (!e2eft_upconv2x_fwd_supported(d)) return fail(E2EFT_ERR_UNSUPPORTED, "upconv2x: this launch is not eligible (ask e2eft_upconv2x_fwd_supported; e2eft_conv2d_fwd serves it)");
     E2EFT_REQUIRE(al16(x) && al16(w_phase) && al16(out) && (!bias || al16(bias)), "upconv2x: pointers must be 16-byte aligned");
-    const bool pers = upconv2x_persistent(d);                // all four phases take the same kernel: the statistics slabs must agree
-    const int rows_img = d->hin * d->win;                    // GEMM rows of one image in ONE phase
-    const int slabs = rows_img / 256;
-    const bool stats = pers && gn_partial && slab_rows;      // (igemm2 serves the phases without statistics: the consuming GroupNorm runs its own pass)
-    if (stats) {
-        const size_t need = (size_t)d->batch * (size_t)cdiv(4 * rows_img, 128) * (size_t)d->cout * 3 * sizeof(float);
-        if (gn_partial_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "upconv2x: gn_partial %zu < %zu bytes", gn_partial_bytes, need);
+    const bool pers = upconv2x_persistent(d);
+    IgemmParams io = {};
+    io.x1 = x; io.w = w_phase; io.bias = bias; io.out = out;
+    if (pers && gn_partial && slab_rows) {                   // (igemm2 serves the phases without statistics: the consuming GroupNorm runs its own pass)
+        if (const int rcw = check_gn_partial("upconv2x", gn_partial_bytes, d->batch, 4L * d->hin * d->win, d->cout)) return rcw;
+        io.gn_partial = gn_partial;
     }
-    const size_t es = dtype_size(d->dtype);
-    for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        IgemmParams p = {};
-        p.x1 = x; p.w = (const char*)w_phase + (size_t)ph * d->cout * 4 * d->c1 * es; p.bias = bias;
-        p.out = (char*)out + ((size_t)py * d->wl + px) * d->ldo * es;
-        p.M = d->batch * rows_img; p.N = d->cout; p.K = 4 * d->c1;
-        p.ldx1 = d->ldx1; p.c1 = d->c1; p.cin = d->c1;
-        p.hin = d->hin; p.win = d->win; p.hl = d->hin; p.wl = d->win;
-        p.kh = 2; p.kw = 2; p.stride = 1; p.pad_t = 1 - py; p.pad_l = 1 - px;
-        p.hout = d->hin; p.wout = d->win;
-        p.up_sh = p.up_sw = 1.f;
-        p.ldw = 4 * d->c1; p.ldo = 2 * d->ldo;
-        p.out_seg = d->win;
-        p.rows_per_img = rows_img;
-        p.alpha = 1.f;
-        p.nzi = 1;
-        if (stats) {       // the four phases deposit into disjoint slab ranges of one [image][4 * slabs][cout][3] buffer
-            p.gn_partial = gn_partial + (size_t)ph * slabs * d->cout * 3;
-            p.gn_islabs = 4 * slabs;
-        }
-        int rc;
-        if (pers) {
-            p.mtiles = p.M / 256; p.ntiles = cdiv(p.N, 128);
-            rc = launch_igemm_patch(d->dtype, 1, p, 1, (hipStream_t)stream);      // round 6: 2x2-tap halo-patch kernel (8 x 32-pixel tiles; same 256-row statistics slabs)
-            if (rc < 0) rc = launch_igemm_persistent(d->dtype, 1, p, 1, (hipStream_t)stream);
-            if (rc < 0) return fail(E2EFT_ERR_UNSUPPORTED, "upconv2x: the persistent kernel declined phase %d", ph);
-        } else {
-            rc = launch_igemm_v2(d->dtype, 1, p, 1, (hipStream_t)stream);
-        }
-        if (rc) return rc;
-    }
-    if (stats) *slab_rows = 256;
-    return E2EFT_OK;
+    return run_upconv2x_phases(d, d->dtype, 1, io, pers, slab_rows, "upconv2x", (hipStream_t)stream);
 }
 
 
@@ -399,8 +422,7 @@ extern "C" int e2eft_gemm_gnstats(const E2eftGemmDesc* d, const void* a, const v
     p.sa_o = d->sa_o; p.sa_i = d->sa_i; p.sw_o = d->sw_o; p.sw_i = d->sw_i;
     p.so_o = d->so_o; p.so_i = d->so_i; p.sr_o = d->sr_o; p.sr_i = d->sr_i;
     if (gn_partial && slab_rows && rows_per_image > 0 && d->nzo * d->nzi == 1 && !d->bias_along_m && d->m % rows_per_image == 0) {
-        const size_t need = (size_t)(d->m / rows_per_image) * (size_t)cdiv(rows_per_image, 128) * (size_t)d->n * 3 * sizeof(float);
-        if (gn_partial_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "gemm: gn_partial %zu < %zu bytes", gn_partial_bytes, need);
+        if (const int rcw = check_gn_partial("gemm", gn_partial_bytes, d->m / rows_per_image, rows_per_image, d->n)) return rcw;
         p.gn_partial = gn_partial;
         p.rows_per_img = rows_per_image;
     }

@@ -438,21 +438,14 @@ template <typename T, int MODE, int NW> static int launch2(IgemmParams& p, int n
     p.ntiles = cdiv(p.N, BN2);
     if (p.gn_partial) {   // statistics need whole tiles inside one image and the vector epilogue
         const bool ok = nz == 1 && p.rows_per_img % Geo<NW>::BM == 0 && p.M % p.rows_per_img == 0 && p.N % 8 == 0 &&
-                        p.ldo % (16 / (int)sizeof(T)) == 0 && (((uintptr_t)p.out) & 15) == 0 &&
-                        (!p.residual || (p.ldr % (16 / (int)sizeof(T)) == 0 && (((uintptr_t)p.residual) & 15) == 0));
+                        p.ldo % (16 / (int)sizeof(T)) == 0 && al16(p.out) &&
+                        (!p.residual || (p.ldr % (16 / (int)sizeof(T)) == 0 && al16(p.residual)));
         if (ok) p.gn_nslabs = p.rows_per_img / Geo<NW>::BM;
         else p.gn_partial = nullptr;
     }
     dim3 grid(p.mtiles * p.ntiles, nz, 1);
     constexpr int BK = 128 / (int)sizeof(T);
-    bool fast;
-    if (MODE == 0) {
-        fast = p.K % BK == 0 && (long)256 * p.ldx1 * (long)sizeof(T) < 0x40000000L && (long)128 * p.ldw * (long)sizeof(T) < 0x40000000L;
-    } else {
-        const long img_bytes = (long)p.hin * p.win * (p.ldx1 > p.ldx2 ? p.ldx1 : p.ldx2) * (long)sizeof(T);
-        const long span_imgs = 256 / ((long)p.hout * p.wout) + 2;
-        fast = p.cin % BK == 0 && p.c1 % BK == 0 && img_bytes * span_imgs < 0xD0000000L && (long)128 * p.ldw * (long)sizeof(T) < 0x40000000L;
-    }
+    const bool fast = (MODE == 0 ? p.K % BK == 0 : p.cin % BK == 0 && p.c1 % BK == 0) && fast_operands_in_range(MODE, p, (long)sizeof(T));
     const bool nofast = option(E2EFT_OPT_IGEMM_GENERAL_OPERANDS) != 0;
     if (p.ksplit_taps > 0 && !(fast && !nofast && MODE == 1)) return fail(E2EFT_ERR_BAD_ARG, "igemm2: split-K needs the FAST conv path");
     if (fast && !nofast) hipLaunchKernelGGL((igemm2_kernel<T, MODE, true, NW>), grid, dim3(NW * 64), 0, s, p);

@@ -26,7 +26,7 @@
 //     layout (a lane owns two columns), values rounded there, two rows per dword through LDS — half the staging bytes, readers only store.
 // Contract, operand layouts, ring, swizzle: as igemm2.hip.  Eligibility is decided on the host (launch_igemm_persistent returns -1 and the
 // caller falls through to igemm2): 16-bit FAST path, M a multiple of 256, at least three k-tiles, the vector epilogue, at least two tiles
-// per workgroup.  e2eft_set_option(E2EFT_OPT_PERSISTENT, 0) disables the variant (A/B runs), E2EFT_OPT_PERSISTENT_GRID shrinks the grid (tests).
+// per workgroup.  e2eft_set_option(E2EFT_OPT_PERSISTENT, 0) disables the variant (A/B runs), the grid option behind persistent_grid() shrinks the grid (tests).
 //
 // GroupNorm statistics (p.gn_partial): per column shifted sums about a per-wave pivot (the wave's first output row), a 14-exchange
 // reduce-scatter over the eight row-lanes of a chunk, per-wave deposits in LDS merged over the four row-waves of a column with Chan's
@@ -477,7 +477,6 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
 
 static std::atomic<long> g_pers_launches{0};      // debug counter (tests assert that the variant under test really ran)
 
-int device_cus();   // api.hip: CU count of the current device
 #ifdef E2EFT_STAMPS
 extern int g_debug_flags5;
 #endif
@@ -496,64 +495,38 @@ template <typename T, int MODE> static int launch5(IgemmParams& p, int nz, int t
     return check_launch("igemm5");
 }
 
-// the checks and the tile plan of launch_igemm_persistent (fills p.mtiles / p.ntiles / p.gn_nslabs): 0, or -1 = not this kernel's launch
-static int persistent_plan(int dtype, int mode, IgemmParams& p, int nz, long& total_out, int& cus_out) {
+// the checks and the tile plan of launch_igemm_persistent: pure host arithmetic (csrc/f32split.hip asks before it splits anything)
+bool igemm_persistent_eligible(int dtype, int mode, const IgemmParams& p, int nz, TilePlan& t) {
     using namespace pers;
-    if (!option(E2EFT_OPT_PERSISTENT)) return -1;
-    if (dtype != E2EFT_F16 && dtype != E2EFT_BF16) return -1;
-    if (p.ksplit_taps > 0 || p.bias_along_m) return -1;
+    if (!option(E2EFT_OPT_PERSISTENT)) return false;
+    if (dtype != E2EFT_F16 && dtype != E2EFT_BF16) return false;
+    if (p.ksplit_taps > 0 || p.bias_along_m) return false;
     if (p.split_c > 0 && (dtype != E2EFT_F16 || nz != 1 || p.x2 || p.rowadd || p.split_c % 64 != 0 || p.cin != 3 * p.split_c || p.c1 != p.cin ||
-                          (mode == 0 && p.K != 3 * p.split_c))) return -1;
+                          (mode == 0 && p.K != 3 * p.split_c))) return false;
     // whole 256-row tiles — except the fp32-split launches (F32O): their row table / A offsets zero the rows beyond M and epilogue_f32 masks them (the 18^2 UNet level
     // of the 576^2 recipe is 20.25 tiles per launch)
-    if ((p.M % BM != 0 && !(p.split_c > 0 && p.out_seg == 0 && p.M > BM)) || p.K % 64 != 0 || p.K / 64 < 3) return -1;
-    if (p.N % 8 != 0 || p.ldo % 8 != 0 || (((uintptr_t)p.out) & 15) != 0) return -1;
-    if (p.residual && (p.ldr % 8 != 0 || (((uintptr_t)p.residual) & 15) != 0)) return -1;
-    if (p.bias && (((uintptr_t)p.bias) & 15) != 0) return -1;
-    if (p.rowadd && ((((uintptr_t)p.rowadd) & 15) != 0 || (p.rows_per_img % BM != 0 && p.rows_per_img < p.M))) return -1;
-    if (nz > 1 && (p.so_o % 8 != 0 || p.so_i % 8 != 0 || p.sr_o % 8 != 0 || p.sr_i % 8 != 0)) return -1;
-    if (p.out_seg != 0 && (p.out_seg < 16 || p.out_seg % 16 != 0 || nz != 1 || p.residual || p.M % p.out_seg != 0)) return -1;
-    if (mode == 0) {
-        if ((long)256 * p.ldx1 * 2 >= 0x40000000L || (long)128 * p.ldw * 2 >= 0x40000000L) return -1;
-    } else {
-        const long img_bytes = (long)p.hin * p.win * (p.ldx1 > p.ldx2 ? p.ldx1 : p.ldx2) * 2;
-        const long span_imgs = 256 / ((long)p.hout * p.wout) + 2;
-        if (p.cin % 64 != 0 || p.c1 % 64 != 0 || img_bytes * span_imgs >= 0xD0000000L || (long)128 * p.ldw * 2 >= 0x40000000L) return -1;
-    }
-    int g_pers_cus = device_cus();     // CUs of the CURRENT device (the one the caller's stream belongs to)
-    if (g_pers_cus == 0) return -1;
-    const int gopt = option(E2EFT_OPT_PERSISTENT_GRID);   // tests: a small grid sends small problems through the persistent kernel
-    if (gopt >= 8 && gopt < g_pers_cus) g_pers_cus = gopt;
-    const int mtiles = cdiv(p.M, BM), ntiles = cdiv(p.N, BN);
-    const long total = (long)mtiles * ntiles * nz;
-    if (4 * total < (long)option(E2EFT_OPT_PERSISTENT_MIN_QROUNDS) * g_pers_cus || total > 2000000000L || mtiles >= (1 << 22)) return -1;   // (tile / row splits use a float reciprocal: quotients below 2^22)
-    p.mtiles = mtiles;
-    p.ntiles = ntiles;
-    if (p.gn_partial) {   // statistics need whole tiles inside one image; otherwise igemm2 may still be able to emit them (128-row slabs): fall through
-        if (!(nz == 1 && p.rows_per_img % BM == 0 && p.M % p.rows_per_img == 0)) return -1;
-        p.gn_nslabs = p.rows_per_img / BM;
-    }
-    total_out = total;
-    cus_out = g_pers_cus;
-    return 0;
-}
-
-bool igemm_persistent_eligible(int dtype, int mode, IgemmParams& p, int nz) {   // pure host arithmetic (csrc/f32split.hip asks before it splits anything)
-    long total;
-    int cus;
-    return persistent_plan(dtype, mode, p, nz, total, cus) == 0;
+    if ((p.M % BM != 0 && !(p.split_c > 0 && p.out_seg == 0 && p.M > BM)) || p.K % 64 != 0 || p.K / 64 < 3) return false;
+    if (!vec_epilogue_ok(p)) return false;
+    if (p.rowadd && (!al16(p.rowadd) || (p.rows_per_img % BM != 0 && p.rows_per_img < p.M))) return false;
+    if (nz > 1 && (p.so_o % 8 != 0 || p.so_i % 8 != 0 || p.sr_o % 8 != 0 || p.sr_i % 8 != 0)) return false;
+    if (p.out_seg != 0 && (p.out_seg < 16 || p.out_seg % 16 != 0 || nz != 1 || p.residual || p.M % p.out_seg != 0)) return false;
+    if ((mode != 0 && (p.cin % 64 != 0 || p.c1 % 64 != 0)) || !fast_operands_in_range(mode, p, 2)) return false;
+    const int cus = persistent_grid();
+    if (!plan_tiles(p, nz, BM, BN, cus, (long)option(E2EFT_OPT_PERSISTENT_MIN_QROUNDS) * cus, t)) return false;
+    // statistics need whole tiles inside one image; otherwise igemm2 may still be able to emit them (128-row slabs): fall through
+    return !p.gn_partial || (nz == 1 && p.rows_per_img % BM == 0 && p.M % p.rows_per_img == 0);
 }
 
 int launch_igemm_persistent(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s) {
-    long total;
-    int g_pers_cus;
-    if (persistent_plan(dtype, mode, p, nz, total, g_pers_cus) != 0) return -1;
+    TilePlan t;
+    if (!igemm_persistent_eligible(dtype, mode, p, nz, t)) return -1;
+    apply_plan(p, t);
     g_pers_launches.fetch_add(1, std::memory_order_relaxed);
 #ifdef E2EFT_STAMPS
     p.debug_flags = g_debug_flags5;
 #endif
-    if (dtype == E2EFT_F16) return mode ? launch5<f16, 1>(p, nz, (int)total, g_pers_cus, s) : launch5<f16, 0>(p, nz, (int)total, g_pers_cus, s);
-    return mode ? launch5<bf16, 1>(p, nz, (int)total, g_pers_cus, s) : launch5<bf16, 0>(p, nz, (int)total, g_pers_cus, s);
+    if (dtype == E2EFT_F16) return mode ? launch5<f16, 1>(p, nz, (int)t.total, t.grid, s) : launch5<f16, 0>(p, nz, (int)t.total, t.grid, s);
+    return mode ? launch5<bf16, 1>(p, nz, (int)t.total, t.grid, s) : launch5<bf16, 0>(p, nz, (int)t.total, t.grid, s);
 }
 
 }  // namespace e2eft

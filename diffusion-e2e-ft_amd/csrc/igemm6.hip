@@ -484,8 +484,6 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
 
 static std::atomic<long> g_patch_launches{0};
 
-int device_cus();   // api.hip
-
 template <typename T> static int launch6(IgemmParams& p, int total, int grid, hipStream_t s) {
     if constexpr (std::is_same<T, f16>::value) {
         if (p.split_c > 0) {   // an fp32 convolution from f16 split planes (patch_eligible): 3x3, or a 2x2 parity phase of an upsampler convolution
@@ -511,7 +509,7 @@ template <typename T> static int launch6(IgemmParams& p, int total, int grid, hi
     return check_launch("igemm6");
 }
 
-static bool patch_eligible(int dtype, int mode, IgemmParams& p, int nz, int& grid_out, long& total_out) {
+bool igemm_patch_eligible(int dtype, int mode, const IgemmParams& p, int nz, TilePlan& t) {   // pure host arithmetic
     using namespace patchk;
     if (!option(E2EFT_OPT_PATCH_CONV) || !option(E2EFT_OPT_PERSISTENT)) return false;
     if (mode != 1 || nz != 1 || (dtype != E2EFT_F16 && dtype != E2EFT_BF16)) return false;
@@ -529,45 +527,24 @@ static bool patch_eligible(int dtype, int mode, IgemmParams& p, int nz, int& gri
     if (p.wl % TW != 0 || p.hl % TH != 0) return false;
     if (p.cin % 64 != 0 || p.c1 % 64 != 0 || p.cin < 128 || p.K != p.kh * p.kw * p.cin) return false;
     if (p.nrm_ad && (p.x2 || p.cin > NORM_CMAX || p.N > BN || !option(E2EFT_OPT_FUSED_NORM))) return false;   // one N tile: every N tile would redo the normalisation
-    if (p.N % 8 != 0 || p.ldo % 8 != 0 || (((uintptr_t)p.out) & 15) != 0) return false;
-    if (p.ldx1 % 8 != 0 || (((uintptr_t)p.x1) & 15) != 0 || (p.x2 && (p.ldx2 % 8 != 0 || (((uintptr_t)p.x2) & 15) != 0))) return false;
-    if (p.ldw % 8 != 0 || (((uintptr_t)p.w) & 15) != 0) return false;
-    if (p.residual && (p.ldr % 8 != 0 || (((uintptr_t)p.residual) & 15) != 0)) return false;
-    if (p.bias && (((uintptr_t)p.bias) & 15) != 0) return false;
-    if (p.rowadd && ((((uintptr_t)p.rowadd) & 15) != 0 || p.rows_per_img != p.hl * p.wl)) return false;
+    if (!vec_epilogue_ok(p)) return false;
+    if (p.ldx1 % 8 != 0 || !al16(p.x1) || (p.x2 && (p.ldx2 % 8 != 0 || !al16(p.x2)))) return false;
+    if (p.ldw % 8 != 0 || !al16(p.w)) return false;
+    if (p.rowadd && (!al16(p.rowadd) || p.rows_per_img != p.hl * p.wl)) return false;
     const long img_bytes = (long)p.hin * p.win * (p.ldx1 > p.ldx2 ? p.ldx1 : p.ldx2) * 2;
-    if (img_bytes >= 0xD0000000L || (long)128 * p.ldw * 2 >= 0x40000000L) return false;
+    if (img_bytes >= SRD_SPAN_MAX || (long)128 * p.ldw * 2 >= SRD_TILE_MAX) return false;
     if (p.M % (p.hl * p.wl) != 0) return false;
-    int cus = device_cus();
-    if (cus == 0) return false;
-    const int gopt = option(E2EFT_OPT_PERSISTENT_GRID);
-    if (gopt >= 8 && gopt < cus) cus = gopt;
-    const int mtiles = p.M / BM, ntiles = cdiv(p.N, BN);
-    const long total = (long)mtiles * ntiles;
-    if (4 * total < (long)option(E2EFT_OPT_PERSISTENT_MIN_QROUNDS) * cus || total > 2000000000L || mtiles >= (1 << 22)) return false;
-    if (p.gn_partial) {
-        if (p.rows_per_img != p.hl * p.wl) return false;
-        p.gn_nslabs = p.rows_per_img / BM;
-    }
-    p.mtiles = mtiles;
-    p.ntiles = ntiles;
-    grid_out = cus;
-    total_out = total;
-    return true;
-}
-
-bool igemm_patch_eligible(int dtype, int mode, IgemmParams& p, int nz) {
-    int grid;
-    long total;
-    return patch_eligible(dtype, mode, p, nz, grid, total);
+    const int cus = persistent_grid();
+    if (!plan_tiles(p, 1, BM, BN, cus, (long)option(E2EFT_OPT_PERSISTENT_MIN_QROUNDS) * cus, t)) return false;
+    return !p.gn_partial || p.rows_per_img == p.hl * p.wl;
 }
 
 int launch_igemm_patch(int dtype, int mode, IgemmParams& p, int nz, hipStream_t s) {
-    int grid;
-    long total;
-    if (!patch_eligible(dtype, mode, p, nz, grid, total)) return -1;
+    TilePlan t;
+    if (!igemm_patch_eligible(dtype, mode, p, nz, t)) return -1;
+    apply_plan(p, t);
     g_patch_launches.fetch_add(1, std::memory_order_relaxed);
-    return dtype == E2EFT_F16 ? launch6<f16>(p, (int)total, grid, s) : launch6<bf16>(p, (int)total, grid, s);
+    return dtype == E2EFT_F16 ? launch6<f16>(p, (int)t.total, t.grid, s) : launch6<bf16>(p, (int)t.total, t.grid, s);
 }
 
 }  // namespace e2eft

@@ -355,8 +355,6 @@ __global__ __launch_bounds__(512) void wgrad32_kernel(const WgradParams p) {
     }
 }
 
-int device_cus();   // api.hip
-
 // pixel split: one workgroup per CU and round.  Among the split counts that leave >= 8 k-tiles per workgroup the one with the best product of
 // (filled fraction of the last round) x (k-tiles / (k-tiles + 3): the pipeline fill of a workgroup) — e.g. conv 320 -> 320 3x3 at 32 x 72^2:
 // 36 tiles x 7 splits = 252 workgroups = 0.98 rounds, not 36 x 22 = 3.09.
