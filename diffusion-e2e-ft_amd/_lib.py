@@ -54,6 +54,15 @@ class D2ntDesc(C.Structure):
 D2NT_F32, D2NT_U16, D2NT_U8 = range(3)      # e2eft_d2nt_desc.out_format
 
 
+class HypersimDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "color_dtype", "distance_dtype", "depth_format")] + [
+        ("focal", C.c_double), ("scale_numerator", C.c_double)]
+
+
+HYPERSIM_DEPTH_U16, HYPERSIM_DEPTH_F32 = range(2)      # e2eft_hypersim_desc.depth_format
+HYPERSIM_RECORD = 16                                    # E2EFT_HYPERSIM_RECORD
+
+
 # e2eft_set_option keys (include/e2eft.h)
 OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT = range(15)
 
@@ -160,6 +169,8 @@ SIGNATURES = {
     "e2eft_normal_eval_update": (_I, [C.POINTER(NormalEvalDesc), _P, _P, _P, _P, _L, _L, _P, _P, _Z, _P]),
     "e2eft_normal_eval_finalize": (_I, [_P, _L, _P, _P, _P, _Z, _P]),
     "e2eft_depth_to_normals": (_I, [C.POINTER(D2ntDesc), _P, _P, _P, _P]),
+    "e2eft_hypersim_preprocess_workspace_bytes": (_Z, [C.POINTER(HypersimDesc)]),
+    "e2eft_hypersim_preprocess": (_I, [C.POINTER(HypersimDesc), _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_workspace_bytes": (_Z, [_I]),
     "e2eft_ensemble_minmax": (_I, [_I, _L, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_gram": (_I, [_I, _L, _P, _P, _P, _P, _Z, _P]),

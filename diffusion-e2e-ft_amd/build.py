@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libe2eft.so")
-SOURCES = ["api.hip", "igemm.hip", "igemm2.hip", "igemm5.hip", "igemm6.hip", "convin.hip", "norm.hip", "attn.hip", "attn32.hip", "attn512.hip", "attn_bwd.hip", "elementwise.hip", "loss.hip", "bwd.hip", "wgrad.hip", "ensemble.hip", "dataprep.hip", "narrow.hip", "dataaug.hip", "evalmetrics.hip", "normaleval.hip", "d2nt.hip", "prepost.hip", "f32split.hip"]
+SOURCES = ["api.hip", "igemm.hip", "igemm2.hip", "igemm5.hip", "igemm6.hip", "convin.hip", "norm.hip", "attn.hip", "attn32.hip", "attn512.hip", "attn_bwd.hip", "elementwise.hip", "loss.hip", "bwd.hip", "wgrad.hip", "ensemble.hip", "dataprep.hip", "narrow.hip", "dataaug.hip", "evalmetrics.hip", "normaleval.hip", "d2nt.hip", "hypersimprep.hip", "prepost.hip", "f32split.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]   # exports = what include/*.h declares
 # Per-file flags.  The implicit-GEMM files are built without the SLP vectorizer: it turns the epilogue's per-column fp32
 # arithmetic into v_pk_add_f32 with operand swizzles (op_sel:[0,1] — the low result lane reads the HIGH dword of src1), and on
@@ -25,7 +25,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # attn.hip / attn512.hip: packed fp32 adds beside MFMAs cost more than the scalar ones they replace (the kernel is one wave per SIMD, every issue slot counts)
 EXTRA_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "attn32.hip": ["-fno-slp-vectorize"], "attn512.hip": ["-fno-slp-vectorize"], "igemm.hip": ["-fno-slp-vectorize"], "igemm2.hip": ["-fno-slp-vectorize"], "igemm5.hip": ["-fno-slp-vectorize"], "igemm6.hip": ["-fno-slp-vectorize"], "f32split.hip": ["-fno-slp-vectorize"], "convin.hip": ["-fno-slp-vectorize"],
                # the depth-to-normal translator restates numpy's fp32 / fp64 roundings step by step: no FMA may fuse a product it rounds
-               "d2nt.hip": ["-ffp-contract=off"]}
+               "d2nt.hip": ["-ffp-contract=off"],
+               # the Hypersim tone map / planar depth restates numpy's fp64 (and fp32 norm) roundings the same way
+               "hypersimprep.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -18,6 +18,10 @@
   depth_to_normals_vkitti   the D2NT "v3" translator the fine-tuning authors ran offline to make Virtual KITTI 2's normals (depth-to-normal-translator/
                     python/gen_vkitti_normals.py), on the device: `VirtualKITTI2(..., normals="d2nt")` synthesises them per batch instead of reading
                     vkitti_DAG_normals/; `write_png16` writes the reference's file format (scripts/gen_vkitti_normals.py).
+  hypersim_from_raw   the offline step that makes Hypersim's processed/ tree (Marigold/script/dataset_preprocess/hypersim/preprocess_hypersim.py: tone
+                    map to the 90th brightness percentile, distance -> planar depth, uint8 / uint16 millimetres) on the device: `Hypersim(...,
+                    source="raw")` reads the dataset as released (HDF5 colour, distance, render ids) and DeviceLoader runs it per batch;
+                    scripts/preprocess_hypersim.py writes the tree where the reference's file workflow is wanted.
 File decoding itself is a callable (`decoder=`): the default uses Pillow when it is importable (every file of both datasets is a PNG / JPEG it reads,
 16-bit depth included — the reference's cv2.imread of the KITTI depth returns the same integers); the package does not import an image library otherwise."""
 import csv
@@ -207,6 +211,25 @@ def pil_decoder(path, kind):
         return np.array(im.convert("RGB"))
 
 
+def read_hdf5(path):
+    """the one array ("dataset") of a Hypersim HDF5 file, as stored.  h5py is imported here, on first use: nothing else in the package needs it"""
+    try:
+        import h5py
+    except ImportError as e:
+        raise ImportError("reading raw Hypersim frames (%s) needs the h5py package, which is not installed: install h5py, pass decoder= to "
+                          "Hypersim(source=\"raw\"), or train from a processed/ tree" % os.path.basename(path)) from e
+    with h5py.File(path, "r") as f:
+        return np.array(f["dataset"])
+
+
+def raw_decoder(path, kind):
+    """default `decoder` of Hypersim(source="raw"): kind "color" / "distance" / "entity_id" -> the HDF5 array as stored (preprocess_hypersim.py:83-88),
+    "normal" -> uint8 [H,W,3] as pil_decoder"""
+    if kind in ("color", "distance", "entity_id"):
+        return read_hdf5(path)
+    return pil_decoder(path, kind)
+
+
 class _DecodedDataset:
     """base: `pairs` (file triplets), `decoder`, the per-dataset constants DeviceLoader needs"""
     name = None
@@ -223,18 +246,48 @@ class _DecodedDataset:
 class Hypersim(_DecodedDataset):
     """load.py:160-283.  root_dir / transform / near_plane / far_plane as the reference; `split_path` (the reference hard-codes the relative path below)
     and `decoder` are additions.  `__getitem__(i)` -> {"rgb_u8" uint8 [768,1024,3], "depth" fp32 [768,1024] metres, "normal_u8" uint8 [768,1024,3]}:
-    decoded, depth converted as the reference converts it (uint16 / 1000 in float64, stored as a float32 PIL image: load.py:220-222)."""
+    decoded, depth converted as the reference converts it (uint16 / 1000 in float64, stored as a float32 PIL image: load.py:220-222).
+    source="processed" (default): root_dir is the processed/ tree preprocess_hypersim.py wrote, split_path its filename_meta_train.csv.
+    source="raw": root_dir is the dataset as released, split_path its metadata_images_split_scene_v1.csv; files are found as the preprocessing script
+    finds them (preprocess_hypersim.py:62-79), the normal map in the same tree (scene_{cam}_geometry_preview), rows filtered as above; `__getitem__(i)` ->
+    {"color" [768,1024,3], "distance" [768,1024] (float16 / float32 as stored), "entity_id" int32 [768,1024], "normal_u8"}: DeviceLoader / finish_samples
+    tone-map and convert on the device (hypersim_from_raw), then continue as for a processed sample.  The reference's `assert (entity_id_map != 0).all()`
+    is kept: DeviceLoader raises for a batch with such a frame when it hands the batch out (where it waits for the batch's event anyway)."""
     name = "hypersim"
     FOCAL = 886.81                   # load.py:230
 
-    def __init__(self, root_dir, transform=True, near_plane=1e-5, far_plane=65.0, split_path=None, decoder=None):
+    def __init__(self, root_dir, transform=True, near_plane=1e-5, far_plane=65.0, split_path=None, decoder=None, source="processed"):
+        if source not in ("processed", "raw"):
+            raise ValueError("source must be 'processed' or 'raw', got %r" % (source,))
+        self.source = source
         self.root_dir = root_dir
-        self.split_path = split_path or os.path.join("data/hypersim/processed/train/filename_meta_train.csv")
+        self.split_path = split_path or (os.path.join("data/hypersim/metadata_images_split_scene_v1.csv") if source == "raw" else
+                                         os.path.join("data/hypersim/processed/train/filename_meta_train.csv"))     # (preprocess_hypersim.py:27's default / load.py:163)
         self.near_plane, self.far_plane = near_plane, far_plane
         self.align_cam_normal = True
-        self.decoder = decoder or pil_decoder
-        self.pairs = self._find_pairs()
+        self.decoder = decoder or (raw_decoder if source == "raw" else pil_decoder)
+        self.pairs = self._find_raw() if source == "raw" else self._find_pairs()
         self.transform = (480, 640) if transform else None          # SynchronizedTransform_Hyper(H=480, W=640)
+
+    @staticmethod
+    def raw_paths(root_dir, scene, camera, frame):
+        """preprocess_hypersim.py:62-79 + the normal preview beside them -> {"color_path", "distance_path", "entity_path", "normal_path"}"""
+        img = os.path.join(root_dir, scene, "images")
+        geo, fr = os.path.join(img, "scene_%s_geometry_hdf5" % camera), "frame.%04d" % int(frame)
+        return {"color_path": os.path.join(img, "scene_%s_final_hdf5" % camera, fr + ".color.hdf5"),
+                "distance_path": os.path.join(geo, fr + ".depth_meters.hdf5"), "entity_path": os.path.join(geo, fr + ".render_entity_id.hdf5"),
+                "normal_path": os.path.join(img, "scene_%s_geometry_preview" % camera, fr + ".normal_cam.png")}
+
+    def _find_raw(self):
+        pairs = []
+        with open(self.split_path, newline="") as f:
+            for row in csv.DictReader(f):
+                if str(row["included_in_public_release"]).strip().lower() not in ("true", "1") or row["split_partition_name"] != "train":
+                    continue
+                pr = self.raw_paths(self.root_dir, row["scene_name"], row["camera_name"], row["frame_id"])
+                if all(os.path.exists(p) for p in pr.values()):
+                    pairs.append(pr)
+        return pairs
 
     def _find_pairs(self):           # load.py:170-183
         pairs = []
@@ -258,6 +311,13 @@ class Hypersim(_DecodedDataset):
 
     def __getitem__(self, idx):
         pr = self.pairs[idx]
+        if self.source == "raw":
+            color, dist = (np.ascontiguousarray(self.decoder(pr[k + "_path"], k)) for k in ("color", "distance"))
+            for name, a in (("color", color), ("distance", dist)):
+                if a.dtype not in (np.float16, np.float32):
+                    raise TypeError("Hypersim(source='raw'): %s of %s is %s (float16 or float32 expected)" % (name, pr[name + "_path"], a.dtype))
+            ids = np.ascontiguousarray(self.decoder(pr["entity_path"], "entity_id"), dtype=np.int32)
+            return {"color": color, "distance": dist, "entity_id": ids, "normal_u8": np.ascontiguousarray(self.decoder(pr["normal_path"], "normal"))}
         rgb, depth, normal = self._decode(pr["rgb_path"], pr["depth_path"], pr["normal_path"])
         return {"rgb_u8": rgb, "depth": np.ascontiguousarray((depth / 1000).astype(np.float32)), "normal_u8": normal}
 
@@ -338,14 +398,40 @@ def write_png16(path, rgb_u16, level=6):
         f.write(blob)
 
 
+def _zero_id_error(zero_ids):
+    bad = [i for i, z in enumerate(zero_ids) if z != 0]
+    return ValueError("Hypersim raw frames %s of the batch hold render_entity_id == 0 (%s pixels): the reference's tone_map asserts there is none "
+                      "(hypersim_util.py:10)" % (bad, [int(zero_ids[i]) for i in bad])) if bad else None
+
+
 @torch.no_grad()
 @ops.tensor_scoped
-def finish_samples(rgb_u8, depth, normal_u8, dataset, flip=None, transform=True, near_plane=None, far_plane=None, align=True):
+def hypersim_from_raw(color, distance, entity_id, check_ids=True):
+    """preprocess_hypersim.py:83-119 on a batch of raw frames on the device + what Hypersim.__getitem__ makes of the stored depth: color [B,H,W,3],
+    distance [B,H,W] fp16 / fp32, entity_id int32 -> (rgb_u8 [B,H,W,3], depth fp32 [B,H,W] metres = float32(uint16 millimetres / 1000), record fp64
+    [B,16] ops.HYPERSIM_RECORD_FIELDS).  check_ids: read the record back (one synchronisation) and raise where the reference's assertion on ids equal
+    to 0 would fail; DeviceLoader passes False and checks when it hands the batch out."""
+    rgb_u8, depth, rec = ops.hypersim_preprocess(color, distance, entity_id, focal=Hypersim.FOCAL, depth_format="f32")
+    if check_ids:
+        err = _zero_id_error(rec[:, 9].cpu().tolist())
+        if err is not None:
+            raise err
+    return rgb_u8, depth, rec
+
+
+@torch.no_grad()
+@ops.tensor_scoped
+def finish_samples(rgb_u8, depth, normal_u8, dataset, flip=None, transform=True, near_plane=None, far_plane=None, align=True, raw=None):
     """everything `__getitem__` does after decoding (load.py:225-283 / :336-375), batched on the device: rgb_u8 / normal_u8 uint8 [B,H0,W0,3], depth fp32
     [B,H0,W0] metres, flip = per-sample booleans -> the batch dict.  Hypersim: normals turned towards the camera on the full-resolution image
     (e2eft_align_normals_u8), then flip + Pillow-exact resize to 480 x 640; Virtual KITTI 2: flip + KITTI benchmark crop; then prepare_batch.
     Virtual KITTI 2 with normal_u8=None: the normals the reference's offline generator would have stored, made from the full-resolution depth first
-    (depth_to_normals_vkitti), where the reference read them."""
+    (depth_to_normals_vkitti), where the reference read them.
+    Hypersim with raw=(color, distance, entity_id) and rgb_u8 = depth = None: the raw frames go through hypersim_from_raw first (ids checked)."""
+    if raw is not None:
+        if dataset != "hypersim" or rgb_u8 is not None or depth is not None:
+            raise ValueError("finish_samples: raw= is Hypersim's (color, distance, entity_id) and replaces rgb_u8 and depth")
+        rgb_u8, depth, _ = hypersim_from_raw(*raw)
     if normal_u8 is None:
         if dataset != "vkitti":
             raise ValueError("finish_samples: normal_u8 is required for %s (only Virtual KITTI 2 normals can be synthesised from depth)" % dataset)
@@ -402,10 +488,12 @@ class DeviceLoader:
         """stack decoded samples into pinned host buffers (one set per call: the upload is asynchronous)"""
         pin = self.device.type == "cuda"
         out = {}
-        for key, dt in (("rgb_u8", torch.uint8), ("depth", torch.float32), ("normal_u8", torch.uint8)):
-            if key == "normal_u8" and key not in samples[0]:          # VirtualKITTI2(normals="d2nt"): synthesised on the device in _finish
+        for key, dt in (("rgb_u8", torch.uint8), ("depth", torch.float32), ("normal_u8", torch.uint8), ("color", None), ("distance", None), ("entity_id", torch.int32)):
+            if key not in samples[0]:          # VirtualKITTI2(normals="d2nt"): normals synthesised in _finish; Hypersim(source="raw"): rgb_u8 / depth made there
                 continue
             first = samples[0][key]
+            if dt is None:                     # raw colour / distance travel as stored (float16 halves the upload); float32 if any sample of the batch is
+                dt = torch.float16 if all(smp[key].dtype == np.float16 for smp in samples) else torch.float32
             buf = torch.empty((len(samples),) + tuple(first.shape), dtype=dt, pin_memory=pin)
             for i, smp in enumerate(samples):
                 if smp[key].shape != first.shape:
@@ -422,6 +510,10 @@ class DeviceLoader:
             self._stream = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self._stream):
             dev = {k: v.to(self.device, non_blocking=True) for k, v in staged.items()}
+            if "color" in dev:                 # Hypersim(source="raw"): the offline preprocessing, here; its id check waits until the batch is handed out
+                dev["rgb_u8"], dev["depth"], rec = hypersim_from_raw(dev["color"], dev["distance"], dev["entity_id"], check_ids=False)
+                staged["zero_ids"] = torch.empty((rec.shape[0],), dtype=torch.float64, pin_memory=True)
+                staged["zero_ids"].copy_(rec[:, 9], non_blocking=True)
             batch = finish_samples(dev["rgb_u8"], dev["depth"], dev.get("normal_u8"), ds.name, flip=flips if ds.transform else None,
                                    transform=bool(ds.transform), near_plane=ds.near_plane, far_plane=ds.far_plane, align=getattr(ds, "align_cam_normal", False))
             ev = torch.cuda.Event()
@@ -472,6 +564,11 @@ class DeviceLoader:
                 nxt = self._finish(self._stage([f.result() for f in futs]), flips)
             if ready is not None:
                 batch, ev, staged = ready
+                if "zero_ids" in staged:       # raw Hypersim: the reference's assertion, on a batch submitted one consumer step ago
+                    ev.synchronize()
+                    err = _zero_id_error(staged["zero_ids"].tolist())
+                    if err is not None:
+                        raise err
                 torch.cuda.current_stream(self.device).wait_event(ev)
                 for v in batch.values():
                     if isinstance(v, torch.Tensor):

@@ -1641,3 +1641,54 @@ def depth_to_normals(depth, intrinsics, refine=True, out_format="f32", depth_sca
     desc.batch, desc.height, desc.width, desc.refine, desc.out_format, desc.depth_scale = B, H, W, 1 if refine else 0, fmt, float(depth_scale)
     check(_lib.load().e2eft_depth_to_normals(C.byref(desc), _ptr(d), _ptr(k), _ptr(out), _stream()))
     return out[0] if squeeze else out
+
+
+_HYPERSIM_DEPTH = {"u16": (_lib.HYPERSIM_DEPTH_U16, torch.uint16), "f32": (_lib.HYPERSIM_DEPTH_F32, torch.float32)}
+HYPERSIM_RECORD_FIELDS = ("invalid_ratio", "rgb_mean", "rgb_std", "rgb_min", "rgb_max", "depth_mean", "depth_std", "depth_min", "depth_max",
+                          "zero_ids", "nan_brightness", "n_valid", "percentile", "scale")
+
+
+def hypersim_scale_numerator():
+    """hypersim_util.py:41-44: np.power(0.8, inv_gamma) with inv_gamma = 1.0 / (1.0 / 2.2), as this host's numpy computes it (once)"""
+    import numpy as np
+    return float(np.power(0.8, 1.0 / (1.0 / 2.2)))
+
+
+def hypersim_preprocess(color, distance, entity_id, focal=886.81, depth_format="u16", out=None):
+    """raw Hypersim frames -> what preprocess_hypersim.py stores (csrc/hypersimprep.hip, include/e2eft.h e2eft_hypersim_preprocess): color [B,H,W,3] and
+    distance [B,H,W] fp16 or fp32, entity_id int32 [B,H,W] (or one frame without the batch axis) -> (rgb_u8 uint8 [B,H,W,3] tone-mapped, depth [B,H,W]
+    planar: "u16" the file's millimetres / "f32" metres as the training loader reads the file back, record fp64 [B,16]: HYPERSIM_RECORD_FIELDS).
+    out = (rgb_u8, depth, record) to write into existing tensors.  No host synchronisation."""
+    if depth_format not in _HYPERSIM_DEPTH:
+        raise ValueError("depth_format must be one of %s, got %r" % (sorted(_HYPERSIM_DEPTH), depth_format))
+    fmt, odt = _HYPERSIM_DEPTH[depth_format]
+    squeeze = entity_id.dim() == 2
+    c, d, e = (color[None], distance[None], entity_id[None]) if squeeze else (color, distance, entity_id)
+    if c.dim() != 4 or c.shape[-1] != 3 or tuple(d.shape) != tuple(c.shape[:3]) or tuple(e.shape) != tuple(c.shape[:3]):
+        raise ValueError("hypersim_preprocess: color [B,H,W,3], distance and entity_id [B,H,W]; got %s, %s, %s" % (tuple(color.shape), tuple(distance.shape), tuple(entity_id.shape)))
+    for name, t in (("color", c), ("distance", d)):
+        if t.dtype not in (torch.float16, torch.float32):
+            raise TypeError("hypersim_preprocess: %s must be float16 or float32, got %s" % (name, t.dtype))
+    if e.dtype != torch.int32:
+        raise TypeError("hypersim_preprocess: entity_id must be int32, got %s" % e.dtype)
+    c, d, e = c.contiguous(), d.contiguous(), e.contiguous()
+    B, H, W = e.shape
+    dev = c.device
+    if out is None:
+        out = (torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev), torch.empty((B, H, W), dtype=odt, device=dev),
+               torch.empty((B, _lib.HYPERSIM_RECORD), dtype=torch.float64, device=dev))
+    rgb, depth, rec = out
+    assert rgb.dtype == torch.uint8 and tuple(rgb.shape) == (B, H, W, 3) and rgb.is_contiguous(), (rgb.dtype, tuple(rgb.shape))
+    assert depth.dtype == odt and tuple(depth.shape) == (B, H, W) and depth.is_contiguous(), (depth.dtype, tuple(depth.shape))
+    assert rec.dtype == torch.float64 and tuple(rec.shape) == (B, _lib.HYPERSIM_RECORD) and rec.is_contiguous(), (rec.dtype, tuple(rec.shape))
+    _check_cuda(c, d, e, rgb, depth, rec)
+    desc = _lib.HypersimDesc()
+    desc.batch, desc.height, desc.width, desc.color_dtype, desc.distance_dtype, desc.depth_format = B, H, W, _lib.dtype_id(c.dtype), _lib.dtype_id(d.dtype), fmt
+    desc.focal, desc.scale_numerator = float(focal), hypersim_scale_numerator()
+    lib = _lib.load()
+    nbytes = lib.e2eft_hypersim_preprocess_workspace_bytes(C.byref(desc))
+    if nbytes == 0:
+        raise RuntimeError(lib.e2eft_last_error().decode())
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    check(lib.e2eft_hypersim_preprocess(C.byref(desc), _ptr(c), _ptr(d), _ptr(e), _ptr(rgb), _ptr(depth), _ptr(rec), _ptr(ws), nbytes, _stream()))
+    return (rgb[0], depth[0], rec[0]) if squeeze else (rgb, depth, rec)

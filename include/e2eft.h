@@ -547,6 +547,38 @@ typedef struct {
     float depth_scale;  /* Z = depth * depth_scale, fp32 */
 } e2eft_d2nt_desc;
 int e2eft_depth_to_normals(const e2eft_d2nt_desc* desc, const float* depth, const float* intrinsics, void* out, void* stream);
+/* Raw Hypersim frames to the training loader's inputs (the offline step Marigold/script/dataset_preprocess/hypersim/preprocess_hypersim.py:83-138
+ * over hypersim_util.py:9-69 that makes the processed/ tree), for a batch of frames, all in DEVICE memory, contiguous:
+ *   color [batch][height][width][3] and distance [batch][height][width] (metres along the ray) of color_dtype / distance_dtype (E2EFT_F32 or
+ *   E2EFT_F16; the reference converts both to fp64 first), entity_id int32 [batch][height][width] (render_entity_id; -1 = invalid pixel).
+ *   rgb_u8 [batch][height][width][3]: brightness = (0.3 r + 0.59 g) + 0.11 b in fp64 over the valid pixels, p = its 90th percentile as
+ *     np.percentile computes it (virtual index 0.9 (n - 1), the two neighbouring exact order statistics a, b, a + (b - a) t or b - (b - a) (1 - t)
+ *     where t >= 0.5; NaN if a valid brightness is NaN), scale = 1 without a valid pixel, 0 where p < 1e-4, else scale_numerator / p
+ *     (scale_numerator: np.power(0.8, 1.0 / (1.0 / 2.2)) as the caller's numpy computes it, 0.6120656...); the image is
+ *     trunc(255 clip(pow(max(scale rgb, 0), 1 / 2.2), 0, 1)) in fp64; a NaN gives 0.
+ *   depth [batch][height][width]: distance / double(sqrtf((x x + y y) + z z)) * focal with the float32 grid x = j - width / 2 + 1 / 2,
+ *     y = i - height / 2 + 1 / 2, z = float(focal); 0 on invalid pixels; * 1000.0, then the uint16 cast, DEFINED as an x86-64 host's numpy is observed
+ *     to do it (C leaves it undefined out of range): the low 16 bits of the truncated integer while that fits int32 (65536 mm and more wrap, as in the
+ *     reference's files; a negative value wraps from the top), 0 for a NaN and beyond the int32 range.
+ *     E2EFT_HYPERSIM_DEPTH_U16: those millimetres (the file); E2EFT_HYPERSIM_DEPTH_F32: float(u16 / 1000.0), what the loader reads back (load.py:220-222).
+ *   record fp64 [batch][E2EFT_HYPERSIM_RECORD]: 0 invalid_ratio, 1-4 mean / std / min / max of rgb_u8, 5-8 mean / std / min / max of u16 / 1000 (the
+ *     columns of filename_meta_{split}.csv), 9 number of ids equal to 0 (the reference asserts there is none), 10 1.0 if a valid brightness is NaN,
+ *     11 n valid, 12 the percentile (NaN without a valid pixel), 13 the scale, 14-15 zero.
+ * The percentile is an exact radix selection over 64-bit keys (six histogram passes that recompute the brightness; nothing is sorted or stored per
+ * pixel).  workspace: e2eft_hypersim_preprocess_workspace_bytes(desc) (0 for a descriptor the call would reject), 16-byte aligned.  height * width
+ * < 2^31, batch <= 65535.  17 launches on `stream`, no host synchronisation, no device read-back: capturable in a graph. */
+enum { E2EFT_HYPERSIM_DEPTH_U16 = 0, E2EFT_HYPERSIM_DEPTH_F32 = 1 };
+#define E2EFT_HYPERSIM_RECORD 16
+typedef struct {
+    int32_t batch, height, width;
+    int32_t color_dtype, distance_dtype; /* E2EFT_F32 or E2EFT_F16 */
+    int32_t depth_format;                /* E2EFT_HYPERSIM_DEPTH_* */
+    double focal;                        /* 886.81 for Hypersim (preprocess_hypersim.py:19) */
+    double scale_numerator;              /* np.power(0.8, 2.2): the brightness the percentile maps to, before the display gamma */
+} e2eft_hypersim_desc;
+size_t e2eft_hypersim_preprocess_workspace_bytes(const e2eft_hypersim_desc* desc);
+int e2eft_hypersim_preprocess(const e2eft_hypersim_desc* desc, const void* color, const void* distance, const int32_t* entity_id, uint8_t* rgb_u8,
+                              void* depth, double* record, void* workspace, size_t ws_bytes, void* stream);
 /* Test-time ensembling of the n_img (<= 32) predictions of ONE image, fp32, replacing
  *   ensemble_depths   /root/reference/Marigold/marigold/util/ensemble.py:40-132 (called from marigold_pipeline.py:293-297;
  *                     twin GeoWizard/geowizard/utils/depth_ensemble.py:21-115)

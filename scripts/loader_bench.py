@@ -9,6 +9,9 @@ Writes `--samples` synthetic Hypersim-format samples (full-size PNGs: rgb, 16-bi
   decode_only     data.Hypersim.__getitem__ (decode only) on `--workers` threads;
   device_loader   data.DeviceLoader end to end (decode threads -> pinned staging -> upload -> e2eft_align_normals_u8 / aug / quantile / prepare kernels), when a GPU
                   is present: images/s of batches ready on the device, and the device time of the preparation alone.
+  raw_source      the same three steps for data.Hypersim(source="raw") over the same number of synthetic RAW frames (fp16 colour, fp32 distance, int32 ids per
+                  pixel: 16 B against the 8 B of the decoded PNGs) — the frames are .npy bytes read by an injected decoder (tests/hypersim_raw_fixture.py): the host
+                  cost of the larger samples is measured, real HDF5 decoding (h5py) is NOT.
 One JSON line on stdout."""
 import argparse
 import json
@@ -93,6 +96,51 @@ def run_ranks(args, root_dir, split_path):
                     "each rank has its own GPU in training, `device_prepare` gives its cost per batch); total images / slowest rank's time"}
 
 
+def raw_source(args, tmp, dev):
+    """decode_only / device_loader / device_prepare as in main(), for Hypersim(source="raw") through the .npy decoder"""
+    from concurrent.futures import ThreadPoolExecutor
+    import hypersim_raw_fixture as rawfx
+    from diffusion_e2e_ft_amd import data
+    raw, split, _ = rawfx.make_raw_tree(os.path.join(tmp, "rawtree"), n=args.samples, H=args.height, W=args.width)
+    ds = data.Hypersim(raw, transform=True, split_path=split, source="raw", decoder=rawfx.npy_decoder)
+    assert len(ds) == args.samples
+    res = {"what": "Hypersim(source='raw'), frames stored as .npy bytes behind the released file names; HDF5 decoding (h5py) not measured",
+           "bytes_per_pixel_staged": 6 + 4 + 4 + 3}
+    with ThreadPoolExecutor(args.workers) as ex:
+        list(ex.map(ds.__getitem__, range(min(len(ds), args.workers))))
+        t0 = time.perf_counter()
+        for _ in range(args.epochs):
+            list(ex.map(ds.__getitem__, range(len(ds))))
+        res["decode_only"] = {"images_per_s": args.epochs * len(ds) / (time.perf_counter() - t0), "threads": args.workers}
+    loader = data.DeviceLoader(ds, batch_size=args.batch, device=dev, shuffle=True, drop_last=True, workers=args.workers, prefetch=3)
+    for b in loader:
+        pass
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = 0
+    for _ in range(args.epochs):
+        for b in loader:
+            n += b["rgb"].shape[0]
+    torch.cuda.synchronize()
+    res["device_loader"] = {"images_per_s": n / (time.perf_counter() - t0), "batches": n // args.batch}
+    st = loader._stage([ds[i] for i in range(args.batch)])
+    dv = {k: v.to(dev) for k, v in st.items()}
+    flips = [i % 2 == 0 for i in range(args.batch)]
+    run = lambda: data.finish_samples(None, None, dv["normal_u8"], "hypersim", flip=flips, raw=(dv["color"], dv["distance"], dv["entity_id"]))
+    for _ in range(3):
+        run()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / 20
+    res["device_prepare"] = {"ms_per_batch": ms, "images_per_s": args.batch / ms * 1e3, "what": "hypersim_from_raw (with its id check: one read-back) + the processed path's preparation, batch resident"}
+    loader.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=24)
@@ -167,6 +215,7 @@ def main():
             ms = e0.elapsed_time(e1) / 20
             out["device_prepare"] = {"ms_per_batch": ms, "images_per_s": args.batch / ms * 1e3, "what": "align_normals + flip / Pillow-exact resize + quantiles + prepare, batch resident"}
             loader.close()
+            out["raw_source"] = raw_source(args, tmp, dev)
             if args.ranks > 1:
                 out["device_loader_ranks"] = run_ranks(args, root_dir, split_path)
     print(json.dumps(out))
