@@ -63,6 +63,15 @@ HYPERSIM_DEPTH_U16, HYPERSIM_DEPTH_F32 = range(2)      # e2eft_hypersim_desc.dep
 HYPERSIM_RECORD = 16                                    # E2EFT_HYPERSIM_RECORD
 
 
+class DepthGtDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("batch", "h0", "w0", "raw_dtype")] + [("divisor", C.c_double)]
+                + [(n, C.c_int32) for n in ("inf_to_zero", "crop_top", "crop_left", "crop_h", "crop_w")] + [("min_depth", C.c_float), ("max_depth", C.c_float)]
+                + [(n, C.c_int32) for n in ("win_y0", "win_y1", "win_x0", "win_x1", "use_ext_mask")])
+
+
+GT_U16, GT_I32, GT_F32 = range(3)      # e2eft_depth_gt_desc.raw_dtype
+
+
 # e2eft_set_option keys (include/e2eft.h)
 OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT = range(15)
 
@@ -171,6 +180,7 @@ SIGNATURES = {
     "e2eft_depth_to_normals": (_I, [C.POINTER(D2ntDesc), _P, _P, _P, _P]),
     "e2eft_hypersim_preprocess_workspace_bytes": (_Z, [C.POINTER(HypersimDesc)]),
     "e2eft_hypersim_preprocess": (_I, [C.POINTER(HypersimDesc), _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "e2eft_depth_gt_prepare": (_I, [C.POINTER(DepthGtDesc), _P, _P, _P, _P, _P, _P]),
     "e2eft_ensemble_workspace_bytes": (_Z, [_I]),
     "e2eft_ensemble_minmax": (_I, [_I, _L, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_gram": (_I, [_I, _L, _P, _P, _P, _P, _Z, _P]),

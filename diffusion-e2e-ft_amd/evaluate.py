@@ -5,6 +5,7 @@ for whole batches in one launch sequence (csrc/evalmetrics.hip), instead of nump
   align_depth_least_square   same name and return convention as the reference's function, torch tensors on the device
   depth_metrics              per-image metric table (dict name -> tensor [B]) and its mean, named as eval.py's metric functions
   MetricTracker              running averages keyed by metric name (the reference's pandas-backed tracker, metric.py:9-31)
+  evaluate_depth_benchmark   the reference's infer.py + eval.py pair over one benchmark dataset (eval_data.py) without the .npy round trip
 
 Surface normals (DSINE's benchmark mode, csrc/normaleval.hip), named as DSINE/utils/utils.py names them:
   normal_error               compute_normal_error (utils.py:150-158): per-pixel angular error in degrees, [B,1,H,W] fp32
@@ -89,6 +90,78 @@ class MetricTracker:
 
     def result(self):
         return {k: self.avg(k) for k in self._tot if self._cnt[k]}
+
+
+def _metric_table(rows):
+    """the name / value table of eval_metrics.txt: tabulate's when it imports (eval.py:237-239), two plain rows otherwise"""
+    try:
+        from tabulate import tabulate
+    except ImportError:
+        cells = [[str(c) for c in r] for r in rows]
+        width = [max(len(r[i]) for r in cells) for i in range(len(cells[0]))]
+        return "\n".join("  ".join(c.ljust(w) for c, w in zip(r, width)).rstrip() for r in cells)
+    return tabulate(rows)
+
+
+def evaluate_depth_benchmark(pipe, dataset, alignment="least_square", alignment_max_res=None, output_dir=None, save_predictions=False, **pipe_kwargs):
+    """Marigold/infer.py:278-333 and Marigold/eval.py:146-249 in one loop over an eval_data dataset in EVAL mode: per sample, `pipe(PIL image,
+    **pipe_kwargs).depth_np` is aligned to depth_raw_linear over valid_mask_raw, clipped to the dataset's range and measured (depth_metrics, on the
+    device); the ten metrics are averaged over the samples (MetricTracker) and returned as a dict.  A sample without a valid pixel is named in a
+    warning and left out of the average.  output_dir: per_sample_metrics.csv and eval_metrics[-<alignment>].txt as eval.py writes them;
+    save_predictions: also the .npy predictions where infer.py puts them (<output_dir>/<scene dir>/<get_pred_name(...)>)."""
+    import os
+    import warnings
+
+    import numpy as np
+    from PIL import Image
+
+    from .eval_data import DatasetMode, get_pred_name
+    if alignment not in ("least_square", "least_square_disparity"):
+        raise ValueError("alignment must be least_square or least_square_disparity (the prediction is affine-invariant)")
+    if dataset.mode != DatasetMode.EVAL:
+        raise ValueError("evaluate_depth_benchmark needs a dataset in DatasetMode.EVAL, got %s" % (dataset.mode,))
+    if save_predictions and output_dir is None:
+        raise ValueError("save_predictions needs an output_dir")
+    tracker = MetricTracker(*METRIC_NAMES)
+    per_sample = None
+    if output_dir is not None:
+        os.makedirs(output_dir, exist_ok=True)
+        per_sample = os.path.join(output_dir, "per_sample_metrics.csv")
+        with open(per_sample, "w") as f:
+            f.write("filename," + ",".join(METRIC_NAMES) + "\n")
+    for i in range(len(dataset)):
+        item = dataset[i]
+        rgb_name = item["rgb_relative_path"]
+        pred_name = os.path.join(os.path.dirname(rgb_name), get_pred_name(os.path.basename(rgb_name), dataset.name_mode, suffix=".npy"))
+        image = Image.fromarray(item["rgb_int"].permute(1, 2, 0).to(torch.uint8).cpu().numpy())
+        pred = np.asarray(pipe(image, **pipe_kwargs).depth_np)
+        if save_predictions:
+            os.makedirs(os.path.dirname(os.path.join(output_dir, pred_name)), exist_ok=True)
+            np.save(os.path.join(output_dir, pred_name), pred)
+        gt, mask = item["depth_raw_linear"][0], item["valid_mask_raw"][0]
+        if tuple(pred.shape) != tuple(gt.shape):
+            raise ValueError("%s: prediction %s and ground truth %s differ in shape" % (rgb_name, tuple(pred.shape), tuple(gt.shape)))
+        if int(item["n_valid_raw"]) == 0:
+            warnings.warn("evaluate_depth_benchmark: %s has no valid ground-truth pixel; skipped" % rgb_name)
+            continue
+        with ops.on_device_of(gt):
+            m = depth_metrics(torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(gt.device), gt, mask, alignment=alignment,
+                              min_depth=dataset.min_depth, max_depth=dataset.max_depth, alignment_max_res=alignment_max_res)
+            values = torch.stack([m[k][0] for k in METRIC_NAMES]).cpu().tolist()
+        for k, v in zip(METRIC_NAMES, values):
+            tracker.update(k, v)
+        if per_sample is not None:
+            with open(per_sample, "a") as f:
+                f.write(pred_name + "," + ",".join(str(v) for v in values) + "\n")
+    result = tracker.result()
+    if output_dir is not None:
+        text = ("Evaluation metrics:\n    of predictions: %s\n    on dataset: %s\n    with samples in: %s\n"
+                % (output_dir if save_predictions else "(in memory)", dataset.disp_name, dataset.filename_ls_path))
+        text += "min_depth = %s\nmax_depth = %s\n" % (dataset.min_depth, dataset.max_depth)
+        text += _metric_table([list(result.keys()), list(result.values())])
+        with open(os.path.join(output_dir, "eval_metrics-%s.txt" % alignment), "w") as f:
+            f.write(text)
+    return result
 
 
 NORMAL_METRIC_NAMES = ("mean", "median", "rmse", "a1", "a2", "a3", "a4", "a5")

@@ -1692,3 +1692,54 @@ def hypersim_preprocess(color, distance, entity_id, focal=886.81, depth_format="
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
     check(lib.e2eft_hypersim_preprocess(C.byref(desc), _ptr(c), _ptr(d), _ptr(e), _ptr(rgb), _ptr(depth), _ptr(rec), _ptr(ws), nbytes, _stream()))
     return (rgb[0], depth[0], rec[0]) if squeeze else (rgb, depth, rec)
+
+
+_GT_DTYPES = {torch.uint16: _lib.GT_U16, torch.int32: _lib.GT_I32, torch.float32: _lib.GT_F32}
+
+
+def depth_gt_prepare(raw, divisor=1.0, min_depth=0.0, max_depth=float("inf"), crop=None, window=None, inf_to_zero=False, ext_mask=None, count=True, out=None):
+    """decoded benchmark ground truth -> evaluation inputs (csrc/evalprep.hip, include/e2eft.h e2eft_depth_gt_prepare): raw [B,H0,W0] (or one raster
+    [H0,W0]) uint16, int32 or float32 -> (depth fp32 [B,h,w] = float(double(raw) / divisor), valid mask bool [B,h,w], n_valid int32 [B] or None).
+    crop = (top, left, h, w) inside the raster (None: all of it); window = (y0, y1, x0, x1) in output coordinates, clamped to the output here as a
+    slice would be (None: no evaluation window); inf_to_zero: +inf -> 0 before the range test; ext_mask uint8 / bool [B,H0,W0]: the mask is
+    ext_mask != 0 alone, cropped like raw.  out = (depth, mask uint8, n_valid) to write into existing tensors.  No host synchronisation."""
+    squeeze = raw.dim() == 2
+    r = raw[None] if squeeze else raw
+    if r.dim() != 3:
+        raise ValueError("depth_gt_prepare: raw must be [H,W] or [B,H,W]; got %s" % (tuple(raw.shape),))
+    if r.dtype not in _GT_DTYPES:
+        raise TypeError("depth_gt_prepare: raw must be uint16, int32 or float32, got %s" % r.dtype)
+    r = r.contiguous()
+    B, H0, W0 = r.shape
+    top, left, h, w = (0, 0, H0, W0) if crop is None else (int(v) for v in crop)
+    if top < 0 or left < 0 or h <= 0 or w <= 0 or top + h > H0 or left + w > W0:
+        raise ValueError("depth_gt_prepare: crop %d x %d at (%d, %d) lies outside the %d x %d raster" % (h, w, top, left, H0, W0))
+    y0, y1, x0, x1 = (0, h, 0, w) if window is None else (int(v) for v in window)
+    y0, y1, x0, x1 = min(max(y0, 0), h), min(max(y1, 0), h), min(max(x0, 0), w), min(max(x1, 0), w)
+    y1, x1 = max(y1, y0), max(x1, x0)
+    e = None
+    if ext_mask is not None:
+        e = ext_mask[None] if ext_mask.dim() == 2 else ext_mask
+        if e.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("depth_gt_prepare: ext_mask must be uint8 or bool, got %s" % e.dtype)
+        if tuple(e.shape) != (B, H0, W0):
+            raise ValueError("depth_gt_prepare: ext_mask %s does not match raw %s" % (tuple(ext_mask.shape), tuple(raw.shape)))
+        e = e.contiguous()
+        e = e.view(torch.uint8) if e.dtype == torch.bool else e
+    dev = r.device
+    if out is None:
+        out = (torch.empty((B, h, w), dtype=torch.float32, device=dev), torch.empty((B, h, w), dtype=torch.uint8, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev) if count else None)
+    depth, mask, nv = out
+    assert depth.dtype == torch.float32 and tuple(depth.shape) == (B, h, w) and depth.is_contiguous(), (depth.dtype, tuple(depth.shape))
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == (B, h, w) and mask.is_contiguous(), (mask.dtype, tuple(mask.shape))
+    assert nv is None or (nv.dtype == torch.int32 and tuple(nv.shape) == (B,) and nv.is_contiguous()), (nv.dtype, tuple(nv.shape))
+    _check_cuda(r, e, depth, mask, nv)
+    desc = _lib.DepthGtDesc()
+    desc.batch, desc.h0, desc.w0, desc.raw_dtype, desc.divisor, desc.inf_to_zero = B, H0, W0, _GT_DTYPES[r.dtype], float(divisor), 1 if inf_to_zero else 0
+    desc.crop_top, desc.crop_left, desc.crop_h, desc.crop_w = top, left, h, w
+    desc.min_depth, desc.max_depth = float(min_depth), float(max_depth)
+    desc.win_y0, desc.win_y1, desc.win_x0, desc.win_x1, desc.use_ext_mask = y0, y1, x0, x1, 0 if e is None else 1
+    check(_lib.load().e2eft_depth_gt_prepare(C.byref(desc), _ptr(r), _ptr(e), _ptr(depth), _ptr(mask), _ptr(nv), _stream()))
+    mb = mask.view(torch.bool)
+    return (depth[0], mb[0], nv) if squeeze else (depth, mb, nv)

@@ -579,6 +579,33 @@ typedef struct {
 size_t e2eft_hypersim_preprocess_workspace_bytes(const e2eft_hypersim_desc* desc);
 int e2eft_hypersim_preprocess(const e2eft_hypersim_desc* desc, const void* color, const void* distance, const int32_t* entity_id, uint8_t* rgb_u8,
                               void* depth, double* record, void* workspace, size_t ws_bytes, void* stream);
+/* Decoded benchmark ground truth to evaluation inputs (what the reference's evaluation dataset classes do to a depth file after decoding it:
+ * Marigold/src/dataset/base_depth_dataset.py:127-141,181-185 and the overrides in nyu / kitti / eth3d / scannet / diode _dataset.py), for a batch of
+ * rasters raw [batch][h0][w0] of raw_dtype in DEVICE memory, contiguous, in one launch.  Per pixel of the output rectangle (crop_top, crop_left,
+ * crop_h, crop_w inside the raster; no crop: 0, 0, h0, w0):
+ *   d = (float)((double)raw / divisor): numpy's float64 division followed by torch's .float() (E2EFT_GT_F32 with divisor 1 passes through bit for bit);
+ *   inf_to_zero: d == +inf becomes 0 (ETH3D; a NaN stays and is invalid by comparison);
+ *   valid = d > min_depth && d < max_depth in float32 (+inf allowed for max_depth), and the pixel lies in rows win_y0:win_y1, columns win_x0:win_x1 of
+ *     the OUTPUT (the evaluation mask window, clamped by the caller; 0:crop_h, 0:crop_w = none);
+ *   use_ext_mask: valid = ext_mask != 0 alone (DIODE: the mask comes from the file; ext_mask is uint8 [batch][h0][w0], cropped like raw; no range or
+ *     window test).
+ * depth fp32 and mask uint8 (0 / 1) [batch][crop_h][crop_w]; n_valid int32 [batch] = the sum of each frame's mask, or NULL.  n_valid is cleared on the
+ * stream and accumulated with one integer atomic per block (exact in any order: bit-reproducible).  Rows are read with 16-byte loads from their aligned
+ * chunks whatever crop_left and w0 are; raw only needs the alignment of its element type.  crop_h <= 262140, batch <= 65535.  No host synchronisation,
+ * no device read-back: capturable in a graph. */
+enum { E2EFT_GT_U16 = 0, E2EFT_GT_I32 = 1, E2EFT_GT_F32 = 2 };
+typedef struct {
+    int32_t batch, h0, w0;
+    int32_t raw_dtype;                             /* E2EFT_GT_* */
+    double divisor;                                /* 1000 (NYUv2, ScanNet), 256 (KITTI), 1 (ETH3D, DIODE) */
+    int32_t inf_to_zero;
+    int32_t crop_top, crop_left, crop_h, crop_w;
+    float min_depth, max_depth;
+    int32_t win_y0, win_y1, win_x0, win_x1;
+    int32_t use_ext_mask;
+} e2eft_depth_gt_desc;
+int e2eft_depth_gt_prepare(const e2eft_depth_gt_desc* desc, const void* raw, const uint8_t* ext_mask, float* depth, uint8_t* mask, int32_t* n_valid,
+                           void* stream);
 /* Test-time ensembling of the n_img (<= 32) predictions of ONE image, fp32, replacing
  *   ensemble_depths   /root/reference/Marigold/marigold/util/ensemble.py:40-132 (called from marigold_pipeline.py:293-297;
  *                     twin GeoWizard/geowizard/utils/depth_ensemble.py:21-115)
