@@ -72,6 +72,21 @@ class DepthGtDesc(C.Structure):
 GT_U16, GT_I32, GT_F32 = range(3)      # e2eft_depth_gt_desc.raw_dtype
 
 
+class NormalGtDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "raw_dtype")]
+
+
+NORMAL_GT_U8, NORMAL_GT_F32 = range(2)      # e2eft_normal_gt_desc.raw_dtype
+
+
+class DsineRgbDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "out_layout")]
+
+
+RGB_HWC, RGB_CHW = range(2)                 # e2eft_dsine_rgb_desc.out_layout
+DSINE_RGB_WS_INTS = 6                       # E2EFT_DSINE_RGB_WS_INTS
+
+
 # e2eft_set_option keys (include/e2eft.h)
 OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT = range(15)
 
@@ -181,6 +196,8 @@ SIGNATURES = {
     "e2eft_hypersim_preprocess_workspace_bytes": (_Z, [C.POINTER(HypersimDesc)]),
     "e2eft_hypersim_preprocess": (_I, [C.POINTER(HypersimDesc), _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "e2eft_depth_gt_prepare": (_I, [C.POINTER(DepthGtDesc), _P, _P, _P, _P, _P, _P]),
+    "e2eft_normal_gt_prepare": (_I, [C.POINTER(NormalGtDesc), _P, _P, _P, _P, _P]),
+    "e2eft_dsine_rgb_requantize": (_I, [C.POINTER(DsineRgbDesc), _P, _P, _P, _P]),
     "e2eft_ensemble_workspace_bytes": (_Z, [_I]),
     "e2eft_ensemble_minmax": (_I, [_I, _L, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_gram": (_I, [_I, _L, _P, _P, _P, _P, _Z, _P]),

@@ -12,6 +12,7 @@ Surface normals (DSINE's benchmark mode, csrc/normaleval.hip), named as DSINE/ut
   normal_metrics             compute_normal_metrics(compute_normal_error(pred, gt)[mask]) (utils.py:161-178) in one call
   NormalMetricAccumulator    the accumulation loop of DSINE/projects/dsine/test.py:104-133 without the torch.cat per image or the host round trip
   format_normal_metrics      the two lines test.py prints and writes to metrics.txt
+  evaluate_normal_benchmark  test.py:40-133 over one normal benchmark (normal_eval_data.py): re-quantised image in, pooled metrics and metrics.txt out
 """
 import torch
 
@@ -304,3 +305,54 @@ class NormalMetricAccumulator:
 def format_normal_metrics(m):
     """the header line and the "%.3f" x 8 line test.py:117-120 prints (and writes to metrics.txt, :126-129)"""
     return NORMAL_METRIC_HEADER + "\n" + "%.3f %.3f %.3f %.3f %.3f %.3f %.3f %.3f" % tuple(m[k] for k in NORMAL_METRIC_NAMES)
+
+
+def normal_metrics_text(m, iterations):
+    """the four lines test.py:126-132 writes to metrics.txt"""
+    return "Normal Estimation Metrics:\nMetrics at iteration %d\n%s\n" % (iterations, format_normal_metrics(m))
+
+
+def evaluate_normal_benchmark(pipe, dataset, output_dir=None, domain=None, **pipe_kwargs):
+    """DSINE/projects/dsine/test.py:40-133 over one normal_eval_data.NormalBenchmarkDataset: per sample, `pipe(PIL image, **pipe_kwargs).normal_np` —
+    the image is the RE-QUANTISED one of test.py:59-68 (the dataset's img_u8), so any callable with the reference's signature works — is measured
+    against the ground truth over its valid pixels on the device (NormalMetricAccumulator: the errors of all images are pooled, then the metrics
+    are taken, as the reference does).  normal_np may be [3,H,W] (Marigold) or [H,W,3] (GeoWizard).  A DepthNormalEstimationPipeline is also given
+    `domain` (None: the dataset's, test.py:47-53).  Returns the metrics dict (evaluate.NORMAL_METRIC_NAMES and "n"), or None with a warning when no
+    pixel is valid anywhere.  output_dir: <output_dir>/test/<dataset_name>/metrics.txt as test.py:123-132 writes it."""
+    import os
+    import warnings
+
+    import numpy as np
+    from PIL import Image
+
+    from .pipeline import DepthNormalEstimationPipeline
+    if isinstance(pipe, DepthNormalEstimationPipeline):
+        pipe_kwargs = dict(pipe_kwargs, domain=domain if domain is not None else dataset.domain)
+    acc = NormalMetricAccumulator()
+    iterations = 0
+    for i in range(len(dataset)):
+        item = dataset[i]
+        name = "%s/%s/%s" % (item["dataset_name"], item["scene_name"], item["img_name"])
+        gt, mask = item["normal"], item["normal_mask"]
+        image = Image.fromarray(item["img_u8"].permute(1, 2, 0).contiguous().cpu().numpy())
+        pred = np.asarray(pipe(image, **pipe_kwargs).normal_np)
+        H, W = gt.shape[-2:]
+        if pred.shape == (3, H, W):
+            p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))
+        elif pred.shape == (H, W, 3):
+            p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).permute(2, 0, 1)          # test.py:84: a view, read in place
+        else:
+            raise ValueError("%s: prediction %s matches neither [3,%d,%d] nor [%d,%d,3], the ground truth's shape" % (name, tuple(pred.shape), H, W, H, W))
+        with ops.on_device_of(gt):
+            acc.update(p.to(gt.device), gt, mask)
+        iterations += 1
+    result = acc.result() if iterations else None
+    if result is None:
+        warnings.warn("evaluate_normal_benchmark: no valid ground-truth pixel in %s (%d samples); no metrics" % (dataset.dataset_name, iterations))
+        return None
+    if output_dir is not None:
+        path = os.path.join(output_dir, "test", dataset.dataset_name, "metrics.txt")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(normal_metrics_text(result, iterations))
+    return result

@@ -1743,3 +1743,79 @@ def depth_gt_prepare(raw, divisor=1.0, min_depth=0.0, max_depth=float("inf"), cr
     check(_lib.load().e2eft_depth_gt_prepare(C.byref(desc), _ptr(r), _ptr(e), _ptr(depth), _ptr(mask), _ptr(nv), _stream()))
     mb = mask.view(torch.bool)
     return (depth[0], mb[0], nv) if squeeze else (depth, mb, nv)
+
+
+_NORMAL_GT_DTYPES = {torch.uint8: _lib.NORMAL_GT_U8, torch.float32: _lib.NORMAL_GT_F32}
+
+
+def normal_gt_prepare(raw, out=None):
+    """decoded benchmark normals -> evaluation inputs (csrc/normalprep.hip, include/e2eft.h e2eft_normal_gt_prepare): raw [B,H,W,3] (or one raster
+    [H,W,3]), R, G, B interleaved, uint8 (a PNG: mask = r + g + b > 0, normal = u8 / 255 * 2 - 1 in fp32) or float32 (an EXR: mask = |n| > 0.5, the
+    values pass through bit for bit) -> (normal fp32 [B,3,H,W], mask bool [B,1,H,W], n_valid int32 [B]).  out = (normal, mask uint8, n_valid) to
+    write into existing tensors.  No host synchronisation."""
+    squeeze = raw.dim() == 3
+    r = raw[None] if squeeze else raw
+    if r.dim() != 4 or r.shape[-1] != 3:
+        raise ValueError("normal_gt_prepare: raw must be [H,W,3] or [B,H,W,3]; got %s" % (tuple(raw.shape),))
+    if r.dtype not in _NORMAL_GT_DTYPES:
+        raise TypeError("normal_gt_prepare: raw must be uint8 or float32, got %s" % r.dtype)
+    if r.numel() == 0:
+        raise ValueError("normal_gt_prepare: empty raster %s" % (tuple(raw.shape),))
+    r = r.contiguous()
+    B, H, W, _ = r.shape
+    dev = r.device
+    if out is None:
+        out = (torch.empty((B, 3, H, W), dtype=torch.float32, device=dev), torch.empty((B, 1, H, W), dtype=torch.uint8, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    normal, mask, nv = out
+    assert normal.dtype == torch.float32 and tuple(normal.shape) == (B, 3, H, W) and normal.is_contiguous(), (normal.dtype, tuple(normal.shape))
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == (B, 1, H, W) and mask.is_contiguous(), (mask.dtype, tuple(mask.shape))
+    assert nv.dtype == torch.int32 and tuple(nv.shape) == (B,) and nv.is_contiguous(), (nv.dtype, tuple(nv.shape))
+    desc = _lib.NormalGtDesc()
+    desc.batch, desc.height, desc.width, desc.raw_dtype = B, H, W, _NORMAL_GT_DTYPES[r.dtype]
+    with on_device_of(r):
+        _check_cuda(r, normal, mask, nv)
+        check(_lib.load().e2eft_normal_gt_prepare(C.byref(desc), _ptr(r), _ptr(normal), _ptr(mask), _ptr(nv), _stream()))
+    mb = mask.view(torch.bool)
+    return (normal[0], mb[0], nv[0]) if squeeze else (normal, mb, nv)
+
+
+_RGB_LAYOUTS = {"hwc": _lib.RGB_HWC, "chw": _lib.RGB_CHW}
+
+
+def dsine_rgb_requantize(rgb_u8, layout="hwc", out=None, workspace=None):
+    """the image DSINE's benchmark mode hands to the pipeline (csrc/normalprep.hip, include/e2eft.h e2eft_dsine_rgb_requantize): rgb_u8 uint8 [B,H,W,3]
+    (or one image [H,W,3]) as decoded -> normalised with the ImageNet constants, stretched to the tensor's own minimum and maximum over all channels
+    and truncated to uint8 again (test.py:59-65; NOT the identity: every channel is stretched differently).  layout "hwc": [B,H,W,3], what
+    Image.fromarray takes; "chw": [B,3,H,W], what the pipelines accept as a tensor.  An image with one single normalised value gives zeros (the
+    reference divides by zero).  out: an existing uint8 tensor of the output's shape; workspace: int32 [6 * B] (allocated when None; pass one under
+    graph capture to keep it out of the graph's pool).  No host synchronisation."""
+    if layout not in _RGB_LAYOUTS:
+        raise ValueError("dsine_rgb_requantize: layout must be one of %s, got %r" % (sorted(_RGB_LAYOUTS), layout))
+    squeeze = rgb_u8.dim() == 3
+    r = rgb_u8[None] if squeeze else rgb_u8
+    if r.dim() != 4 or r.shape[-1] != 3:
+        raise ValueError("dsine_rgb_requantize: rgb_u8 must be [H,W,3] or [B,H,W,3]; got %s" % (tuple(rgb_u8.shape),))
+    if r.dtype != torch.uint8:
+        raise TypeError("dsine_rgb_requantize: rgb_u8 must be uint8, got %s" % r.dtype)
+    if r.numel() == 0:
+        raise ValueError("dsine_rgb_requantize: empty image %s" % (tuple(rgb_u8.shape),))
+    r = r.contiguous()
+    B, H, W, _ = r.shape
+    dev = r.device
+    shape = (B, H, W, 3) if layout == "hwc" else (B, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    o = out[None] if squeeze and out.dim() == 3 else out
+    assert o.dtype == torch.uint8 and tuple(o.shape) == shape and o.is_contiguous(), (o.dtype, tuple(o.shape))
+    if o.data_ptr() == r.data_ptr():
+        raise ValueError("dsine_rgb_requantize: out must not be the input")
+    if workspace is None:
+        workspace = torch.empty((_lib.DSINE_RGB_WS_INTS * B,), dtype=torch.int32, device=dev)
+    assert workspace.dtype == torch.int32 and workspace.numel() >= _lib.DSINE_RGB_WS_INTS * B and workspace.is_contiguous(), (workspace.dtype, tuple(workspace.shape))
+    desc = _lib.DsineRgbDesc()
+    desc.batch, desc.height, desc.width, desc.out_layout = B, H, W, _RGB_LAYOUTS[layout]
+    with on_device_of(r):
+        _check_cuda(r, o, workspace)
+        check(_lib.load().e2eft_dsine_rgb_requantize(C.byref(desc), _ptr(r), _ptr(o), _ptr(workspace), _stream()))
+    return o[0] if squeeze else o

@@ -606,6 +606,40 @@ typedef struct {
 } e2eft_depth_gt_desc;
 int e2eft_depth_gt_prepare(const e2eft_depth_gt_desc* desc, const void* raw, const uint8_t* ext_mask, float* depth, uint8_t* mask, int32_t* n_valid,
                            void* stream);
+/* The surface-normal benchmarks' ground truth (what DSINE/data/datasets/{nyuv2,scannet,ibims,sintel}/__init__.py and ToTensor,
+ * DSINE/data/augmentations/basic.py:68-84, do to a normal file after decoding it), for a batch of rasters raw [batch][height][width][3] (R, G, B
+ * interleaved) of raw_dtype in DEVICE memory, contiguous, in one launch:
+ *   E2EFT_NORMAL_GT_U8 (NYUv2, ScanNet: PNG)     mask = r + g + b > 0 (integer sum); normal = (float(u8) / 255.0f) * 2.0f - 1.0f in fp32;
+ *   E2EFT_NORMAL_GT_F32 (iBims-1, Sintel: EXR)   mask = sqrtf((r r + g g) + b b) > 0.5f in fp32, np.linalg.norm's order of additions (a NaN is
+ *                                                invalid); the values pass through bit for bit, NaN payloads included.
+ * normal fp32 [batch][3][height][width] (planar), mask uint8 (0 / 1) [batch][1][height][width], n_valid int32 [batch] = the sum of each frame's mask,
+ * cleared on the stream and accumulated with one integer atomic per block (exact in any order: bit-reproducible).  Rows are read with 16-byte loads
+ * from their aligned chunks whatever 3 * width is; uint8 raw needs no alignment, float32 raw 4 bytes.  height <= 262140, batch <= 65535,
+ * height * width * 3 < 2^31.  No host synchronisation, no device read-back: capturable in a graph. */
+enum { E2EFT_NORMAL_GT_U8 = 0, E2EFT_NORMAL_GT_F32 = 1 };
+typedef struct {
+    int32_t batch, height, width;
+    int32_t raw_dtype; /* E2EFT_NORMAL_GT_* */
+} e2eft_normal_gt_desc;
+int e2eft_normal_gt_prepare(const e2eft_normal_gt_desc* desc, const void* raw, float* normal, uint8_t* mask, int32_t* n_valid, void* stream);
+/* The image round trip of DSINE's benchmark mode (DSINE/projects/dsine/test.py:59-65 after Normalize, DSINE/data/augmentations/basic.py:221-239), per
+ * image of a batch rgb uint8 [batch][height][width][3] as decoded, DEVICE memory, contiguous:
+ *   f(c, v) = (float(v) / 255.0f - mean_c) / std_c in fp32 (ImageNet mean 0.485, 0.456, 0.406 and std 0.229, 0.224, 0.225, rounded to fp32);
+ *   min, max of f over the whole image (all three channels); range = float(double(max) - double(min));
+ *   out = uint8(trunc(((f - min) / range) * 255.0f)), true fp32 divisions.
+ * The result is NOT the input: each channel is stretched differently.  out uint8: E2EFT_RGB_HWC [batch][height][width][3] or E2EFT_RGB_CHW
+ * [batch][3][height][width]; it must not be the input.  max == min (the reference divides by zero) gives zeros.  workspace: int32
+ * [E2EFT_DSINE_RGB_WS_INTS * batch], cleared on the stream: each channel's smallest and largest byte, found with one integer atomic each per
+ * channel and block (the smallest kept as the maximum of 255 - v, so that one clear to zero starts all six); pass 2 rebuilds the 768-entry (channel, byte) table per block from them.  16-byte loads and stores where an image's (and a
+ * plane's) addresses are 16-byte aligned, byte accesses elsewhere.  height * width * 3 < 2^31, batch <= 65535.  One memset and two launches on
+ * `stream`; no host synchronisation, no device read-back: capturable in a graph. */
+enum { E2EFT_RGB_HWC = 0, E2EFT_RGB_CHW = 1 };
+#define E2EFT_DSINE_RGB_WS_INTS 6
+typedef struct {
+    int32_t batch, height, width;
+    int32_t out_layout; /* E2EFT_RGB_* */
+} e2eft_dsine_rgb_desc;
+int e2eft_dsine_rgb_requantize(const e2eft_dsine_rgb_desc* desc, const uint8_t* rgb, uint8_t* out, int32_t* workspace, void* stream);
 /* Test-time ensembling of the n_img (<= 32) predictions of ONE image, fp32, replacing
  *   ensemble_depths   /root/reference/Marigold/marigold/util/ensemble.py:40-132 (called from marigold_pipeline.py:293-297;
  *                     twin GeoWizard/geowizard/utils/depth_ensemble.py:21-115)
