@@ -119,6 +119,8 @@ SIGNATURES = {
     "e2eft_f32_split_weight": (_I, [_P, _L, _I, _P, _P, _P]),
     "e2eft_f32_split2_cat": (_I, [_P, _I, _I, _P, _I, _I, _L, _P, _I, _P, _P]),
     "e2eft_f32_split2": (_I, [_P, _L, _I, _I, _P, _I, _P, _P]),
+    "e2eft_f32_split2_cols": (_I, [_P, _I, _I, _P, _I, _I, _L, _P, _I, _P, _P]),
+    "e2eft_f32_split_wgrad_finish": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
     "e2eft_conv2d_fwd_f32split_supported": (_I, [C.POINTER(ConvDesc)]),
     "e2eft_conv2d_fwd_f32split": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _Z, C.POINTER(C.c_int32), _P]),
     "e2eft_upconv2x_fwd_f32split_supported": (_I, [C.POINTER(ConvDesc)]),
@@ -271,7 +273,11 @@ class option:
         return False
 
 
+CALLS = [0]      # library calls checked so far: any of them may have written a buffer through its raw pointer, which no tensor's `_version` sees (ops.f32_split2)
+
+
 def check(rc):
+    CALLS[0] += 1
     if rc != 0:
         msg = load().e2eft_last_error()
         raise RuntimeError("libe2eft error %d: %s" % (rc, msg.decode() if msg else "?"))

@@ -6,9 +6,13 @@
 //     x0 = f16(x s),   x1 = f16(x s - x0)          (x s - x0 is representable in fp32: Sterbenz; both roundings to nearest even)
 // and a product of two such values is  x0 w0 + x0 w1 + x1 w0  up to 3 * 2^-22 |x w| (the dropped x1 w1 term is 2^-22) — each term is an exact f16 x f16 product
 // accumulated in fp32 by v_mfma_f32_32x32x16_f16.  That error is below what the fp32 accumulation of a K = 1152 ... 4608 reduction adds on EITHER pipe
-// (~sqrt(K) 2^-24), and it is measured, not argued: tests/test_f32split_gpu.py compares both routes with a float64 convolution.  Range: the scale comes from the
-// tensor's own maximum (one reduction pass, on the device: no host synchronisation), so nothing overflows; values more than 2^17 below the maximum lose RELATIVE
-// precision (their x1 is an f16 subnormal) but keep an ABSOLUTE error of 2^-39 of the maximum — invisible in a sum of products.
+// (~sqrt(K) 2^-24), and it is measured, not argued: tests/test_f32split_gpu.py compares both routes with a float64 convolution (bar: 1.5 x the fp32 instruction's
+// error; measured 0.4 - 1.16 x).  Range: the scale comes from the tensor's own maximum (one reduction pass, on the device: no host synchronisation), so nothing
+// overflows; values more than 2^17 below the maximum lose RELATIVE precision (their x1 is an f16 subnormal) and keep an ABSOLUTE error of 2^-39 of the maximum;
+// below 2^-39 of it they vanish.  Forward and data-gradient products reduce over the channels and live with that: per output element
+//     err <= 2^-37 amax(X) sum|w| + 2^-20 sum|x w| + the accumulation error        (tests/test_f32split_range_gpu.py)
+// so an output that is small beside an outlier elsewhere in the tensor is only that accurate.  A WEIGHT GRADIENT separates per channel and gets one scale per
+// channel of each operand (e2eft_f32_split2_cols / e2eft_f32_split_wgrad_finish below): every entry keeps the 2^-22 split relative to its own two columns.
 //   e2eft_f32_split2            x fp32 [pixels][c]  ->  planes f16 [pixels][x0 (c) | x1 (c)],  scale[1] = s, scale[2] = 1 / s
 //   e2eft_conv2d_fwd_f32split   the 3x3 / stride-1 / pad-1 convolution of such planes with weights split the same way on the host (once per weight):
 //                               igemm6_kernel<f16, ..., F32O> — K runs over the blocks (x0, w0), (x0, w1), (x1, w0); fp32 bias / residual / output / statistics.
@@ -84,6 +88,105 @@ __global__ __launch_bounds__(256) void split2_f16_kernel(long pixels, int c, int
         st16(planes + pix * ldp + coff + ch, p0);
         st16(planes + pix * ldp + ctot + coff + ch, p1);
         if (third) st16(planes + pix * ldp + 2 * ctot + coff + ch, p0);
+    }
+}
+
+// ---- per-channel scales: the operands of a weight gradient.  dW[co][tap][ci] = sum_pixels dY[.][co] X[.][ci] separates per output channel and per input channel, so
+// each column of dY and of X gets its OWN power-of-two scale and the result is scaled back by the outer product of the inverses: every column keeps the full 2^-22
+// split whatever the other columns (or one outlier elsewhere in the tensor) hold.
+// |x| maxima per column of an fp32 [pixels][ldx] tensor's first c columns (c % 4 == 0) into amax_bits[0, c).  gridDim.x * 256 is a multiple of c / 4 (the host rounds
+// it), so a thread keeps ONE group of four columns through its stride loop; threads of a workgroup that share a group meet in LDS, then one atomic per column and
+// workgroup, as contiguous 256-byte wave instructions
+__global__ __launch_bounds__(256) void col_absmax_f32_kernel(long pixels, int c, int ldx, const float* __restrict__ x, unsigned* __restrict__ amax_bits) {
+    __shared__ unsigned smax[1024];
+    const int c4 = c >> 2;
+    const int nslot = c4 < 256 ? c4 : 256;                   // distinct column groups in this workgroup
+    for (int i = threadIdx.x; i < 4 * nslot; i += 256) smax[i] = 0u;
+    __syncthreads();
+    const long first = (long)blockIdx.x * 256 + threadIdx.x;
+    const int cg = (int)(first % c4);
+    const long pstep = (long)gridDim.x * 256 / c4;
+    const float* xc = x + cg * 4;
+    floatx4 m = {0.f, 0.f, 0.f, 0.f};
+    auto fold = [&](const floatx4& v) {                      // (fmaxf drops NaNs, as in absmax_f32_kernel)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], fabsf(v[j]));
+    };
+    long pix = first / c4;
+    for (; pix + 3 * pstep < pixels; pix += 4 * pstep) {     // four independent 16-byte loads in flight per thread
+        const floatx4 v0 = *reinterpret_cast<const floatx4*>(xc + pix * ldx), v1 = *reinterpret_cast<const floatx4*>(xc + (pix + pstep) * ldx);
+        const floatx4 v2 = *reinterpret_cast<const floatx4*>(xc + (pix + 2 * pstep) * ldx), v3 = *reinterpret_cast<const floatx4*>(xc + (pix + 3 * pstep) * ldx);
+        fold(v0); fold(v1); fold(v2); fold(v3);
+    }
+    for (; pix < pixels; pix += pstep) fold(*reinterpret_cast<const floatx4*>(xc + pix * ldx));
+    const int slot = (int)threadIdx.x % nslot;               // threads of one group: threadIdx.x equal modulo c4 (only when c4 < 256)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (m[j] > 0.f) atomicMax(&smax[4 * slot + j], __float_as_uint(m[j]));
+    __syncthreads();
+    const long col0 = ((long)blockIdx.x * 256 % c4) * 4;     // slot 0's first column
+    for (int i = threadIdx.x; i < 4 * nslot; i += 256)
+        if (smax[i] != 0u) atomicMax(amax_bits + (int)((col0 + i) % c), smax[i]);
+}
+
+// split2_f16_kernel under per-column scales: column ch of this source is scaled by split_scale(amax_bits[coff + ch]); the first workgroup leaves the inverse
+// scales in inv_out[coff + ch].  gridDim.x * 256 is a multiple of c / 8: a thread's eight scales stay in registers
+__global__ __launch_bounds__(256) void split2_f16_cols_kernel(long pixels, int c, int ldx, int ldp, int coff, int ctot, const float* __restrict__ x, f16* __restrict__ planes,
+                                                              const unsigned* __restrict__ amax_bits, float* __restrict__ inv_out) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < c; i += 256) {
+            float s, inv;
+            split_scale(amax_bits[coff + i], s, inv);
+            inv_out[coff + i] = inv;
+        }
+    const int c8 = c >> 3;
+    const long first = (long)blockIdx.x * 256 + threadIdx.x;
+    const int ch = (int)(first % c8) * 8;
+    const long pstep = (long)gridDim.x * 256 / c8;
+    float s[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float inv;
+        split_scale(amax_bits[coff + ch + e], s[e], inv);
+    }
+    for (long pix = first / c8; pix < pixels; pix += pstep) {
+        const floatx4 a = *reinterpret_cast<const floatx4*>(x + pix * ldx + ch);
+        const floatx4 b = *reinterpret_cast<const floatx4*>(x + pix * ldx + ch + 4);
+        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        Vec16<f16> p0, p1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float t = v[e] * s[e];
+            const f16 h0 = (f16)t;                      // round to nearest even
+            p0.e[e] = h0;
+            p1.e[e] = (f16)(t - (float)h0);             // exact difference, rounded once
+        }
+        st16(planes + pix * ldp + coff + ch, p0);
+        st16(planes + pix * ldp + ctot + coff + ch, p1);
+    }
+}
+
+// out[co][tap][ci] = (t0 + t1 + t2) * inv_dy[co] * inv_x[ci]: the three partial gradients of the split operands, scaled back — exactly, all scales being powers of two.
+// The two exponents are added as integers and applied in two halves of the same sign, so every intermediate lies between the sum and the result: nothing overflows
+// or is flushed on the way where the result itself is a normal fp32 value (|exponent| <= 100 each: split_scale).  out may be t0.
+__global__ __launch_bounds__(256) void wgrad_unscale_kernel(long rows, int n, int cin, const float* t0, const float* t1, const float* t2,
+                                                            const float* __restrict__ inv_dy, const float* __restrict__ inv_x, float* out) {
+    const int n4 = n >> 2;
+    const long total = rows * n4;
+    for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
+        const long co = it / n4;
+        const int ci = (int)((it - co * n4) * 4 % cin);
+        const floatx4 a = *reinterpret_cast<const floatx4*>(t0 + it * 4), b = *reinterpret_cast<const floatx4*>(t1 + it * 4), d = *reinterpret_cast<const floatx4*>(t2 + it * 4);
+        const floatx4 ix = *reinterpret_cast<const floatx4*>(inv_x + ci);
+        const int ea = (int)((__float_as_uint(inv_dy[co]) >> 23) & 0xffu) - 127;
+        floatx4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = ea + (int)((__float_as_uint(ix[j]) >> 23) & 0xffu) - 127;
+            const int h = k >> 1;
+            r[j] = ((a[j] + b[j]) + d[j]) * __uint_as_float((unsigned)(127 + h) << 23) * __uint_as_float((unsigned)(127 + k - h) << 23);
+        }
+        *reinterpret_cast<floatx4*>(out + it * 4) = r;
     }
 }
 
@@ -165,6 +268,52 @@ extern "C" int e2eft_f32_split2_cat(const float* x1, int32_t c1, int32_t ldx1, c
     }
     tag_kernel("split2_f16_kernel");
     return check_launch("f32_split2_cat");
+}
+
+// the planes of [x1 (c1) | x2 (c2)] (x2 null, c2 = 0: one source) under per-COLUMN power-of-two scales, for the operands of a weight gradient:
+// planes [pixels][x1_0 | x2_0 | x1_1 | x2_1] as e2eft_f32_split2_cat's; colscale: 2 (c1 + c2) device floats — [0, c1 + c2) workspace (the maxima),
+// [c1 + c2, 2 (c1 + c2)) the inverse scales 1 / s[column] on return.  Two launches per source, no host read.
+extern "C" int e2eft_f32_split2_cols(const float* x1, int32_t c1, int32_t ldx1, const float* x2, int32_t c2, int32_t ldx2, int64_t pixels, void* planes, int32_t ldp,
+                                     float* colscale, void* stream) {
+    E2EFT_REQUIRE(x1 && planes && colscale && pixels > 0 && (x2 != nullptr) == (c2 != 0), "f32_split2_cols: null pointer / empty tensor");
+    E2EFT_REQUIRE(c1 > 0 && c1 % 8 == 0 && c2 >= 0 && c2 % 8 == 0 && ldx1 >= c1 && ldx1 % 4 == 0 && (!x2 || (ldx2 >= c2 && ldx2 % 4 == 0)) && ldp >= 2 * (c1 + c2) && ldp % 8 == 0,
+                  "f32_split2_cols: c1=%d c2=%d ldx1=%d ldx2=%d ldp=%d", c1, c2, ldx1, ldx2, ldp);
+    E2EFT_REQUIRE(al16(x1) && al16(x2) && al16(planes) && ((uintptr_t)colscale & 3) == 0, "f32_split2_cols: alignment");
+    hipStream_t s = (hipStream_t)stream;
+    const int ctot = c1 + c2;
+    if (hipMemsetAsync(colscale, 0, sizeof(float) * ctot, s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2_cols: memset failed");
+    const float* xs[2] = {x1, x2};
+    const int cs[2] = {c1, c2}, lds[2] = {ldx1, ldx2}, offs[2] = {0, c1};
+    // workgroups for `units` work items of `per` columns groups per pixel: at most `cap`, a multiple of what makes gridDim.x * 256 a multiple of `per`
+    auto grid = [](long units, int per, long cap) -> unsigned {
+        int g = per, r = 256;
+        while (r) { const int t = g % r; g = r; r = t; }      // gcd(per, 256)
+        const long mult = per / g;
+        long nb = (units + 255) / 256;
+        nb = nb > cap ? cap : nb < 1 ? 1 : nb;
+        return (unsigned)((nb + mult - 1) / mult * mult);
+    };
+    unsigned* bits = reinterpret_cast<unsigned*>(colscale);
+    for (int i = 0; i < 2 && cs[i]; ++i)
+        hipLaunchKernelGGL(col_absmax_f32_kernel, dim3(grid(pixels * (cs[i] / 4) / 4, cs[i] / 4, 1024)), dim3(256), 0, s, (long)pixels, cs[i], lds[i], xs[i], bits + offs[i]);
+    for (int i = 0; i < 2 && cs[i]; ++i)
+        hipLaunchKernelGGL(split2_f16_cols_kernel, dim3(grid(pixels * (cs[i] / 8), cs[i] / 8, 65536)), dim3(256), 0, s, (long)pixels, cs[i], lds[i], ldp, offs[i], ctot, xs[i],
+                           (f16*)planes, bits, colscale + ctot);
+    return check_launch("f32_split2_cols");
+}
+
+// the weight gradient of two such operands: out [cout][n = taps * cin] = (t0 + t1 + t2) / (s_dy[co] s_x[ci]) for the 16-bit kernel's three results on the planes
+// (d0, x0), (d0, x1), (d1, x0) — dense fp32 [cout][n] each, 16-byte aligned; inv_dy [cout], inv_x [cin]: the inverse scales e2eft_f32_split2_cols left.  out may be t0.
+extern "C" int e2eft_f32_split_wgrad_finish(const float* t0, const float* t1, const float* t2, int64_t cout, int32_t taps, int32_t cin, const float* inv_dy, const float* inv_x,
+                                            float* out, void* stream) {
+    E2EFT_REQUIRE(t0 && t1 && t2 && inv_dy && inv_x && out && cout > 0 && taps > 0, "f32_split_wgrad_finish: null pointer / empty gradient");
+    E2EFT_REQUIRE(cin > 0 && cin % 4 == 0 && (long)taps * cin < 2147483647L, "f32_split_wgrad_finish: cin=%d must be a multiple of 4", cin);
+    E2EFT_REQUIRE(al16(t0) && al16(t1) && al16(t2) && al16(out) && al16(inv_x), "f32_split_wgrad_finish: pointers must be 16-byte aligned");
+    const int n = taps * cin;
+    long nb = (cout * (n / 4) + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    hipLaunchKernelGGL(wgrad_unscale_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (long)cout, n, cin, t0, t1, t2, inv_dy, inv_x, out);
+    return check_launch("f32_split_wgrad_finish");
 }
 
 // pure host arithmetic: would e2eft_conv2d_fwd_f32split take this launch (with 16-byte aligned pointers)?  desc: dtype E2EFT_F32, c1 = channels of the fp32

@@ -252,9 +252,11 @@ def _launch_with_stats(launch, out, want, images, rows_per_image, cout):
 def f32_split2(x, keep=False, x2=None):
     """fp32 NHWC [B,H,W,C] or row view [M,C] (C % 8 == 0) -> (planes f16 [..., 2C] = [x0 | x1] with x * s = x0 + x1 to 2^-22, scale workspace fp32 [4]: [1] = s, [2] = 1 / s).
     s is the power of two that brings the tensor's maximum into [2^14, 2^15), found on the device (csrc/f32split.hip).
-    keep: park the result on the tensor object (per version) — a gradient dY is split once for its data-gradient convolution AND its weight-gradient launches, and once
-    for the backward calls of two convolutions that receive the same dY object (a convolution hands its residual's gradient on as dY itself); only for short-lived
-    tensors (the planes live as long as x does).  x2 (NHWC only): a second source — the planes are then those of cat(x, x2) along the channels, under one scale."""
+    keep: park the result on the tensor object; a second call returns it only while x has the same `_version` AND no library call has been made since — the
+    library's kernels write through raw pointers (ops.add(out=), ops.copy_scale, ops.cast_, ...) and bump no version, so any launch in between may have refilled x.
+    For a caller that splits one tensor for several consumers before it launches any of them; nothing in the package does at present (a weight gradient takes
+    per-channel planes of dY, f32_split2_cols, and the data gradient of the same dY launches its convolution right behind its split).  The planes live as long as x
+    does.  x2 (NHWC only): a second source — the planes are then those of cat(x, x2) along the channels, under one scale."""
     _check_cuda(x, x2)
     Cc = x.shape[-1]
     assert x.dtype == torch.float32 and Cc % 8 == 0
@@ -264,7 +266,7 @@ def f32_split2(x, keep=False, x2=None):
         B, H, W, _ = x.shape
         pixels, ld, label = B * H * W, _nhwc_ld(x), "split2 B%d %dx%d C%d" % (B, H, W, Cc)
     ent = getattr(x, "_e2eft_planes", None) if keep else None
-    if ent is not None and ent[0] == x._version:
+    if ent is not None and ent[0] == (x._version, _lib.CALLS[0]):
         return ent[1], ent[2]
     c2 = 0 if x2 is None else x2.shape[3]
     planes = torch.empty(tuple(x.shape[:-1]) + (2 * (Cc + c2),), dtype=torch.float16, device=x.device)
@@ -277,8 +279,24 @@ def f32_split2(x, keep=False, x2=None):
         with _timed("f32split", 0.0, 12.0 * pixels * Cc, label=label, launches=2):
             check(_lib.load().e2eft_f32_split2(_ptr(x), pixels, Cc, ld, _ptr(planes), 2 * Cc, _ptr(scale), _stream()))
     if keep:
-        x._e2eft_planes = (x._version, planes, scale)
+        x._e2eft_planes = ((x._version, _lib.CALLS[0]), planes, scale)
     return planes, scale
+
+
+def f32_split2_cols(x, x2=None):
+    """fp32 NHWC x (x2: cat(x, x2) along the channels) -> (planes f16 [..., 2C] = [x0 | x1], inverse scales fp32 [C]): f32_split2 under one power-of-two scale per
+    CHANNEL, found on the device (e2eft_f32_split2_cols) — the operands of a weight gradient, whose algebra separates per channel (conv2d_wgrad)."""
+    _check_cuda(x, x2)
+    B, H, W, Cc = x.shape
+    c2 = 0 if x2 is None else x2.shape[3]
+    assert x.dtype == torch.float32 and Cc % 8 == 0 and c2 % 8 == 0 and (x2 is None or (tuple(x2.shape[:3]) == (B, H, W) and x2.dtype == torch.float32))
+    ctot, pixels = Cc + c2, B * H * W
+    planes = torch.empty((B, H, W, 2 * ctot), dtype=torch.float16, device=x.device)
+    cs = torch.empty(2 * ctot, dtype=torch.float32, device=x.device)
+    with _timed("f32split", 0.0, 12.0 * pixels * ctot, label="split2 cols B%d %dx%d C%d" % (B, H, W, ctot), launches=2 if x2 is None else 4):
+        check(_lib.load().e2eft_f32_split2_cols(_ptr(x), Cc, _nhwc_ld(x), _ptr(x2), c2, _nhwc_ld(x2) if x2 is not None else 0, pixels, _ptr(planes), 2 * ctot, _ptr(cs),
+                                                _stream()))
+    return planes, cs[ctot:]
 
 
 def f32_split_weight(w_packed, taps, c):
@@ -384,15 +402,14 @@ def _f32split_conv_launch(d, planes, scale, wsplit, bias, residual, out, want, l
     return out
 
 
-def _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, geom=(3, 3, 1, (1, 1, 1, 1)), x2=None, keep_planes=False):
-    """An fp32 convolution of x (x2: of cat(x, x2) — one pair of planes, one scale) through e2eft_conv2d_fwd_f32split, or None when the route does not take it.
-    keep_planes: see f32_split2."""
+def _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, geom=(3, 3, 1, (1, 1, 1, 1)), x2=None):
+    """An fp32 convolution of x (x2: of cat(x, x2) — one pair of planes, one scale) through e2eft_conv2d_fwd_f32split, or None when the route does not take it."""
     c1 = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
     d = _f32split_conv_desc(*x.shape[:3], c1, w_packed, bias, cout, residual, alpha, out, geom, (x, x2))
     if d is None:
         return None
     wsplit = f32_split_weight(w_packed, geom[0] * geom[1], c1)
-    planes, scale = f32_split2(x, keep=keep_planes, x2=x2)
+    planes, scale = f32_split2(x, x2=x2)
     return _f32split_conv_launch(d, planes, scale, wsplit, bias, residual, out, want, label)
 
 
@@ -1047,6 +1064,27 @@ WGRAD_DIRECT = True   # tests / A-B: False keeps every weight gradient on the tr
 WGRAD_DIRECT_FP32 = True   # round 6: strict-fp32 weight gradients straight from the NHWC tensors too (csrc/wgrad.hip::wgrad32_kernel); False: the round-5 path
 
 
+def _wgrad_split_serves(dy, x, cin, cout, kh, kw, stride, pad):
+    """pure host arithmetic: does the 16-bit kernel serve the f16 split planes of this fp32 weight gradient (dY planes of pixel stride 2 c0, ONE source of cin channels
+    at pixel stride 2 cin), in every launch of conv2d_wgrad's cut along the batch?  Asked before anything is split: a shape it refuses goes to wgrad32_kernel."""
+    B, H, W, _ = x.shape
+    c0 = dy.shape[3]
+    per_img = max(dy.shape[1] * dy.shape[2] * 2 * c0, H * W * 2 * cin) * 2
+    step = max(1, min(B, (0xFFFF0000 - 1) // max(per_img, 1), ((1 << 24) - 1) // max(dy.shape[1] * dy.shape[2], 1)))
+    pt, pb, pl, pr = pad
+    for nb in {step, B % step or step}:
+        d = ConvDesc()
+        d.dtype = _lib.F16
+        d.batch, d.hin, d.win, d.hl, d.wl = nb, H, W, H, W
+        d.c1, d.ldx1, d.c2, d.ldx2 = cin, 2 * cin, 0, 0
+        d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
+        d.hout, d.wout = dy.shape[1], dy.shape[2]
+        d.cout, d.alpha = cout, 1.0
+        if _lib.load().e2eft_conv2d_wgrad_workspace_bytes(C.byref(d), 2 * c0) == 0:
+            return False
+    return True
+
+
 def conv2d_wgrad(dy, x, x2, cout, kh, kw, stride, pad, alpha, out=None):
     """Weight gradient straight from the NHWC tensors (csrc/wgrad.hip): dy [B,hout,wout,>=cout] (pixel-dense), x [B,H,W,c1], x2 optional second
     concat source -> fp32 [cout, kh*kw*(c1+c2)] (OHWI rows), or None when the kernel does not serve the problem (the caller falls back).
@@ -1059,25 +1097,29 @@ def conv2d_wgrad(dy, x, x2, cout, kh, kw, stride, pad, alpha, out=None):
     _check_cuda(dy, x, x2)
     cin = x.shape[3] + (x2.shape[3] if x2 is not None else 0)
     if (dy.dtype == torch.float32 and cin % 64 == 0 and cout % 64 == 0 and _lib.load().e2eft_get_option(_lib.OPT_F32_SPLIT) == 1
-            and f32split_operands_ok((dy, x, x2))):
-        # fp32 on the f16 matrix pipe (csrc/f32split.hip): dy s_dy = d0 + d1, x s_x = x0 + x1 (two-term f16 splits, exact to 2^-22); the gradient is the sum of the
-        # 16-bit kernel's results for (d0, x0), (d0, x1), (d1, x0), scaled back by the two device scalars — three launches at the f16 rate instead of one at the fp32 rate
-        dyp, sdy = f32_split2(dy, keep=True)          # (the data-gradient convolution of the same dY has usually split it already: autograd._Conv2dFn.backward)
-        xp, sx = f32_split2(x, x2=x2)                 # (two sources: the planes of their concatenation — the 16-bit kernel then sees ONE source of c1 + c2 channels)
+            and f32split_operands_ok((dy, x, x2)) and _wgrad_split_serves(dy, x, cin, cout, kh, kw, stride, pad)):
+        # fp32 on the f16 matrix pipe (csrc/f32split.hip): dy[:, co] s_dy[co] = d0 + d1, x[:, ci] s_x[ci] = x0 + x1 (two-term f16 splits, exact to 2^-22, one power-of-two
+        # scale per CHANNEL: dW[co, tap, ci] only ever multiplies column co of dY with column ci of X, so every entry keeps that precision relative to its own two
+        # columns); the gradient is the sum of the 16-bit kernel's results for (d0, x0), (d0, x1), (d1, x0), scaled back by the outer product of the inverse scales in
+        # one pass — three launches at the f16 rate instead of one at the fp32 rate.  (The data-gradient convolution of the same dY reduces OVER the channels: it keeps
+        # its own per-tensor planes.)
+        dyp, idy = f32_split2_cols(dy)
+        xp, ix = f32_split2_cols(x, x2)               # (two sources: the planes of their concatenation — the 16-bit kernel then sees ONE source of c1 + c2 channels)
         c0, c1 = dy.shape[3], cin
-        r = None
+        ts = []
         for (a_, b_) in ((dyp[..., :c0], xp[..., :c1]), (dyp[..., :c0], xp[..., c1:]), (dyp[..., c0:], xp[..., :c1])):
             t = conv2d_wgrad(a_, b_, None, cout, kh, kw, stride, pad, alpha)
             if t is None:
-                r = None
-                break
-            r = t if r is None else r.add_(t)
-        if r is not None:
-            r = r.mul_(sdy[2] * sx[2])
-            if out is not None:
-                out.view(r.shape).copy_(r)
-                return out.view(r.shape)
-            return r
+                raise RuntimeError("conv2d_wgrad: the 16-bit kernel refused planes that _wgrad_split_serves accepted")
+            ts.append(t)
+        direct = out is not None and out.data_ptr() % 16 == 0      # (a slot of the flat gradient buffer may start off a 16-byte boundary: one copy then)
+        r = out.view(ts[0].shape) if direct else ts[0]
+        with _timed("f32split", 0.0, 16.0 * cout * kh * kw * cin, label="wgrad finish %d x %d" % (cout, kh * kw * cin)):
+            check(_lib.load().e2eft_f32_split_wgrad_finish(_ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), cout, kh * kw, cin, _ptr(idy), _ptr(ix), _ptr(r), _stream()))
+        if out is not None and not direct:
+            out.view(r.shape).copy_(r)
+            return out.view(r.shape)
+        return r
     B = x.shape[0]
     lddy = _nhwc_ld(dy)
     es = dy.element_size()
@@ -1152,7 +1194,7 @@ def conv2d_dgrad(dy, w_dgrad, x_shape, c2, kh, kw, stride, pad, up_to, alpha):
     if (dy.dtype == torch.float32 and ((kh, kw, stride, tuple(pad)) == (3, 3, 1, (1, 1, 1, 1)) or (kh, kw, stride, tuple(pad)) == (1, 1, 1, (0, 0, 0, 0)))
             and up_to is None and cop % 64 == 0 and cin % 8 == 0):
         # the data gradient of a 3x3 / stride-1 / pad-1 (or 1x1) convolution IS such a convolution of dY with the flipped, transposed weights: the f16-split route of conv2d
-        if _conv2d_f32split(dy, w_dgrad, None, cin, None, alpha, dx, False, label, geom=(kh, kw, 1, tuple(pad)), keep_planes=True) is not None:
+        if _conv2d_f32split(dy, w_dgrad, None, cin, None, alpha, dx, False, label, geom=(kh, kw, 1, tuple(pad))) is not None:
             return dx
     with _timed("igemm", 2.0 * B * hl * wl * cin * kh * kw * cop, label=label):
         check(_lib.load().e2eft_conv2d_dgrad(C.byref(d), _ptr(dy), _nhwc_ld(dy), cop, _ptr(w_dgrad), w_dgrad.shape[1], _ptr(dx), _nhwc_ld(dx),

@@ -185,6 +185,16 @@ int e2eft_f32_split_weight(const float* w, int64_t rows, int32_t c, void* w_spli
 /* the channel concatenation [x1 (c1) | x2 (c2)] as one pair of planes under one scale: planes [pixels][x1_0 | x2_0 | x1_1 | x2_1] (the UNet's two-source convolutions) */
 int e2eft_f32_split2_cat(const float* x1, int32_t c1, int32_t ldx1, const float* x2, int32_t c2, int32_t ldx2, int64_t pixels, void* planes, int32_t ldp,
                          float* scale, void* stream);
+/* the operands of a weight gradient, split under per-COLUMN power-of-two scales: dW[co][tap][ci] = sum over pixels of dY[.][co] X[.][ci] separates per output and per input
+ * channel, so each column of dY and of [x1 | x2] is scaled by its own maximum and keeps the full 2^-22 split whatever the rest of the tensor holds.  x2 may be null
+ * (c2 = 0).  planes as e2eft_f32_split2_cat's; colscale: 2 (c1 + c2) device floats, [0, c1 + c2) workspace, [c1 + c2, 2 (c1 + c2)) = 1 / s[column] on return.
+ * e2eft_f32_split_wgrad_finish: out [cout][taps * cin] = (t0 + t1 + t2) * inv_dy[co] * inv_x[ci] for the 16-bit e2eft_conv2d_wgrad results t0, t1, t2 (dense fp32, 16-byte
+ * aligned) on the planes (d0, x0), (d0, x1), (d1, x0): exact, and ordered so that no intermediate overflows or is flushed where the result is a normal fp32 value.
+ * out may be t0.  No host synchronisation in either call. */
+int e2eft_f32_split2_cols(const float* x1, int32_t c1, int32_t ldx1, const float* x2, int32_t c2, int32_t ldx2, int64_t pixels, void* planes, int32_t ldp,
+                          float* colscale, void* stream);
+int e2eft_f32_split_wgrad_finish(const float* t0, const float* t1, const float* t2, int64_t cout, int32_t taps, int32_t cin, const float* inv_dy, const float* inv_x,
+                                 float* out, void* stream);
 int e2eft_conv2d_fwd_f32split_supported(const E2eftConvDesc* d);
 int e2eft_conv2d_fwd_f32split(const E2eftConvDesc* d, const void* planes, const float* scale, const void* w_split, const float* w_inv_scale, const float* bias,
                               const float* residual, float* out, float* gn_partial, size_t gn_partial_bytes, int32_t* slab_rows, void* stream);

@@ -42,3 +42,32 @@ def pack_conv_weight(w, dtype, dev, cin_pad=None):
     if cin_pad is not None and cin_pad != Ci:
         w = torch.nn.functional.pad(w, (0, cin_pad - Ci))
     return w.reshape(Co, -1).contiguous().to(dtype).to(dev)
+
+
+def chan_err_wgrad(got, ref, dy, x, taps):
+    """Channel-aware error of a weight gradient: max over entries of |got - ref| / (||dY[..., co]||_2 * ||X[..., ci]||_2).  got, ref: [cout, taps * cin] in OHWI
+    order; dy [..., cout] and x [..., cin] channels-last, norms in float64 over all pixels.  The normaliser is invariant to any per-channel rescaling of either
+    operand and, unlike |ref| itself, never tiny through cancellation; all-zero channels are left out of the maximum."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    dy, x = dy.detach().double().cpu(), x.detach().double().cpu()
+    cout, cin = dy.shape[-1], x.shape[-1]
+    assert tuple(got.shape) == tuple(ref.shape) == (cout, taps * cin), (got.shape, ref.shape, cout, taps, cin)
+    ny = dy.reshape(-1, cout).square().sum(0).sqrt()
+    nx = x.reshape(-1, cin).square().sum(0).sqrt()
+    den = ny[:, None, None] * nx[None, None, :]
+    err = (got - ref).abs().view(cout, taps, cin)
+    live = (den > 0).expand_as(err)
+    if not live.any():
+        return 0.0
+    return (err[live] / den.expand_as(err)[live]).max().item()
+
+
+def chan_err_rows(got, ref):
+    """max over output channels (the LAST dimension) of max|err| in the channel / max|ref| in the channel: forward and data-gradient outputs, channels-last.
+    Channels whose reference is all zero are left out."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    c = ref.shape[-1]
+    e = (got - ref).abs().reshape(-1, c).max(0).values
+    m = ref.abs().reshape(-1, c).max(0).values
+    live = m > 0
+    return (e[live] / m[live]).max().item() if live.any() else 0.0
