@@ -88,7 +88,7 @@ DSINE_RGB_WS_INTS = 6                       # E2EFT_DSINE_RGB_WS_INTS
 
 
 # e2eft_set_option keys (include/e2eft.h)
-OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT = range(15)
+OPT_PERSISTENT, OPT_PERSISTENT_GRID, OPT_NARROW_CONV, OPT_NARROW_MFMA, OPT_IGEMM_GENERAL_OPERANDS, OPT_IGEMM2_WAVES, OPT_PATCH_CONV, OPT_THIN_INPUT_CONV, OPT_FUSED_NORM, OPT_ATTN_DMA, OPT_UPCONV_PHASES, OPT_PATCH_CONV_2X2, OPT_PERSISTENT_MIN_QROUNDS, OPT_GN_APPLY_ITERS, OPT_F32_SPLIT, OPT_F32_SPLIT_ATTN = range(16)
 
 _P = C.c_void_p
 _I = C.c_int32
@@ -126,6 +126,7 @@ SIGNATURES = {
     "e2eft_upconv2x_fwd_f32split_supported": (_I, [C.POINTER(ConvDesc)]),
     "e2eft_upconv2x_fwd_f32split": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _Z, C.POINTER(C.c_int32), _P]),
     "e2eft_gemm_f32split_supported": (_I, [C.POINTER(GemmDesc)]),
+    "e2eft_attn_f32split_supported": (_I, [C.POINTER(AttnDesc), _I]),
     "e2eft_gemm_f32split": (_I, [C.POINTER(GemmDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "e2eft_conv2d_fwd_normed": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, C.POINTER(C.c_int32), _P]),
     "e2eft_groupnorm_workspace_bytes": (_Z, [C.POINTER(GroupNormDesc)]),

@@ -497,7 +497,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
 
 }  // namespace e2eft
 
-namespace e2eft { int attn32_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream); }   // attn32.hip
+namespace e2eft {
+int attn32_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream);          // attn32.hip
+int attn_f32split_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream);   // attn_f32split.hip
+}
 using namespace e2eft;
 
 extern "C" int e2eft_attn_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, void* stream) {
@@ -511,7 +514,10 @@ extern "C" int e2eft_attn_fwd_lse(const E2eftAttnDesc* d, const void* q, const v
     E2EFT_REQUIRE(d->kv_nseg == 1 || d->kv_nseg == 2, "attn: kv_nseg must be 1 or 2");
     E2EFT_REQUIRE(d->kv_bmod > 0, "attn: kv_bmod");
     E2EFT_REQUIRE(d->scale > 0.f, "attn: scale must be positive");
-    if (d->dtype == E2EFT_F32) return attn32_fwd(d, q, k, v, out, lse, stream);      // strict fp32 on v_mfma_f32_32x32x2_f32: attn32.hip
+    if (d->dtype == E2EFT_F32) {
+        if (e2eft_attn_f32split_supported(d, 0) == 1) return attn_f32split_fwd(d, q, k, v, out, lse, stream);      // E2EFT_OPT_F32_SPLIT_ATTN: two-term f16 splits
+        return attn32_fwd(d, q, k, v, out, lse, stream);      // strict fp32 on v_mfma_f32_32x32x2_f32: attn32.hip
+    }
     const int w = d->heads * 64;
     E2EFT_REQUIRE(d->ldq >= w && d->ldk >= w && d->ldv >= w && d->ldo >= w, "attn: row strides smaller than heads*64");
     E2EFT_REQUIRE(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 4 == 0, "attn: row strides must be multiples of 8");

@@ -16,6 +16,7 @@
 // LDS tiles are [64 rows][68 floats]: 272-byte rows keep ds_read_b128 of 16 different rows conflict-free (row starts 4 dwords apart mod 64) and 16-byte alignment.
 // MFMA work per 32 x 32 (query, key) block: forward 2 x 32 instructions, backward 7 x 32; softmax VALU (one v_exp_f32 per score) is ~5 % beside them.
 #include "gfx950.h"
+#include "attn32.h"
 
 namespace e2eft {
 
@@ -24,32 +25,6 @@ constexpr int PITCH = 68;                 // floats per LDS row
 constexpr int TILEF = 64 * PITCH;         // floats per 64-row tile
 constexpr float LN2 = 0.6931471805599453f;
 }  // namespace a32
-
-struct Attn32Params {
-    const float* q;
-    const float* k;
-    const float* v;
-    float* out;
-    int batch, heads, nq, nk_seg, kv_nseg, kv_bmod, nk_total, nqb;
-    int ldq, ldk, ldv, ldo;
-    float c;        // scale * log2(e)
-    float* lse;     // optional [batch][heads][nq]: base-2 log-sum-exp of the scaled scores
-};
-
-struct Attn32BwdParams {
-    const float* q;
-    const float* k;
-    const float* v;
-    const float* dout;
-    const float* lse;
-    const float* dsum;
-    float* dq;
-    float* dk;
-    float* dv;
-    int batch, heads, nq, nk;
-    int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
-    float c, scale;
-};
 
 __device__ __forceinline__ floatx16 mma32(float a, float b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ floatx16 zero16() {
@@ -417,12 +392,12 @@ __global__ __launch_bounds__(256, 2) void attn32_bwd_dq_kernel(const Attn32BwdPa
 }
 
 // ---- host side (called from e2eft_attn_fwd_lse / e2eft_attn_bwd for dtype E2EFT_F32; argument checks common to all dtypes are done there) ----------------
-int attn32_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream) {
+int attn32_fwd_params(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, Attn32Params* pp) {
     const int w = d->heads * 64;
     E2EFT_REQUIRE(d->ldq >= w && d->ldk >= w && d->ldv >= w && d->ldo >= w && d->ldq % 4 == 0 && d->ldk % 4 == 0 && d->ldv % 4 == 0 && d->ldo % 4 == 0,
                   "attn (fp32): row strides must cover heads * 64 floats and keep 16-byte alignment");
     E2EFT_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0, "attn (fp32): pointers must be 16-byte aligned");
-    Attn32Params p;
+    Attn32Params& p = *pp;
     p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.out = (float*)out; p.lse = lse;
     p.batch = d->batch; p.heads = d->heads; p.nq = d->nq; p.nk_seg = d->nk_seg; p.kv_nseg = d->kv_nseg; p.kv_bmod = d->kv_bmod;
     p.nk_total = d->nk_seg * d->kv_nseg;
@@ -431,33 +406,55 @@ int attn32_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void*
     p.nqb = cdiv(d->nq, 128);
     const long blocks = (long)d->batch * d->heads * p.nqb;
     E2EFT_REQUIRE(blocks < 2147483647L, "attn (fp32): grid");
+    return E2EFT_OK;
+}
+
+int attn32_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream) {
+    Attn32Params p;
+    const int rc = attn32_fwd_params(d, q, k, v, out, lse, &p);
+    if (rc != E2EFT_OK) return rc;
+    const unsigned blocks = (unsigned)((long)d->batch * d->heads * p.nqb);
     hipStream_t s = (hipStream_t)stream;
-    if (d->kv_nseg > 1) hipLaunchKernelGGL((attn32_fwd_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((attn32_fwd_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    if (d->kv_nseg > 1) hipLaunchKernelGGL((attn32_fwd_kernel<true>), dim3(blocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attn32_fwd_kernel<false>), dim3(blocks), dim3(256), 0, s, p);
+    tag_kernel("attn32_fwd_kernel<%s>", d->kv_nseg > 1 ? "true" : "false");
     return check_launch("attn_fwd (fp32)");
 }
 
-int attn32_bwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, const void* out, const void* dout, int32_t lddo, const float* lse, void* dq,
-               int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, void* workspace, void* stream) {
+int attn32_bwd_params(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, const void* out, const void* dout, int32_t lddo, const float* lse,
+                      void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, void* workspace, Attn32BwdParams* pp) {
     const int w = d->heads * 64;
     E2EFT_REQUIRE(d->ldq >= w && d->ldk >= w && d->ldv >= w && d->ldo >= w && lddo >= w && lddq >= w && lddk >= w && lddv >= w, "attn_bwd (fp32): row strides");
     E2EFT_REQUIRE(d->ldq % 4 == 0 && d->ldk % 4 == 0 && d->ldv % 4 == 0 && d->ldo % 4 == 0 && lddo % 4 == 0 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0,
                   "attn_bwd (fp32): row strides must keep 16-byte alignment");
     E2EFT_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) == 0,
                   "attn_bwd (fp32): pointers must be 16-byte aligned");
-    Attn32BwdParams p;
+    Attn32BwdParams& p = *pp;
     p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.dout = (const float*)dout; p.lse = lse; p.dsum = (const float*)workspace;
     p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv;
     p.batch = d->batch; p.heads = d->heads; p.nq = d->nq; p.nk = d->nk_seg;
     p.ldq = d->ldq; p.ldk = d->ldk; p.ldv = d->ldv; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
     p.scale = d->scale;
     p.c = d->scale * 1.4426950408889634f;
-    hipStream_t s = (hipStream_t)stream;
+    return E2EFT_OK;
+}
+
+void attn32_bwd_prep(const E2eftAttnDesc* d, const void* out, const void* dout, int32_t lddo, float* dsum, hipStream_t s) {
     const long rows = (long)d->batch * d->nq;
     hipLaunchKernelGGL(attn32_bwd_prep_kernel, dim3((unsigned)cdiv(rows * d->heads, 256)), dim3(256), 0, s, rows, d->heads, d->ldo, lddo, d->nq, (const float*)out,
-                       (const float*)dout, (float*)workspace);
+                       (const float*)dout, dsum);
+}
+
+int attn32_bwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, const void* out, const void* dout, int32_t lddo, const float* lse, void* dq,
+               int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, void* workspace, void* stream) {
+    Attn32BwdParams p;
+    const int rc = attn32_bwd_params(d, q, k, v, out, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, workspace, &p);
+    if (rc != E2EFT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    attn32_bwd_prep(d, out, dout, lddo, (float*)workspace, s);
     hipLaunchKernelGGL(attn32_bwd_dkdv_kernel, dim3(cdiv(p.nk, 128), d->heads, d->batch), dim3(256), 0, s, p);
     hipLaunchKernelGGL(attn32_bwd_dq_kernel, dim3(cdiv(p.nq, 128), d->heads, d->batch), dim3(256), 0, s, p);
+    tag_kernel("attn32_bwd_prep_kernel + attn32_bwd_dkdv_kernel + attn32_bwd_dq_kernel");
     return check_launch("attn_bwd (fp32)");
 }
 

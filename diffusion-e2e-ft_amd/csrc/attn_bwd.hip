@@ -403,6 +403,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
 namespace e2eft {
 int attn32_bwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, const void* out, const void* dout, int32_t lddo, const float* lse, void* dq,
                int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, void* workspace, void* stream);   // attn32.hip
+int attn_f32split_bwd(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, const void* out, const void* dout, int32_t lddo, const float* lse,
+                      void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, void* workspace, void* stream);   // attn_f32split.hip
 }
 using namespace e2eft;
 
@@ -418,10 +420,11 @@ extern "C" int e2eft_attn_bwd(const E2eftAttnDesc* d, const void* q, const void*
     E2EFT_REQUIRE(d->dtype == E2EFT_F16 || d->dtype == E2EFT_BF16 || d->dtype == E2EFT_F32, "attn_bwd: dtype %d unsupported (head dim 64)", d->dtype);
     E2EFT_REQUIRE(d->batch > 0 && d->heads > 0 && d->nq > 0 && d->nk_seg > 0, "attn_bwd: geometry");
     E2EFT_REQUIRE(d->kv_nseg == 1 && d->kv_bmod == d->batch, "attn_bwd: joint (segmented) keys are not supported; concatenate k / v");
-    if (d->dtype == E2EFT_F32) {      // strict fp32: attn32.hip
+    if (d->dtype == E2EFT_F32) {      // attn32.hip (strict fp32), or attn_f32split.hip when E2EFT_OPT_F32_SPLIT_ATTN takes the shape
         E2EFT_REQUIRE(d->heads <= 65535 && d->batch <= 65535, "attn_bwd: grid");
         const size_t need32 = e2eft_attn_bwd_workspace_bytes(d);
         if (ws_bytes < need32) return fail(E2EFT_ERR_WORKSPACE, "attn_bwd: workspace %zu < %zu", ws_bytes, need32);
+        if (e2eft_attn_f32split_supported(d, 1) == 1) return attn_f32split_bwd(d, q, k, v, out, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, workspace, stream);
         return attn32_bwd(d, q, k, v, out, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, workspace, stream);
     }
     const int w = d->heads * 64;

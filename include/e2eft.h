@@ -34,7 +34,8 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: what this header (and e2eft_debug.h) declares is ALL it exports (tests/test_abi.py) */
 #pragma GCC visibility push(default)
 
-#define E2EFT_VERSION 119 /* 0.1.1: backward entry points; 111: test-time ensembling, CLIP towers, sample preparation */
+#define E2EFT_VERSION 119 /* 0.1.1: backward entry points; 111: test-time ensembling, CLIP towers, sample preparation; 119 later gained one export
+                             (e2eft_attn_f32split_supported) and one option (E2EFT_OPT_F32_SPLIT_ATTN) without a new number */
 
 enum {
     E2EFT_OK = 0,
@@ -70,7 +71,8 @@ enum {
     E2EFT_OPT_PERSISTENT_MIN_QROUNDS = 12, /* 2 (default since round 6, was 8): the persistent kernels (igemm5 / igemm6) take a launch of at least n / 4 tiles per CU (2 = half a round of the machine, 8 = two rounds); 1 .. 64 */
     E2EFT_OPT_GN_APPLY_ITERS = 13,   /* 0 (default): the GroupNorm apply pass picks its pixels per thread (4 x n sixteen-byte loads) by tensor size; 1 .. 16: forced n */
     E2EFT_OPT_F32_SPLIT = 14,        /* 1 (default, round 6): e2eft_conv2d_fwd_f32split_supported may answer 1 (fp32 3x3 convolutions from two-term f16 splits on the f16 matrix pipe); 0: it answers 0 (v_mfma_f32_32x32x2_f32 on igemm2) */
-    E2EFT_OPT_COUNT = 15
+    E2EFT_OPT_F32_SPLIT_ATTN = 15,   /* 0 (default): fp32 fused attention (e2eft_attn_fwd / _lse / e2eft_attn_bwd) on v_mfma_f32_32x32x2_f32 (attn32.hip); 1: e2eft_attn_f32split_supported may answer 1 (every fp32 product from two-term f16 splits on v_mfma_f32_32x32x16_f16, attn_f32split.hip) */
+    E2EFT_OPT_COUNT = 16
 };
 int e2eft_set_option(int32_t key, int32_t value);
 int e2eft_get_option(int32_t key);
@@ -305,6 +307,11 @@ int e2eft_attn_fwd(const E2eftAttnDesc* d, const void* q, const void* k, const v
 /* same, also storing lse[batch][heads][nq] (fp32): the base-2 log-sum-exp of the scaled scores of every query row, which
  * e2eft_attn_bwd needs to recompute the probabilities (lse may be NULL) */
 int e2eft_attn_fwd_lse(const E2eftAttnDesc* d, const void* q, const void* k, const void* v, void* out, float* lse, void* stream);
+/* Pure host arithmetic: 1 when e2eft_attn_fwd / _lse (backward == 0) or e2eft_attn_bwd (backward != 0) will run this fp32 attention on the split route
+ * (attn_f32split.hip: each fp32 product = three v_mfma_f32_32x32x16_f16 on two-term f16 splits, power-of-two scales found on the device, fp32 accumulation,
+ * softmax and storage; same arguments, strides, outputs and workspace as the strict route).  0 when E2EFT_OPT_F32_SPLIT_ATTN is 0 (the default), for a
+ * NULL descriptor, for 16-bit dtypes and for joint keys (kv_nseg > 1): those launches go to attn.hip / attn32.hip as before. */
+int32_t e2eft_attn_f32split_supported(const E2eftAttnDesc* d, int32_t backward);
 /* Fused attention forward for ONE head of width 512 (fp16 / bf16): the mid-block attention of AutoencoderKL
  * (GeoWizard/geowizard/models/unet_2d_blocks.py:589-601 — `Attention(heads = 1, dim_head = 512)` through AttnProcessor2_0:
  * F.scaled_dot_product_attention on [B, 1, H*W, 512]).  Descriptor as above with heads = 1, kv_nseg = 1, kv_bmod = batch;
