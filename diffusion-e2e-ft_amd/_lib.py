@@ -207,6 +207,11 @@ SIGNATURES = {
     "e2eft_ensemble_depth_reduce": (_I, [_I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "e2eft_ensemble_depth_finish": (_I, [_L, _P, _P, _P, _P]),
     "e2eft_ensemble_normals": (_I, [_I, _L, _P, _P, _P, _P, _Z, _P]),
+    # latent noise (csrc/noise.hip)
+    "e2eft_randn_fill": (_I, [_I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "e2eft_pyramid_noise_workspace_bytes": (_Z, [_I, _I, _I]),
+    "e2eft_pyramid_noise": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _F, _I, C.POINTER(C.c_int32), _P, _P, _Z, _P]),
+    "e2eft_latent_x0": (_I, [_I, _L, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
 }
 
 

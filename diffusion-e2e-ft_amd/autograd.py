@@ -861,6 +861,36 @@ def nchw_to_nhwc(x, cpad):
     return _NchwToNhwcFn.apply(x, cpad) if needs_grad(x) else ops.nchw_to_nhwc(x.contiguous(), cpad=cpad)
 
 
+def _nhwc_view(x):
+    """logical-NCHW tensor -> an NHWC view the kernels can stride (a copy only when its pixels are not dense)"""
+    xv = x.permute(0, 2, 3, 1)
+    try:
+        ops._nhwc_ld(xv)
+    except ValueError:
+        xv = xv.contiguous()
+    return xv
+
+
+class _LatentX0Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, x_t, c_x, c_v):
+        ctx.c_v = c_v
+        return ops.latent_x0(x_t, _nhwc_view(v), c_x, c_v).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dx0):
+        g = _nhwc_view(dx0)
+        dv = torch.empty(g.shape, dtype=g.dtype, device=g.device)
+        ops.copy_scale(g, dv, mul=ctx.c_v)
+        return dv.permute(0, 3, 1, 2), None, None, None
+
+
+def latent_x0(v, x_t, c_x, c_v):
+    """x0 = c_x * x_t + c_v * v  (train.py:509-518, 1 / scaling_factor folded into both): v logical NCHW [B,C,h,w] (the UNet's prediction), x_t an NHWC view
+    [B,h,w,C] read in place (the noise channels of the UNet input; carries no gradient).  Returns logical NCHW over NHWC storage; dv = c_v * dx0."""
+    return _LatentX0Fn.apply(v, x_t, c_x, c_v) if needs_grad(v) else ops.latent_x0(x_t, _nhwc_view(v), c_x, c_v).permute(0, 3, 1, 2)
+
+
 class _DepthHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, to_unit):

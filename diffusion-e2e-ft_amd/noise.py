@@ -1,0 +1,63 @@
+"""Latent noise drawn on the device (csrc/noise.hip): `--noise_type gaussian | pyramid` of training/train.py:483-491 and the `noise=` settings of
+marigold_pipeline.py:420-431, written straight into the noise channels of the UNet input.
+
+The generator is counter-based (Philox4x32-10 on the logical NCHW index, include/e2eft.h): a value is a pure function of (seed, draw, slot, element), so
+nothing is synchronised with the host, the result does not depend on memory layout or launch geometry, and a host restatement reproduces it
+(tests/noise_ref.py).  Bit parity with torch's own RNG streams is not a goal — torch's CPU and device generators already disagree with each other.
+
+NOT capture-safe: `draw` is a host counter passed to the kernels by value, so a replayed hipGraph repeats the noise it was captured with.  The captured
+paths of the pipelines remain the zeros ones.
+"""
+import random
+
+from . import ops
+
+
+class DeviceNoise:
+    """seed + a host-side `draw` counter that advances once per call (`next_draw`) and never reads the device.  Two generators with the same seed that
+    have made the same number of calls produce the same noise."""
+
+    def __init__(self, seed=0, draw=0):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.draw = int(draw) & 0xFFFFFFFF
+
+    def next_draw(self):
+        d = self.draw
+        self.draw = (d + 1) & 0xFFFFFFFF
+        return d
+
+
+def pyramid_level_sizes(rows, cols, rng=random):
+    """the (rows, cols) of every level grid `pipeline.pyramid_noise_like` (training/util/noise.py:8-18) would draw for a [.., rows, cols] latent: one
+    `rng.random()` per level in the reference's order (level 0 included, where shrink ** 0 = 1), the shrink cumulative, stopping after the first level
+    with a dimension of 1 — so `seed_all` gives the reference's sizes and leaves Python's `random` where the reference leaves it."""
+    sizes = []
+    for level in range(10):
+        shrink = (rng.random() * 2 + 2) ** level
+        rows, cols = max(1, int(rows / shrink)), max(1, int(cols / shrink))
+        sizes.append((rows, cols))
+        if rows == 1 or cols == 1:
+            break
+    return sizes
+
+
+def randn_into(dst_nhwc_slice, gen):
+    """standard normals into an NHWC view [B,H,W,C] (e.g. `xin[..., 4:]`); advances `gen.draw`"""
+    return ops.randn_fill_(dst_nhwc_slice, gen.seed, gen.next_draw(), slot=0)
+
+
+def pyramid_noise_into(dst_nhwc_slice, gen, discount=0.9, sizes=None):
+    """multi-resolution noise of unit std into an NHWC view [B,H,W,C]; `sizes` defaults to `pyramid_level_sizes(H, W)` (Python's `random`, as the
+    reference); advances `gen.draw`"""
+    _, H, W, _ = dst_nhwc_slice.shape
+    if sizes is None:
+        sizes = pyramid_level_sizes(H, W)
+    return ops.pyramid_noise_(dst_nhwc_slice, gen.seed, gen.next_draw(), sizes, discount)
+
+
+def noise_into(kind, dst_nhwc_slice, gen):
+    if kind == "gaussian":
+        return randn_into(dst_nhwc_slice, gen)
+    if kind == "pyramid":
+        return pyramid_noise_into(dst_nhwc_slice, gen)
+    raise ValueError("Unknown noise type %s" % kind)

@@ -855,6 +855,43 @@ def copy_scale(x, out, mul=1.0, add=0.0):
     return out
 
 
+def randn_fill_(dst, seed, draw, slot=0):
+    """dst[..., :] = standard normals of the device generator (include/e2eft.h: Philox4x32-10 on the LOGICAL NCHW index, Box-Muller) for an NHWC view
+    [B,H,W,C] (a strided channel slice allowed; the other channels of the buffer are untouched).  Same (seed, draw, slot, shape) -> same bits."""
+    _check_cuda(dst)
+    B, H, W, Cc = dst.shape
+    check(_lib.load().e2eft_randn_fill(dtype_id(dst.dtype), B, Cc, H * W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, int(slot), _ptr(dst), _stream()))
+    return dst
+
+
+def pyramid_noise_(dst, seed, draw, sizes, discount=0.9):
+    """dst[..., :] = multi-resolution noise (training/util/noise.py:8-18): base + sum_i discount^i * bilinear_up(level_i), divided by its unbiased std over the
+    whole tensor, for an NHWC view [B,H,W,C]; sizes: up to 10 (rows, cols) level sizes (host ints, passed by value: no host-to-device copy, no synchronisation)."""
+    _check_cuda(dst)
+    B, H, W, Cc = dst.shape
+    lib = _lib.load()
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    if len(sizes) > 10:
+        raise ValueError("pyramid_noise_: at most 10 levels, got %d" % len(sizes))
+    table = (C.c_int32 * max(2 * len(sizes), 2))(*[v for rc in sizes for v in rc])
+    nbytes = lib.e2eft_pyramid_noise_workspace_bytes(B, Cc, H * W)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dst.device)
+    check(lib.e2eft_pyramid_noise(dtype_id(dst.dtype), B, Cc, H, W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(discount), len(sizes),
+                                  table, _ptr(dst), _ptr(ws), nbytes, _stream()))
+    return dst
+
+
+def latent_x0(x_t, v, c_x, c_v, out=None):
+    """out = c_x * x_t + c_v * v for NHWC views [B,H,W,C] of one shape (x_t typically the noise channels of the UNet input, read in place)."""
+    _check_cuda(x_t, v, out)
+    assert x_t.shape == v.shape and x_t.dtype == v.dtype, (x_t.shape, v.shape, x_t.dtype, v.dtype)
+    if out is None:
+        out = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+    xa, va, oa = _as_rows(x_t), _as_rows(v), _as_rows(out)
+    check(_lib.load().e2eft_latent_x0(dtype_id(v.dtype), va.shape[0], v.shape[-1], _rows_ld(xa), _rows_ld(va), _rows_ld(oa), c_x, c_v, _ptr(xa), _ptr(va), _ptr(oa), _stream()))
+    return out
+
+
 def add(a, b, out=None):
     _check_cuda(a, b, out)
     assert a.shape == b.shape and a.dtype == b.dtype

@@ -162,8 +162,13 @@ class MarigoldPipeline:
         # UNet input buffer [B,h,w,8] NHWC: channels 0:4 rgb latent, 4:8 current latent ("this order is important" :447-449)
         xin = torch.zeros((B, h, w, 2 * C), dtype=dt, device=device)
         ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[..., :C])
+        on_device = None
         if isinstance(noise, torch.Tensor):      # an explicit initial latent [B,4,h,w]
             latent = noise.to(device=device, dtype=dt)
+        elif _device_noise(noise, generator):    # drawn by the device generator straight into channels 4:8 of the input buffer (noise.py): no host tensor, no copy
+            from . import noise as N
+            N.noise_into(noise, xin[..., C:], generator)
+            latent, on_device = to_nchw_view(xin[..., C:]), True
         elif noise == "gaussian":
             latent = torch.randn((B, C, h, w), device=device, dtype=dt, generator=generator)
         elif noise == "pyramid":
@@ -172,7 +177,7 @@ class MarigoldPipeline:
             latent = None  # xin[..., C:] is already zero
         else:
             raise ValueError("Unknown noise type: %s" % noise)
-        if latent is not None:
+        if latent is not None and not on_device:
             ops.copy_scale(latent.permute(0, 2, 3, 1).contiguous(), xin[..., C:])
         if self.empty_text_embed is None:
             self.encode_empty_text()
@@ -301,7 +306,9 @@ class MarigoldPipeline:
     @torch.no_grad()
     def __call__(self, input_image, denoising_steps=10, ensemble_size=10, processing_res=768, match_input_res=True,
                  resample_method="bilinear", batch_size=0, color_map="Spectral", show_progress_bar=True, ensemble_kwargs=None,
-                 noise="gaussian", normals=False):
+                 noise="gaussian", normals=False, generator=None):
+        """generator: a `torch.Generator` (host / torch RNG, as before) or a `noise.DeviceNoise` — then noise="gaussian" / "pyramid" is drawn on the device,
+        once per ensemble batch, directly in the UNet's input buffer"""
         assert processing_res >= 0 and ensemble_size >= 1
         if isinstance(input_image, torch.Tensor):
             rgb = input_image.squeeze()
@@ -320,7 +327,7 @@ class MarigoldPipeline:
         bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size, max(rgb_norm.shape[1:]), self.dtype)   # :254-261
         preds = []
         for s in range(0, ensemble_size, bs):
-            preds.append(self.single_infer(dup[s:s + bs], denoising_steps, show_progress_bar, noise=noise, normals=normals))
+            preds.append(self.single_infer(dup[s:s + bs], denoising_steps, show_progress_bar, noise=noise, normals=normals, generator=generator))
         preds = torch.cat(preds, dim=0).float().squeeze()
         if ensemble_size > 1:   # marigold_pipeline.py:293-297 (E2E-FT checkpoints are run with ensemble_size=1)
             from .ensemble import ensemble_depths, ensemble_normals
@@ -351,6 +358,12 @@ class MarigoldPipeline:
         pred = pred.clip(-1.0, 1.0)
         colored = _to_pil(np.moveaxis((((pred + 1) / 2) * 255).astype(np.uint8), 0, -1))                     # :338-341
         return MarigoldDepthOutput(depth_np=None, depth_colored=None, uncertainty=pred_uncert, normal_np=pred, normal_colored=colored)
+
+
+def _device_noise(noise, generator):
+    """noise="gaussian" / "pyramid" with a noise.DeviceNoise generator: drawn on the device.  Any other generator (None, a torch.Generator) keeps torch's path."""
+    from .noise import DeviceNoise
+    return isinstance(noise, str) and noise in ("gaussian", "pyramid") and isinstance(generator, DeviceNoise)
 
 
 def _evict_stale_graphs(graphs, new_key, n_weight_fields):
@@ -611,6 +624,9 @@ class DepthNormalEstimationPipeline:
         _, C, h, w = rgb_latent.shape
         if isinstance(noise, torch.Tensor):          # an explicit initial latent [B,4,h,w] (tests, reproducibility across devices)
             geo = noise.to(device=device, dtype=dt)
+        elif _device_noise(noise, generator):        # drawn on the device (noise.py); the depth and the normal row share it as below
+            from . import noise as N
+            geo = to_nchw_view(N.noise_into(noise, torch.empty((B, h, w, C), dtype=dt, device=device), generator))
         elif noise == "gaussian":
             geo = torch.randn((B, C, h, w), device=device, dtype=dt, generator=generator)
         elif noise == "pyramid":

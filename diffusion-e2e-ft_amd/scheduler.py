@@ -93,6 +93,15 @@ class DDIMScheduler:
             return 1.0
         raise ValueError("Unknown prediction type %s" % pt)
 
+    def x0_coefficients_for(self, t):
+        """(c_x, c_v) with x0 = c_x * x_t + c_v * model_output for ANY x_t (training/train.py:509-518, as in step()): v_prediction
+        (sqrt(abar_t), -sqrt(1 - abar_t)), epsilon (1 / sqrt(abar_t), -sqrt(1 - abar_t) / sqrt(abar_t)), sample (0, 1).  c_v is
+        `zero_latent_x0_scale(t)`; clip_sample / thresholding configurations are refused in the same way."""
+        c_v = self.zero_latent_x0_scale(t)
+        sa, _ = self.x0_coefficients(t)
+        pt = self.config.prediction_type
+        return {"v_prediction": sa, "epsilon": 1.0 / sa, "sample": 0.0}[pt], c_v
+
     def step(self, model_output, timestep, sample, eta=0.0, **kw):
         """DDIM step for epsilon / sample / v_prediction with eta = 0 (elementwise torch ops on tiny latents; the
         pipelines' fused path uses ops.copy_scale instead)."""

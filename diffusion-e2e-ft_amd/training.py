@@ -64,34 +64,74 @@ def encode_image(vae, image):
     return latent
 
 
-def e2e_ft_loss(unet, vae, batch, empty_encoding, modality="depth", noise_scheduler=None, return_estimate=False):
-    """Forward half of one micro-step (train.py:472-556) with the zeros latent at t = 999 (the E2E-FT recipe).
+NOISE_TYPES = ("zeros", "gaussian", "pyramid", None)      # training/train.py:57-63 (`--noise_type`; unset = a UNet without noise channels)
+
+
+def e2e_ft_loss(unet, vae, batch, empty_encoding, modality="depth", noise_scheduler=None, return_estimate=False, noise_type="zeros", generator=None,
+                noise=None):
+    """Forward half of one micro-step (train.py:472-556) at t = 999 (the E2E-FT recipe).
     batch: rgb [b,3,H,W] in [-1,1], val_mask [b,1,H,W] bool, metric [b,1,H,W] / normals [b,3,H,W].  Returns the scalar loss
     (device tensor with a grad_fn through the decoder and the UNet).  `unet` may be wrapped (DistributedDataParallel by
-    `accelerator.prepare`, train.py:369): attributes are read from `.module`, the forward goes through the wrapper."""
+    `accelerator.prepare`, train.py:369): attributes are read from `.module`, the forward goes through the wrapper.
+    noise_type (train.py:483-499): "zeros" (default: the zeros latent, x0 = c * model_pred), "gaussian" / "pyramid" (drawn on the device by
+    `generator`, a noise.DeviceNoise, straight into channels 4:8 of the UNet input; x0 by the scheduler's prediction_type from that x_t), None
+    (a 4-channel UNet fed the rgb latent alone).  noise: an explicit x_t [b,4,h,w] instead of a drawn one (tests, reproducibility across devices).
+    The drawn settings are not capture-safe (noise.py): a replayed graph repeats its noise."""
+    if noise_type not in NOISE_TYPES:
+        raise ValueError("Unknown noise type %s" % noise_type)
     core = getattr(unet, "module", unet)
-    dev = core.device
     with ops.on_device_of(next(core.parameters())):
-        return _e2e_ft_loss(unet, core, vae, batch, empty_encoding, modality, noise_scheduler, return_estimate)
+        return _e2e_ft_loss(unet, core, vae, batch, empty_encoding, modality, noise_scheduler, return_estimate, noise_type, generator, noise)
 
 
-def _e2e_ft_loss(unet, core, vae, batch, empty_encoding, modality, noise_scheduler, return_estimate):
+def _e2e_ft_loss(unet, core, vae, batch, empty_encoding, modality, noise_scheduler, return_estimate, noise_type="zeros", generator=None, noise=None):
     dev = core.device
     dt = getattr(core, "compute_dtype", core.dtype)
+    if noise_type is None:
+        if noise is not None:
+            raise ValueError("noise_type=None feeds the UNet no noise channels: an explicit `noise` has nowhere to go")
+        if core.config["in_channels"] != 4:
+            raise ValueError("noise_type=None needs a UNet whose conv_in takes the 4 rgb-latent channels alone; this one has in_channels=%s "
+                             "(replace_unet_conv_in doubles them for the other noise types)" % core.config["in_channels"])
     with torch.no_grad():
         rgb_latents = encode_image(vae, batch["rgb"].to(device=dev, dtype=dt)) * vae.config.scaling_factor
     val_mask = batch["val_mask"].bool().to(dev)
     b = rgb_latents.shape[0]
     timesteps = torch.full((b,), 999, device=dev, dtype=torch.long)
-    noisy = torch.zeros_like(rgb_latents)
     ctx = empty_encoding.to(device=dev, dtype=dt).repeat(b, 1, 1)
-    unet_input = torch.cat((rgb_latents, noisy), dim=1).contiguous(memory_format=torch.channels_last)
-    model_pred = unet(unet_input, timesteps, ctx, return_dict=False)[0]
     if noise_scheduler is None:
         from .scheduler import DDIMScheduler
         noise_scheduler = DDIMScheduler()
-    # x_t = 0: x0 = c * model_pred with c by the scheduler's prediction_type (v: -sqrt(1 - alpha_prod), train.py:509-518), then / scaling_factor (:528)
-    x0 = model_pred * (noise_scheduler.zero_latent_x0_scale(999) / vae.config.scaling_factor)
+    x_t = None              # NHWC view of the noise channels when x_t != 0
+    if noise_type is None:
+        unet_input = rgb_latents
+    elif noise is None and noise_type == "zeros":
+        noisy = torch.zeros_like(rgb_latents)
+        unet_input = torch.cat((rgb_latents, noisy), dim=1).contiguous(memory_format=torch.channels_last)
+    else:
+        # UNet input buffer [b,h,w,8] NHWC: channels 0:4 the rgb latent, 4:8 x_t, written in place (no concat, no layout copy)
+        _, C, h, w = rgb_latents.shape
+        xin = torch.empty((b, h, w, 2 * C), dtype=dt, device=dev)
+        ops.copy_scale(F._nhwc_view(rgb_latents), xin[..., :C])
+        x_t = xin[..., C:]
+        if noise is not None:
+            if tuple(noise.shape) != (b, C, h, w):
+                raise ValueError("noise must be [%d,%d,%d,%d], got %s" % (b, C, h, w, tuple(noise.shape)))
+            ops.copy_scale(F._nhwc_view(noise.to(device=dev, dtype=dt)), x_t)
+        else:
+            from . import noise as N
+            if not isinstance(generator, N.DeviceNoise):
+                raise TypeError("noise_type=%r draws on the device: pass generator=noise.DeviceNoise(seed)" % noise_type)
+            N.noise_into(noise_type, x_t, generator)
+        unet_input = xin.permute(0, 3, 1, 2)
+    model_pred = unet(unet_input, timesteps, ctx, return_dict=False)[0]
+    sf = vae.config.scaling_factor
+    if x_t is None:
+        # x_t = 0: x0 = c * model_pred with c by the scheduler's prediction_type (v: -sqrt(1 - alpha_prod), train.py:509-518), then / scaling_factor (:528)
+        x0 = model_pred * (noise_scheduler.zero_latent_x0_scale(999) / sf)
+    else:
+        c_x, c_v = noise_scheduler.x0_coefficients_for(999)
+        x0 = F.latent_x0(model_pred, x_t, c_x / sf, c_v / sf)
     est = vae.decoder(vae.post_quant_conv(x0))                     # [b,3,H,W] logical NCHW, NHWC memory
     est_nhwc = est.permute(0, 2, 3, 1)
     if modality == "depth":

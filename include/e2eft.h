@@ -706,6 +706,41 @@ int e2eft_adamw_step_guarded(int64_t n, float* param, const float* grad, float* 
 int e2eft_ema_step(int64_t n, float* shadow, const float* param, float one_minus_decay, void* stream);
 int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accumulate, const void* x, void* y, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Latent noise on the device (csrc/noise.hip): `--noise_type gaussian | pyramid` of training/train.py:483-491 and the
+ * `noise=` settings of marigold_pipeline.py:420-431, and the x0 of a non-zero x_t (train.py:509-518).
+ *
+ * Generator: Philox4x32-10, counter-based.  Element e of a tensor is its LOGICAL NCHW linear index, whatever the memory
+ * layout: q = e >> 2, counter = (q & 0xffffffff, q >> 32, slot, draw), key = (seed & 0xffffffff, seed >> 32), word = output[e & 3],
+ * u = ((word >> 8) + 0.5) * 2^-24 (strictly inside (0,1)).  Box-Muller pairs the words (0,1) and (2,3) of one counter:
+ * r = sqrt(-2 ln u_even), theta = 2 pi u_odd; the even word's element gets r cos(theta), the odd word's r sin(theta) — fp32 with the
+ * accurate logf / log1pf / sqrtf / sinf / cosf, rounded once to `dtype` at the store.  (u has 25 significant bits for word >> 8 >= 2^23; the
+ * kernel then works from 1 - u, which is exact in fp32 there: ln u = log1p(-(1 - u)), cos / sin by the reflection theta -> 2 pi - theta.)  slot 0 is the base grid of a call, slot 1 + i the grid
+ * of pyramid level i; `draw` is the caller's per-call counter.  Same (seed, draw, slot, shape) -> the same bits, on every launch:
+ * the values do not depend on the launch geometry and no floating-point atomics are used.  `draw` travels by value, so a
+ * captured graph that contains one of these calls repeats its noise on replay.
+ * ---------------------------------------------------------------------------------------------------- */
+#define E2EFT_PYRAMID_MAX_LEVELS 10
+/* y[p, 0:c] = standard normals for the NHWC destination [batch, hw, (ldy)] — element (b, ch, pix) is e = (b*c + ch)*hw + pix; channels
+ * c..ldy of a pixel are not touched (the caller offsets y to the noise channels of the UNet input).  y aligned to its element size; whole-pixel
+ * stores when c == 4, hw % 4 == 0, ldy % 4 == 0 and y is aligned to 4 elements.  batch*c*hw < 2^31. */
+int e2eft_randn_fill(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, uint32_t draw, uint32_t slot, void* y,
+                     void* stream);
+/* Multi-resolution noise (training/util/noise.py:8-18 = marigold_pipeline.py:76-86):
+ *   total = base + sum_i discount^i * bilinear_up(level_i),  y = total / std(total)      (std unbiased, over the whole tensor, batch included)
+ * base is the grid of slot 0 ([batch,c,rows,cols]), level_i the grid of slot 1 + i ([batch,c,level_sizes[2i],level_sizes[2i+1]]); bilinear_up is
+ * nn.Upsample(size=(rows,cols), mode="bilinear"), i.e. align_corners=False.  level_sizes is a HOST array of n_levels (<= E2EFT_PYRAMID_MAX_LEVELS)
+ * (rows, cols) pairs, read before the call returns.  The level grids are never stored: a level's corner values are evaluated from the counter.
+ * Two launches: totals (fp32, workspace) + per-block partial sums, then every block combines the partials in one fixed order in fp64 and scales
+ * into y (NHWC, pixel stride ldy, channels c..ldy untouched).  workspace: e2eft_pyramid_noise_workspace_bytes, 16-byte aligned. */
+size_t e2eft_pyramid_noise_workspace_bytes(int32_t batch, int32_t c, int32_t hw);
+int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
+                        int32_t n_levels, const int32_t* level_sizes, void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* x0[p, 0:c] = c_x * x_t[p, 0:c] + c_v * v[p, 0:c] in fp32 (train.py:509-518 by prediction_type; the caller folds 1 / scaling_factor, :528, into both
+ * coefficients).  x_t is read in place from the noise channels of the UNet input (pixel stride ldxt), v and x0 have their own pixel strides. */
+int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,
+                    const void* v, void* x0, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
