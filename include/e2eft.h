@@ -276,9 +276,11 @@ int e2eft_geglu_fwd(int32_t dtype, int64_t rows, int32_t c, int32_t ldh, int32_t
                     void* stream);
 
 /* Row softmax in place: s[r, :n] = softmax(scale * s[r, :n]) for r < rows (row stride lds).
+ * The pad columns [n, roundup(n, 16 bytes)) of every row are written as zeros, whatever they held (lds >= that round-up); nothing beyond it is touched.
  * Used by the unfused attention path (VAE mid-block d=512 attention and the strict-fp32 path). */
 int e2eft_softmax_rows(int32_t dtype, int64_t rows, int32_t n, int64_t lds, float scale, void* s, void* stream);
 /* The same with a causal mask: row r is query r % nq and attends to keys 0 .. r % nq, the rest of the row is written as zeros
+ * (the pad columns [n, roundup(n, 16 bytes)) included, as in e2eft_softmax_rows)
  * (the CLIP text tower behind encode_empty_text, /root/reference/Marigold/marigold/marigold_pipeline.py:356-369 and
  * training/train.py:455-458: transformers CLIPTextModel builds a causal attention mask). */
 int e2eft_softmax_rows_causal(int32_t dtype, int64_t rows, int32_t n, int64_t lds, float scale, int32_t nq, void* s, void* stream);
@@ -443,7 +445,8 @@ int e2eft_layernorm_bwd(int32_t dtype, int64_t rows, int32_t c, int32_t ldx, int
 /* GEGLU backward: h [rows, 2c] (value | gate), dy [rows, c] -> dh [rows, 2c] */
 int e2eft_geglu_bwd(int32_t dtype, int64_t rows, int32_t c, int32_t ldh, int32_t lddy, int32_t lddh, const void* h,
                     const void* dy, void* dh, void* stream);
-/* softmax backward in place on dp: ds = p * (dp - rowsum(dp * p)) * scale (attention backward, p = softmax(scale * s)) */
+/* softmax backward in place on dp: ds = p * (dp - rowsum(dp * p)) * scale (attention backward, p = softmax(scale * s)).
+ * The pad columns [n, roundup(n, 16 bytes)) of every row of dp are written as zeros; what p and dp held there is never used (any bit pattern is fine). */
 int e2eft_softmax_bwd_rows(int32_t dtype, int64_t rows, int32_t n, int64_t lds, float scale, const void* p, void* dp,
                            void* stream);
 int e2eft_silu_bwd(int32_t dtype, int64_t n, const void* x, const void* dy, void* dx, void* stream);
