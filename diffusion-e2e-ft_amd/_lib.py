@@ -172,9 +172,11 @@ SIGNATURES = {
     "e2eft_silu_bwd": (_I, [_I, _L, _P, _P, _P, _P]),
     "e2eft_depth_head_bwd": (_I, [_I, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
     "e2eft_normal_head_bwd": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "e2eft_ssi_loss_bwd_workspace_bytes": (_Z, [_I]),
     "e2eft_ssi_loss_bwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "e2eft_angular_loss_bwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "e2eft_sumsq": (_I, [_L, _P, _P, _P]),
+    "e2eft_sumsq_workspace_bytes": (_Z, [_L]),
+    "e2eft_sumsq": (_I, [_L, _P, _P, _P, _Z, _P]),
     "e2eft_adamw_step": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _P, _F, _F, _P]),
     "e2eft_adamw_step_guarded": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _F, _F, _P]),
     "e2eft_cast": (_I, [_I, _I, _L, _F, _I, _P, _P, _P]),

@@ -227,49 +227,44 @@ __global__ __launch_bounds__(256) void normal_head_bwd_kernel(int batch, int hw,
 
 // ---------------------------------------------------------------------------------------------------------------
 // losses (training/util/loss.py), backward.  fp32 I/O, fp64 reductions like the forward.
-__device__ __forceinline__ double wave_sum_d2(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // per image: Gs = sum m sign(r) p, Gh = sum m sign(r), r = s p + h - t
 __global__ __launch_bounds__(256) void ssi_bwd_sums_kernel(int hw, const float* __restrict__ pred, const float* __restrict__ tgt,
                                                            const uint8_t* __restrict__ mask, const float* __restrict__ ss,
-                                                           double* __restrict__ gsum /* [B][2] */) {
-    __shared__ double red[4][2];
+                                                           double* __restrict__ gpart /* [B][nb][2] */) {
     const int b = blockIdx.y;
     const float sc = ss[b * 2], sh = ss[b * 2 + 1];
     const float* p = pred + (long)b * hw;
     const float* t = tgt + (long)b * hw;
     const uint8_t* m = mask + (long)b * hw;
-    double v0 = 0, v1 = 0;
+    double v[2] = {0, 0};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += gridDim.x * 256) {
         if (m[i]) {
             const float r = sc * p[i] + sh - t[i];
             const float sg = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
-            v0 += (double)(sg * p[i]);
-            v1 += (double)sg;
+            v[0] += (double)(sg * p[i]);
+            v[1] += (double)sg;
         }
     }
-    v0 = wave_sum_d2(v0); v1 = wave_sum_d2(v1);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = v0; red[threadIdx.x >> 6][1] = v1; }
-    __syncthreads();
-    if (threadIdx.x < 2) atomicAdd(gsum + b * 2 + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+    block_sums<2>(v, gpart + ((long)b * gridDim.x + blockIdx.x) * 2);
 }
 
-// grad_j = gout * m_j * (c0 sign(r_j) + c1 + c2 t_j + c3 p_j)  — the chain through the closed-form scale/shift included
+// grad_j = gout * m_j * (c0 sign(r_j) + c1 + c2 t_j + c3 p_j)  — the chain through the closed-form scale/shift included.
+// Every block first takes Gs, Gh of its image: the gridDim.x partials of ssi_bwd_sums_kernel (same grid) in index order.
 __global__ __launch_bounds__(256) void ssi_bwd_apply_kernel(int hw, const float* __restrict__ pred, const float* __restrict__ tgt,
                                                             const uint8_t* __restrict__ mask, const float* __restrict__ ss,
                                                             const double* __restrict__ sums /* [B][5] */, const double* __restrict__ acc /* [2] */,
-                                                            const double* __restrict__ gsum, const float* __restrict__ gout,
+                                                            const double* __restrict__ gpart, const float* __restrict__ gout,
                                                             float* __restrict__ dpred) {
     const int b = blockIdx.y;
     const double s = ss[b * 2], h = ss[b * 2 + 1];
     const double a00 = sums[b * 5], a01 = sums[b * 5 + 1], a11 = sums[b * 5 + 2], b0 = sums[b * 5 + 3], b1 = sums[b * 5 + 4];
     const double det = (double)((float)a00 * (float)a11 - (float)a01 * (float)a01);   // the forward's fp32 determinant decides validity
     const double nv = acc[1];
-    const double Gs = gsum[b * 2], Gh = gsum[b * 2 + 1];
+    double Gs = 0, Gh = 0;
+    for (int k = 0; k < (int)gridDim.x; ++k) {
+        Gs += gpart[((long)b * gridDim.x + k) * 2];
+        Gh += gpart[((long)b * gridDim.x + k) * 2 + 1];
+    }
     double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     const bool live = nv > 0.0 && !isnan(acc[0]);     // skipped loss term (no valid pixel / NaN loss, train.py:504,548): zero gradient
     if (det > 0.0 && live) {
@@ -322,14 +317,17 @@ __global__ __launch_bounds__(256) void angular_bwd_kernel(int hw, const float* _
 
 // ---------------------------------------------------------------------------------------------------------------
 // flat-buffer optimizer: all UNet parameters / gradients live in one fp32 buffer each (one RCCL all-reduce, one update launch)
-__global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* __restrict__ g, double* __restrict__ out) {
-    __shared__ double red[4];
-    double a = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) a += (double)g[i] * (double)g[i];
-    a = wave_sum_d2(a);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+constexpr int SUMSQ_NBLK = 2048;   // most partial blocks of e2eft_sumsq
+__global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* __restrict__ g, double* __restrict__ part) {
+    double a[1] = {0};
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) a[0] += (double)g[i] * (double)g[i];
+    block_sums<1>(a, part + blockIdx.x);
+}
+// one block: thread t adds partials t, t + 256, ... in order, then the fixed block sum -> out[0]
+__global__ __launch_bounds__(256) void sumsq_final_kernel(int nparts, const double* __restrict__ part, double* __restrict__ out) {
+    double a[1] = {0};
+    for (int k = threadIdx.x; k < nparts; k += 256) a[0] += part[k];
+    block_sums<1>(a, out);
 }
 
 // torch.optim.AdamW semantics (decoupled decay), gradient pre-scaled by min(1, max_norm / (||g|| + 1e-6)) when sumsq is given
@@ -526,23 +524,25 @@ extern "C" int e2eft_normal_head_bwd(int32_t dt_x, int32_t dt_y, int32_t batch, 
     return check_launch("normal_head_bwd");
 }
 
+extern "C" size_t e2eft_ssi_loss_bwd_workspace_bytes(int32_t batch) { return batch > 0 ? (size_t)batch * LOSS_NBLK * 2 * sizeof(double) : 0; }
+
 // fwd_workspace: the buffer e2eft_ssi_loss_fwd filled (per-image sums, valid count); scale_shift: its [B][2] output
 extern "C" int e2eft_ssi_loss_bwd(int32_t batch, int32_t hw, const float* pred, const float* target, const uint8_t* mask,
                                   const float* scale_shift, const void* fwd_workspace, const float* grad_out, float* dpred, void* workspace,
                                   size_t ws_bytes, void* stream) {
     E2EFT_REQUIRE(pred && target && mask && scale_shift && fwd_workspace && grad_out && dpred && workspace, "ssi_loss_bwd: null pointer");
     E2EFT_REQUIRE(batch > 0 && batch <= 65535 && hw > 0, "ssi_loss_bwd: shape");
-    if (ws_bytes < (size_t)batch * 2 * sizeof(double)) return fail(E2EFT_ERR_WORKSPACE, "ssi_loss_bwd: workspace too small");
+    const size_t need = e2eft_ssi_loss_bwd_workspace_bytes(batch);
+    if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "ssi_loss_bwd: workspace %zu < %zu", ws_bytes, need);
     E2EFT_REQUIRE(((uintptr_t)workspace & 7) == 0, "ssi_loss_bwd: workspace must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const double* sums = (const double*)fwd_workspace;
     const double* acc = sums + (size_t)batch * 5;
-    double* gsum = (double*)workspace;
-    if (hipMemsetAsync(workspace, 0, (size_t)batch * 2 * sizeof(double), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "ssi_loss_bwd: memset failed");
+    double* gpart = (double*)workspace;
     int nb = cdiv(hw, 256 * 8);
-    if (nb > 256) nb = 256;
-    hipLaunchKernelGGL(ssi_bwd_sums_kernel, dim3(nb, batch), dim3(256), 0, s, hw, pred, target, mask, scale_shift, gsum);
-    hipLaunchKernelGGL(ssi_bwd_apply_kernel, dim3(nb, batch), dim3(256), 0, s, hw, pred, target, mask, scale_shift, sums, acc, gsum, grad_out, dpred);
+    if (nb > LOSS_NBLK) nb = LOSS_NBLK;
+    hipLaunchKernelGGL(ssi_bwd_sums_kernel, dim3(nb, batch), dim3(256), 0, s, hw, pred, target, mask, scale_shift, gpart);
+    hipLaunchKernelGGL(ssi_bwd_apply_kernel, dim3(nb, batch), dim3(256), 0, s, hw, pred, target, mask, scale_shift, sums, acc, gpart, grad_out, dpred);
     return check_launch("ssi_loss_bwd");
 }
 
@@ -552,7 +552,7 @@ extern "C" int e2eft_angular_loss_bwd(int32_t batch, int32_t hw, const float* pr
     E2EFT_REQUIRE(batch > 0 && batch <= 65535 && hw > 0, "angular_loss_bwd: shape");
     hipStream_t s = (hipStream_t)stream;
     int nb = cdiv(hw, 256 * 8);
-    if (nb > 256) nb = 256;
+    if (nb > LOSS_NBLK) nb = LOSS_NBLK;
     hipLaunchKernelGGL(angular_bwd_kernel, dim3(nb, batch), dim3(256), 0, s, hw, pred, target, mask, (const double*)fwd_workspace, grad_out, dpred);
     return check_launch("angular_loss_bwd");
 }
@@ -581,13 +581,16 @@ extern "C" int e2eft_ema_step(int64_t n, float* shadow, const float* param, floa
     return check_launch("ema_step");
 }
 
-extern "C" int e2eft_sumsq(int64_t n, const float* g, double* out, void* stream) {
-    E2EFT_REQUIRE(g && out && n > 0 && ((uintptr_t)out & 7) == 0, "sumsq: bad args");
+extern "C" size_t e2eft_sumsq_workspace_bytes(int64_t n) { return n > 0 ? (size_t)(grid_for(n) < SUMSQ_NBLK ? grid_for(n) : SUMSQ_NBLK) * sizeof(double) : 0; }
+
+extern "C" int e2eft_sumsq(int64_t n, const float* g, double* out, void* workspace, size_t ws_bytes, void* stream) {
+    E2EFT_REQUIRE(g && out && workspace && n > 0 && (((uintptr_t)out | (uintptr_t)workspace) & 7) == 0, "sumsq: bad args");
+    const size_t need = e2eft_sumsq_workspace_bytes(n);
+    if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "sumsq: workspace %zu < %zu", ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(double), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "sumsq: memset failed");
-    unsigned nb = grid_for(n);
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, s, (long)n, g, out);
+    const unsigned nb = (unsigned)(need / sizeof(double));
+    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, s, (long)n, g, (double*)workspace);
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, (int)nb, (const double*)workspace, out);
     return check_launch("sumsq");
 }
 

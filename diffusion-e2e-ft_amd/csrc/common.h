@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include "../../include/e2eft.h"
 #include "../../include/e2eft_debug.h"
+#include "reduce.h"   // wave_sum / wave_min / wave_max, block_sums, block_minmax
 
 namespace e2eft {
 
@@ -82,18 +83,8 @@ __device__ __forceinline__ float gn_act_u(const float u, const bool silu) {
 }
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+constexpr int LOSS_NBLK = 256;   // loss.hip, bwd.hip: most partial blocks per image of the loss reductions (the workspaces are sized for it)
 
 // dispatch helper: calls F<T>(args...) for the runtime dtype
 #define E2EFT_DISPATCH_DTYPE(dt, T, ...)                                  \

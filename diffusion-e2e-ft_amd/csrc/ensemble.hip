@@ -15,31 +15,6 @@ namespace e2eft {
 constexpr int ENS_MAX = 32;      // images per ensemble (the reference's default ensemble_size is 10)
 constexpr int ENS_BLOCKS = 256;  // partials per reduction
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// block (256 threads) min / max -> out[0], out[1] by thread 0
-__device__ __forceinline__ void block_minmax(float mn, float mx, float* out) {
-    __shared__ float red[2][4];
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[0][wave] = mn; red[1][wave] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
-        out[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-    }
-}
-
 // ---- per-image min / max (ensemble.py:68-69): grid (ENS_BLOCKS, N) -> part [N][ENS_BLOCKS][2] ------------------------------
 __global__ __launch_bounds__(256) void ens_minmax_partial(long npix, const float* __restrict__ x, float* __restrict__ part) {
     const float* p = x + (long)blockIdx.y * npix;
@@ -80,7 +55,7 @@ __global__ __launch_bounds__(256) void ens_gram_partial(int n, long npix, const 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j <= ENS_MAX; ++j) {
-        const double v = wave_sum_f64(acc[j]);
+        const double v = wave_sum(acc[j]);
         if (lane == 0) red[wave][j] = v;
     }
     __syncthreads();
@@ -222,7 +197,7 @@ __global__ __launch_bounds__(256) void ens_normals_partial(int n, long hw, const
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll 1
     for (int k = 0; k < n; ++k) {
-        const double v = wave_sum_f64(acc[k][tid]);
+        const double v = wave_sum(acc[k][tid]);
         __syncthreads();
         if (lane == 0) red[wave] = v;
         __syncthreads();

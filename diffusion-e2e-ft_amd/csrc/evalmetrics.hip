@@ -16,24 +16,6 @@ constexpr int EV_NBLK = 128;      // partial blocks per image
 constexpr int EV_NSUM = 5;        // alignment sums: n, sum p, sum p^2, sum g, sum p g
 constexpr int EV_NMET = 12;       // metric sums (below)
 
-__device__ __forceinline__ double ev_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <int N> __device__ __forceinline__ void ev_block_store(double (&v)[N], double* dst) {
-    __shared__ double red[4][N];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        v[i] = ev_wave_sum(v[i]);
-        if (lane == 0) red[wave][i] = v[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < N) dst[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
 // pass 1: per-image sums of the (optionally nearest-down-sampled) valid pixels.  disparity != 0: the target is 1 / gt where gt > 0 and
 // only pixels with gt > 0 and pred > 0 take part (eval.py:182-190).  Down-sampling: torch.nn.Upsample(scale_factor, "nearest") reads source
 // index floor(dst * (1 / scale_factor)) (alignment.py:23-33; the host passes oh == h: see e2eft_depth_eval); oh == h, ow == w means none.
@@ -60,7 +42,7 @@ __global__ __launch_bounds__(256) void ev_align_sums_kernel(int h, int w, int oh
         }
         v[0] += 1.0; v[1] += (double)p; v[2] += (double)p * p; v[3] += (double)g; v[4] += (double)p * g;
     }
-    ev_block_store<EV_NSUM>(v, part + ((long)b * gridDim.x + blockIdx.x) * EV_NSUM);
+    block_sums<EV_NSUM>(v, part + ((long)b * gridDim.x + blockIdx.x) * EV_NSUM);
 }
 
 // closed-form least squares  [sum p^2, sum p; sum p, n] [s; t] = [sum p g; sum g]  in fp64 (numpy.linalg.lstsq solves the same normal
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(256) void ev_metric_sums_kernel(int hw, int dispari
         v[9] += r < 1.953125f ? 1.0 : 0.0;
         v[10] += (double)(id * id);
     }
-    ev_block_store<EV_NMET>(v, part + ((long)b * gridDim.x + blockIdx.x) * EV_NMET);
+    block_sums<EV_NMET>(v, part + ((long)b * gridDim.x + blockIdx.x) * EV_NMET);
 }
 
 // per image: abs_rel, sq_rel, rmse, rmse_log, log10, delta1, delta2, delta3, i_rmse, silog, scale, shift  (metric.py; order of eval.py's table)

@@ -83,8 +83,7 @@ __global__ __launch_bounds__(GP_THREADS) void gp_kernel(const e2eft_depth_gt_des
         }
     }
     if (n_valid == nullptr) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if (lane == 0) cnt[w] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void absmax_f32_kernel(long pixels, int c, int
         fold(v0); fold(v1); fold(v2); fold(v3);
     }
     for (; it < total; it += stride) fold(at(it));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     // ONE atomic per workgroup, at most 1024 workgroups: 16 k same-address atomics (one per wave of 4096 workgroups) cost 0.25 ms — more than the pass itself on a 100 MB tensor
     __shared__ float wmax[4];
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;

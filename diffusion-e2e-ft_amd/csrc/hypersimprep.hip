@@ -201,11 +201,7 @@ __global__ __launch_bounds__(HP_THREADS) void hp_min_kernel(int64_t n, const T* 
         const uint64_t k = hp_key(hp_brightness(c + i * 3));
         if (k > a && k < mn) mn = k;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_xor(mn, o, 64);
-        mn = u < mn ? u : mn;
-    }
+    mn = wave_min(mn);
     __shared__ unsigned long long red[HP_THREADS / 64];
     if ((t & 63) == 0) red[t >> 6] = mn;
     __syncthreads();
@@ -227,11 +223,7 @@ __global__ __launch_bounds__(64) void hp_scale_kernel(int nblk, double numerator
             const unsigned long long u = mpart[(int64_t)f * nblk + j];
             mn = u < mn ? u : mn;
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_xor(mn, o, 64);
-        mn = u < mn ? u : mn;
-    }
+    mn = wave_min(mn);
     if (t != 0) return;
     double p = __longlong_as_double(0x7ff8000000000000LL), s = 1.0;
     if (st[0] != 0) {
@@ -308,13 +300,7 @@ __global__ __launch_bounds__(HP_THREADS) void hp_apply_kernel(int height, int wi
     }
     unsigned long long v[8] = {s8, q8, mn8, mx8, sd, qd, mnd, mxd};
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long w = __shfl_xor(v[k], o, 64);
-            const bool isMin = (k & 3) == 2, isMax = (k & 3) == 3;
-            v[k] = isMin ? (w < v[k] ? w : v[k]) : isMax ? (w > v[k] ? w : v[k]) : v[k] + w;
-        }
+    for (int k = 0; k < 8; ++k) v[k] = (k & 3) == 2 ? wave_min(v[k]) : (k & 3) == 3 ? wave_max(v[k]) : wave_sum(v[k]);
     if ((t & 63) == 0) {
         unsigned long long* st = stats + (int64_t)f * HP_NSTAT + 2;
 #pragma unroll

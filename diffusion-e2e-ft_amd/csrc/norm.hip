@@ -233,8 +233,8 @@ __global__ __launch_bounds__(256) void gn_split_scale_kernel(int C, float sqrt_n
         if (gamma) mg = fmaxf(mg, fabsf(gamma[c]));
         if (beta) mb = fmaxf(mb, fabsf(beta[c]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mg = fmaxf(mg, __shfl_xor(mg, o, 64)); mb = fmaxf(mb, __shfl_xor(mb, o, 64)); }
+    mg = wave_max(mg);
+    mb = wave_max(mb);
     __shared__ float sg[4], sb[4];
     if ((threadIdx.x & 63) == 0) { sg[threadIdx.x >> 6] = mg; sb[threadIdx.x >> 6] = mb; }
     __syncthreads();

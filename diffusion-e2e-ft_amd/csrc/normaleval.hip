@@ -53,17 +53,6 @@ static NeLayout ne_layout(void* ws) {
     return l;
 }
 
-__device__ __forceinline__ double ne_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t ne_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // torch.cosine_similarity (ATen: x / max(|x|, eps) per vector, then the product summed over the channel) -> clamp -> acos -> degrees, in fp32
 __device__ __forceinline__ float ne_angle(float p0, float p1, float p2, float g0, float g1, float g2) {
     const float np_ = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(p0, p0), __fmul_rn(p1, p1)), __fmul_rn(p2, p2))), 1e-8f);
@@ -118,30 +107,20 @@ __global__ __launch_bounds__(NE_UTHREADS) void ne_update_kernel(e2eft_normal_eva
             pixel(i, b, y, (int32_t)(r - (int64_t)y * d.width));
         }
     }
-    __shared__ double reds[NE_UTHREADS / 64][2];
     __shared__ uint32_t redc[NE_UTHREADS / 64][7];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s = ne_wave_sum(s);
-    ss = ne_wave_sum(ss);
 #pragma unroll
-    for (int k = 0; k < 7; ++k) cnt[k] = ne_wave_sum(cnt[k]);
-    if (lane == 0) {
-        reds[wave][0] = s;
-        reds[wave][1] = ss;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) redc[wave][k] = cnt[k];
+    for (int k = 0; k < 7; ++k) {
+        cnt[k] = wave_sum(cnt[k]);
+        if (lane == 0) redc[wave][k] = cnt[k];
     }
-    __syncthreads();
     int64_t* o = part + (int64_t)blockIdx.x * NE_NTOT;
+    double sv[2] = {s, ss};
+    block_sums<2, NE_UTHREADS / 64>(sv, reinterpret_cast<double*>(o + 7));      // (its barrier covers redc too)
     if (threadIdx.x < 7) {
         int64_t v = 0;
         for (int w = 0; w < NE_UTHREADS / 64; ++w) v += redc[w][threadIdx.x];
         o[threadIdx.x] = v;
-    } else if (threadIdx.x < 9) {
-        const int k = threadIdx.x - 7;
-        double v = 0.0;
-        for (int w = 0; w < NE_UTHREADS / 64; ++w) v += reds[w][k];
-        o[threadIdx.x] = __double_as_longlong(v);
     }
 }
 
@@ -161,11 +140,9 @@ __global__ __launch_bounds__(256) void ne_update_reduce_kernel(int nblk, const i
         ss += __longlong_as_double(p[8]);
     }
 #pragma unroll
-    for (int k = 0; k < 7; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
-    s = ne_wave_sum(s);
-    ss = ne_wave_sum(ss);
+    for (int k = 0; k < 7; ++k) c[k] = wave_sum(c[k]);
+    s = wave_sum(s);
+    ss = wave_sum(ss);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) redc[wave][k] = c[k];
@@ -174,10 +151,10 @@ __global__ __launch_bounds__(256) void ne_update_reduce_kernel(int nblk, const i
     }
     __syncthreads();
     if (t < 7) {
-        totals[t] += (redc[0][t] + redc[1][t]) + (redc[2][t] + redc[3][t]);
+        totals[t] += redc[0][t] + redc[1][t] + redc[2][t] + redc[3][t];
     } else if (t < 9) {
         const int k = t - 7;
-        const double v = (reds[0][k] + reds[1][k]) + (reds[2][k] + reds[3][k]);
+        const double v = reds[0][k] + reds[1][k] + reds[2][k] + reds[3][k];      // the waves left to right, as block_sums
         totals[t] = __double_as_longlong(__longlong_as_double(totals[t]) + v);
     }
 }
@@ -311,8 +288,7 @@ __global__ __launch_bounds__(NE_HTHREADS) void ne_min_kernel(int64_t m, const ui
         const uint32_t u = bits[i];
         if (u > a && u < mn) mn = u;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+    mn = wave_min(mn);
     __shared__ uint32_t red[NE_HTHREADS / 64];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();
@@ -329,8 +305,7 @@ __global__ __launch_bounds__(64) void ne_finish_kernel(int nblk, const int64_t* 
     uint32_t mn = NE_INF_BITS;
     if (state[0] && state[4])
         for (int j = t; j < nblk; j += 64) mn = min(mn, mpart[j]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+    mn = wave_min(mn);
     if (t != 0) return;
     const int64_t n = totals[0], nan = totals[1];
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);

@@ -96,8 +96,7 @@ __global__ __launch_bounds__(NG_THREADS) void ng_kernel(const int H, const int W
             }
         }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+    c = wave_sum(c);
     if (lane == 0) cnt[w] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -145,11 +144,8 @@ __global__ __launch_bounds__(RQ_THREADS) void rq_range_kernel(const int n, const
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {
-            l[c] = min(l[c], (uint32_t)__shfl_xor((int)l[c], s, 64));
-            h[c] = max(h[c], (uint32_t)__shfl_xor((int)h[c], s, 64));
-        }
+        l[c] = wave_min(l[c]);
+        h[c] = wave_max(h[c]);
         if (lane == 0) slo[w][c] = l[c], shi[w][c] = h[c];
     }
     __syncthreads();

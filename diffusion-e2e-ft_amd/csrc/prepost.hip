@@ -43,37 +43,21 @@ __global__ __launch_bounds__(256) void aa_resample_v_kernel(int h0, int w, int h
 
 // min / max of a flat fp32 buffer in two fixed-order stages (no atomics: reproducible), then out = (x - min) / (max - min) (zeros when max == min)
 __global__ __launch_bounds__(256) void minmax_partial_kernel(long n, const float* __restrict__ x, float* __restrict__ part /* [256][2] */) {
-    __shared__ float smn[4], smx[4];
     float mn = INFINITY, mx = -INFINITY;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float v = x[i];
         mn = fminf(mn, v);
         mx = fmaxf(mx, v);
     }
-    mn = -wave_max(-mn);
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[blockIdx.x * 2] = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
-        part[blockIdx.x * 2 + 1] = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-    }
+    block_minmax(mn, mx, part + blockIdx.x * 2);
 }
 __global__ __launch_bounds__(256) void minmax_final_kernel(int nparts, const float* __restrict__ part, float* __restrict__ mm /* [2] */) {
-    __shared__ float smn[4], smx[4];
     float mn = INFINITY, mx = -INFINITY;
     for (int i = threadIdx.x; i < nparts; i += 256) {
         mn = fminf(mn, part[i * 2]);
         mx = fmaxf(mx, part[i * 2 + 1]);
     }
-    mn = -wave_max(-mn);
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        mm[0] = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
-        mm[1] = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-    }
+    block_minmax(mn, mx, mm);
 }
 __global__ __launch_bounds__(256) void minmax_apply_kernel(long n, const float* __restrict__ x, const float* __restrict__ mm, float* __restrict__ out) {
     const float mn = mm[0], mx = mm[1];

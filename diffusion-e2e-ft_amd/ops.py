@@ -961,12 +961,7 @@ def ssi_loss(pred, target, mask, return_scale_shift=False):
     p = pred.reshape(B, -1).float().contiguous()
     t = target.reshape(B, -1).float().contiguous()
     m = mask.reshape(B, -1).to(torch.uint8).contiguous()
-    lib = _lib.load()
-    nbytes = lib.e2eft_ssi_loss_workspace_bytes(B)
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=p.device)
-    out = torch.empty(1, dtype=torch.float32, device=p.device)
-    ss = torch.empty((B, 2), dtype=torch.float32, device=p.device)
-    check(lib.e2eft_ssi_loss_fwd(B, p.shape[1], _ptr(p), _ptr(t), _ptr(m), _ptr(out), _ptr(ss), _ptr(ws), nbytes, _stream()))
+    out, ss, _ = ssi_loss_fwd_saved(p, t, m)
     return (out[0], ss) if return_scale_shift else out[0]
 
 
@@ -977,12 +972,7 @@ def angular_loss(pred, target, mask):
     p = pred.reshape(B, 3, -1).float().contiguous()
     t = target.reshape(B, 3, -1).float().contiguous()
     m = mask[:, 0].reshape(B, -1).to(torch.uint8).contiguous()
-    lib = _lib.load()
-    nbytes = lib.e2eft_angular_loss_workspace_bytes(B)
-    ws = torch.empty(2, dtype=torch.float64, device=p.device)
-    out = torch.empty(1, dtype=torch.float32, device=p.device)
-    check(lib.e2eft_angular_loss_fwd(B, p.shape[2], _ptr(p), _ptr(t), _ptr(m), _ptr(out), _ptr(ws), nbytes, _stream()))
-    return out[0]
+    return angular_loss_fwd_saved(p, t, m)[0][0]
 
 
 # =========================================================================================================
@@ -1405,18 +1395,21 @@ def ssi_loss_fwd_saved(p, t, m):
 def ssi_loss_bwd(p, t, m, ss, fwd_ws, gout):
     B = p.shape[0]
     dp = torch.empty_like(p)
-    ws = torch.empty(2 * B, dtype=torch.float64, device=p.device)
+    lib = _lib.load()
+    nbytes = lib.e2eft_ssi_loss_bwd_workspace_bytes(B)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=p.device)
     g = gout.reshape(1).float().contiguous()
-    check(_lib.load().e2eft_ssi_loss_bwd(B, p.shape[1], _ptr(p), _ptr(t), _ptr(m), _ptr(ss), _ptr(fwd_ws), _ptr(g), _ptr(dp), _ptr(ws), 16 * B, _stream()))
+    check(lib.e2eft_ssi_loss_bwd(B, p.shape[1], _ptr(p), _ptr(t), _ptr(m), _ptr(ss), _ptr(fwd_ws), _ptr(g), _ptr(dp), _ptr(ws), nbytes, _stream()))
     return dp
 
 
 def angular_loss_fwd_saved(p, t, m):
     """p, t fp32 [B,3,hw], m uint8 [B,hw]"""
     lib = _lib.load()
-    ws = torch.empty(2, dtype=torch.float64, device=p.device)
+    nbytes = lib.e2eft_angular_loss_workspace_bytes(p.shape[0])
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=p.device)
     out = torch.empty(1, dtype=torch.float32, device=p.device)
-    check(lib.e2eft_angular_loss_fwd(p.shape[0], p.shape[2], _ptr(p), _ptr(t), _ptr(m), _ptr(out), _ptr(ws), 16, _stream()))
+    check(lib.e2eft_angular_loss_fwd(p.shape[0], p.shape[2], _ptr(p), _ptr(t), _ptr(m), _ptr(out), _ptr(ws), nbytes, _stream()))
     return out, ws
 
 
@@ -1427,13 +1420,21 @@ def angular_loss_bwd(p, t, m, fwd_ws, gout):
     return dp
 
 
-def sumsq(g, out=None):
-    """fp64 [1] device scalar = sum g^2 over a flat fp32 buffer"""
+def sumsq_workspace(g):
+    """the fp64 workspace `sumsq` needs for g (a caller that keeps one passes it as ws=)"""
+    nbytes = _lib.load().e2eft_sumsq_workspace_bytes(g.numel())
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=g.device)
+
+
+def sumsq(g, out=None, ws=None):
+    """fp64 [1] device scalar = sum g^2 over a flat fp32 buffer; fixed summation order (bit-reproducible)"""
     _check_cuda(g)
     assert g.dtype == torch.float32 and g.is_contiguous()
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=g.device)
-    check(_lib.load().e2eft_sumsq(g.numel(), _ptr(g), _ptr(out), _stream()))
+    if ws is None:
+        ws = sumsq_workspace(g)
+    check(_lib.load().e2eft_sumsq(g.numel(), _ptr(g), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream()))
     return out
 
 

@@ -255,6 +255,7 @@ class FlatAdamW(torch.optim.Optimizer):
             self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
             self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
             self._sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._sumsq_ws = ops.sumsq_workspace(self.flat_grad)             # per-block partials of the gradient norm, sized once
             self._steps = torch.zeros(2, dtype=torch.int64, device=dev)      # {applied, skipped} — advanced by the update kernel itself
             self._coef = torch.zeros(4, dtype=torch.float32, device=dev)
             with torch.no_grad():
@@ -466,7 +467,7 @@ class FlatAdamW(torch.optim.Optimizer):
             self._adopt_grads()
             self._finish_exchange()
             g = self.param_groups[0]
-            sumsq = ops.sumsq(self.flat_grad, out=self._sumsq)     # always: the non-finite guard needs it even without clipping
+            sumsq = ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws)     # always: the non-finite guard needs it even without clipping
             ops.adamw_step_guarded_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, float(g["lr"]) * lr_scale, g["betas"][0], g["betas"][1],
                                     g["eps"], g["weight_decay"], self._steps, self._coef, sumsq, grad_scale=grad_scale / self.world,
                                     max_norm=float(self.max_grad_norm or 0.0))
@@ -483,9 +484,9 @@ class FlatAdamW(torch.optim.Optimizer):
         with ops.on_device_of(self.flat_param):
             self._adopt_grads()
             if not self.sync_grads:
-                return math.sqrt(float(ops.sumsq(self.flat_grad, out=self._sumsq).item()))
+                return math.sqrt(float(ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws).item()))
             self._finish_exchange()
-            return math.sqrt(float(ops.sumsq(self.flat_grad, out=self._sumsq).item())) / self.world
+            return math.sqrt(float(ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws).item())) / self.world
 
     @torch.no_grad()
     def zero_grad(self, set_to_none=None):

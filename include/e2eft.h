@@ -35,7 +35,9 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 #define E2EFT_VERSION 119 /* 0.1.1: backward entry points; 111: test-time ensembling, CLIP towers, sample preparation; 119 later gained one export
-                             (e2eft_attn_f32split_supported) and one option (E2EFT_OPT_F32_SPLIT_ATTN) without a new number */
+                             (e2eft_attn_f32split_supported) and one option (E2EFT_OPT_F32_SPLIT_ATTN) without a new number; so did the
+                             workspace of e2eft_sumsq and the queries e2eft_sumsq_workspace_bytes / e2eft_ssi_loss_bwd_workspace_bytes
+                             (a stale binary is told apart by e2eft_build_id) */
 
 enum {
     E2EFT_OK = 0,
@@ -384,7 +386,12 @@ int e2eft_normal_head(int32_t dt_in, int32_t dt_out, int32_t batch, int32_t hw, 
 /* ------------------------------------------------------------------------------------------------------
  * Task losses (fp32), forward.  Replace training/util/loss.py:13-47 (ScaleAndShiftInvariantLoss) and
  * :51-67 (AngularLoss).  pred/target fp32 NCHW contiguous, mask uint8 [B,1,H,W].
- * ssi workspace: 8 floats per image + 2; out_loss: 1 float on the device.
+ * out_loss: 1 float on the device.  Workspaces (8-byte aligned, sizes from the queries, functions of batch alone; the layout is private):
+ * per-block partial sums, 256 blocks per image at the most, the per-image and global totals, and for ssi the scale/shift when
+ * out_scale_shift is NULL.  A workspace needs no clearing: every word read is written by the same call.  The forward workspace is
+ * what the matching *_bwd call takes as fwd_workspace.  e2eft_ssi_loss_fwd / _bwd, e2eft_angular_loss_fwd / _bwd and e2eft_sumsq
+ * are deterministic: fp64 sums in a fixed order (wave butterfly, waves of a block left to right, the blocks' partials in index
+ * order), no floating-point atomics — the same input gives the same bits on every run, rank and graph replay.
  * ---------------------------------------------------------------------------------------------------- */
 size_t e2eft_ssi_loss_workspace_bytes(int32_t batch);
 int e2eft_ssi_loss_fwd(int32_t batch, int32_t hw, const float* pred, const float* target, const uint8_t* mask,
@@ -456,7 +463,9 @@ int e2eft_depth_head_bwd(int32_t dt_x, int32_t dt_y, int64_t pixels, int32_t ldx
 int e2eft_normal_head_bwd(int32_t dt_x, int32_t dt_y, int32_t batch, int32_t hw, int32_t ldx, int32_t lddx, int32_t cpad,
                           int32_t clamp, float sign, const void* x, const void* dy, void* dx, void* stream);
 /* loss gradients w.r.t. pred (training/util/loss.py autograd, including the chain through the closed-form scale/shift):
- * fwd_workspace = the workspace the matching *_fwd call filled; grad_out = 1 float on the device; workspace: 2 doubles/image */
+ * fwd_workspace = the workspace the matching *_fwd call filled; grad_out = 1 float on the device; workspace: per-block partials of
+ * the two per-image sums (e2eft_ssi_loss_bwd_workspace_bytes, 8-byte aligned, no clearing needed) */
+size_t e2eft_ssi_loss_bwd_workspace_bytes(int32_t batch);
 int e2eft_ssi_loss_bwd(int32_t batch, int32_t hw, const float* pred, const float* target, const uint8_t* mask,
                        const float* scale_shift, const void* fwd_workspace, const float* grad_out, float* dpred,
                        void* workspace, size_t ws_bytes, void* stream);
@@ -685,10 +694,12 @@ int e2eft_ensemble_depth_finish(int64_t npix, const float* minmax, float* pred, 
 int e2eft_ensemble_normals(int32_t n_img, int64_t hw, const float* x, float* unit, double* err, void* workspace, size_t ws_bytes,
                            void* stream);
 /* Flat-buffer optimizer step (torch.optim.AdamW + accelerator.clip_grad_norm_, train.py:561-566): all trainable
- * parameters / gradients / moments are single fp32 buffers.  e2eft_sumsq: out[0] = sum g^2 (fp64).  e2eft_adamw_step
+ * parameters / gradients / moments are single fp32 buffers.  e2eft_sumsq: out[0] = sum g^2 (fp64), per-block partials in `workspace`
+ * (e2eft_sumsq_workspace_bytes(n), 8-byte aligned, no clearing needed) summed by one block in a fixed order.  e2eft_adamw_step
  * scales the gradient by grad_scale * min(1, max_norm / (sqrt(grad_sumsq) * grad_scale + 1e-6)) when grad_sumsq != NULL
  * and max_norm > 0 (no host synchronisation), then applies decoupled-decay Adam with bias correction for `step` (>= 1). */
-int e2eft_sumsq(int64_t n, const float* g, double* out, void* stream);
+size_t e2eft_sumsq_workspace_bytes(int64_t n);
+int e2eft_sumsq(int64_t n, const float* g, double* out, void* workspace, size_t ws_bytes, void* stream);
 int e2eft_adamw_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int32_t step, const double* grad_sumsq, float grad_scale,
                      float max_norm, void* stream);

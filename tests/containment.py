@@ -119,11 +119,11 @@ def poisoned_allocations(fill, device_filter=_on_gpu):
         torch.Tensor.new_empty = saved["new_empty"]
 
 
-def check_two_fills(run, check=None, inexact=(), device_filter=_on_gpu, what=""):
+def check_two_fills(run, check=None, device_filter=_on_gpu, what=""):
     """run(fill) -> (outputs, guards): outputs {name: tensor}; guards a list of (buffer, view) or (buffer, view, allowed) of EVERY guarded operand, inputs included.
     run builds its operands with guarded(..., fill) and makes the call; it runs under poisoned_allocations(fill).  Asserted, per fill: every output finite, check(name,
     tensor) (the comparison with the reference), every guard's bands intact; then across the fills: torch.equal for every output — the two runs have identical
-    layout and addresses — except those named in `inexact` {name: compare(a, b)} (reductions through floating atomics), which get their own comparison.
+    layout and addresses.
     -> the outputs of the first fill."""
     results = {}
     for fill in FILLS:
@@ -143,9 +143,7 @@ def check_two_fills(run, check=None, inexact=(), device_filter=_on_gpu, what="")
     signed = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}      # (comparisons of the wide unsigned types are not implemented everywhere)
     for name in a:
         ta, tb = (t.view(signed[t.dtype]) if t.dtype in signed else t for t in (a[name], b[name]))
-        if name in inexact:
-            inexact[name](a[name], b[name])
-        elif not torch.equal(ta, tb):
+        if not torch.equal(ta, tb):
             ne = ta != tb
             raise AssertionError("%s: output %s depends on the fill: %d of %d entries differ between the 0xFF and the 0x00 run, first at %s"
                                  % (what, name, int(ne.sum()), ne.numel(), tuple(ne.nonzero()[0].tolist())))

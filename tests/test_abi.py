@@ -90,6 +90,28 @@ def test_argument_validation_without_gpu():
     assert lib.e2eft_groupnorm_workspace_bytes(ctypes.byref(g)) > 0
 
 
+def test_loss_and_sumsq_workspaces_without_gpu():
+    """the workspace queries of the losses and of e2eft_sumsq: 0 for an empty problem, monotone; a workspace one byte short is refused before any device call"""
+    from diffusion_e2e_ft_amd import _lib
+    lib = _lib.load()
+    queries = (lib.e2eft_ssi_loss_workspace_bytes, lib.e2eft_angular_loss_workspace_bytes, lib.e2eft_ssi_loss_bwd_workspace_bytes)
+    for fn in queries:
+        assert fn(0) == 0 and fn(-3) == 0
+        sizes = [fn(b) for b in (1, 2, 3, 8, 64, 65535)]
+        assert sizes[0] > 0 and sizes == sorted(sizes) and len(set(sizes)) == len(sizes), sizes
+    assert lib.e2eft_sumsq_workspace_bytes(0) == 0 and lib.e2eft_sumsq_workspace_bytes(-1) == 0
+    sizes = [lib.e2eft_sumsq_workspace_bytes(n) for n in (1, 256, 257, 10007, 2048 * 256, 1 << 33)]
+    assert sizes[0] == 8 and sizes == sorted(sizes) and sizes[-1] == sizes[-2] == 2048 * 8, sizes
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    n = 10007
+    assert lib.e2eft_sumsq(n, p, p, p, lib.e2eft_sumsq_workspace_bytes(n) - 1, None) == 2 and b"workspace" in lib.e2eft_last_error()
+    assert lib.e2eft_ssi_loss_bwd(3, 2240, p, p, p, p, p, p, p, p, lib.e2eft_ssi_loss_bwd_workspace_bytes(3) - 1, None) == 2
+    assert b"workspace" in lib.e2eft_last_error()
+    assert lib.e2eft_ssi_loss_fwd(3, 2240, p, p, p, p, p, p, lib.e2eft_ssi_loss_workspace_bytes(3) - 1, None) == 2
+    assert lib.e2eft_angular_loss_fwd(3, 2240, p, p, p, p, p, lib.e2eft_angular_loss_workspace_bytes(3) - 1, None) == 2
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -448,3 +448,109 @@ def test_flat_adamw_matches_torch(ops, dev):
     acc = torch.ones(1000, device=dev)
     ops.cast_(y, acc, mul=2.0, accumulate=True)
     assert torch.allclose(acc.cpu(), 1 + 2 * x.to(torch.bfloat16).float())
+
+
+# ------------------------------------------------------------------------------------------------ fixed-order reductions: losses, sumsq
+def _loss_case(B, H, W, seed, mask_out=None):
+    """Inputs whose reference gradient is well conditioned at every size, so the parity tolerances of the small cases hold for a million pixels too:
+    SSI: target = 0.6 pred + 0.2 + e with |e| in [0.025, 0.075] and a random sign, so after the least-squares fit every residual stays away from 0 — sign(r),
+    the loss's derivative, jumps there, and one pixel whose sign differs between two fp32 evaluations is an O(1) relative gradient error.
+    Angular: the target is the prediction rotated by an angle in [0.2, 1.2] about a random perpendicular axis, so the dot product stays in [0.36, 0.99] —
+    1 / sqrt(1 - d^2) is unbounded at |d| = 1, where one ulp of d changes it by tens of percent."""
+    g = _g(seed)
+    pred = torch.rand(B, 1, H, W, generator=g) * 2 - 1
+    e = (0.025 + 0.05 * torch.rand(B, 1, H, W, generator=g)) * (torch.randint(0, 2, (B, 1, H, W), generator=g) * 2 - 1)
+    tgt = 0.6 * pred + 0.2 + e
+    mask = torch.rand(B, 1, H, W, generator=g) > 0.05
+    if mask_out is not None:
+        mask[mask_out] = False
+    nrm = TF.normalize(torch.randn(B, 3, H, W, generator=g), dim=1)
+    axis = TF.normalize(torch.cross(nrm, torch.randn(B, 3, H, W, generator=g), dim=1), dim=1)
+    ang = 0.2 + torch.rand(B, 1, H, W, generator=g)
+    nt = TF.normalize(torch.cos(ang) * nrm + torch.sin(ang) * axis, dim=1)
+    return pred, tgt, mask, nrm, nt
+
+
+# one block and a partial wave; two blocks per image, one image fully masked (the containment case); the 256-block cap and a second grid-stride trip
+@pytest.mark.parametrize("B,H,W,mask_out", [(3, 1, 37, None), (3, 40, 56, 2), (2, 1, 256 * 2048 + 2049, None)])
+def test_losses_bit_equal_run_to_run_and_match_reference(ops, dev, B, H, W, mask_out):
+    """the fp64 sums of the loss kernels run in a fixed order: four calls give the same bits (loss, scale/shift, gradient), and they are the reference's values
+    within the tolerances of test_containment_gpu.py::test_losses_forward_and_backward_poisoned"""
+    from oracle.losses_ref import angular_loss_ref, compute_scale_and_shift_masked_ref, ssi_loss_ref
+    pred, tgt, mask, nrm, nt = _loss_case(B, H, W, 1000 + W, mask_out)
+    pr, nr = _ref(pred), _ref(nrm)
+    ref_s, ref_a = ssi_loss_ref(pr, tgt, mask), angular_loss_ref(nr, nt, mask)
+    (3.0 * ref_s).backward()
+    ref_a.backward()
+    ref_ss = torch.stack(compute_scale_and_shift_masked_ref(pred.squeeze(1), tgt.squeeze(1), mask.squeeze(1)), dim=1)
+    p, t, m = pred.to(dev).view(B, -1), tgt.to(dev).view(B, -1), mask.to(dev).view(B, -1).to(torch.uint8)
+    n_, nt_ = nrm.to(dev).view(B, 3, -1), nt.to(dev).view(B, 3, -1)
+    gs, ga = torch.full((1,), 3.0, device=dev), torch.ones(1, device=dev)
+    runs = []
+    for _ in range(4):
+        loss, ss, ws = ops.ssi_loss_fwd_saved(p, t, m)
+        dp = ops.ssi_loss_bwd(p, t, m, ss, ws, gs)
+        la, wsa = ops.angular_loss_fwd_saved(n_, nt_, m)
+        dn = ops.angular_loss_bwd(n_, nt_, m, wsa, ga)
+        runs.append(dict(ssi=loss, scale_shift=ss, ssi_dpred=dp, angular=la, angular_dpred=dn))
+    for r in runs[1:]:
+        for name in r:
+            assert torch.equal(r[name], runs[0][name]), name
+    r = runs[0]
+    print("ssi %.9g ref %.9g | angular %.9g ref %.9g | scale_shift err %.3g | dpred err %.3g %.3g" % (
+        r["ssi"].item(), ref_s.item(), r["angular"].item(), ref_a.item(), rel_err(r["scale_shift"], ref_ss), rel_err(r["ssi_dpred"].view(B, 1, H, W), pr.grad),
+        rel_err(r["angular_dpred"].view(B, 3, H, W), nr.grad)))
+    assert abs(r["ssi"].item() - ref_s.item()) <= 2e-5 * max(1.0, abs(ref_s.item()))
+    assert abs(r["angular"].item() - ref_a.item()) <= 2e-5
+    assert rel_err(r["scale_shift"], ref_ss) <= 2e-5
+    assert rel_err(r["ssi_dpred"].view(B, 1, H, W), pr.grad) < 2e-4
+    assert rel_err(r["angular_dpred"].view(B, 3, H, W), nr.grad) < 2e-4
+    if mask_out is not None:
+        assert r["ssi_dpred"][mask_out].abs().max().item() == 0 and r["angular_dpred"][mask_out].abs().max().item() == 0
+
+
+# one thread; one partial block; a partial wave; the 2048-block cap and a second grid-stride trip
+@pytest.mark.parametrize("n", [1, 255, 11, 2048 * 256 * 2 + 77])
+def test_sumsq_bit_equal_in_fp64(ops, dev, n):
+    """+-2^e (1 + u), e uniform in [-30, 30]: the squares span 120 binades, so the last bits of an fp64 sum depend on the order of the additions.  The order is
+    fixed: four calls, and a fifth with a workspace at another address, give the same 64 bits"""
+    g = _g(n % 1000)
+    e = torch.randint(-30, 31, (n,), generator=g).float()
+    x = torch.exp2(e) * (1 + torch.rand(n, generator=g)) * (torch.randint(0, 2, (n,), generator=g).float() * 2 - 1)
+    ref = torch.sum(x.double() ** 2).item()
+    xd = x.to(dev)
+    ws = ops.sumsq_workspace(xd)
+    outs = [ops.sumsq(xd, ws=ws).view(torch.int64).item() for _ in range(4)]
+    assert len(set(outs)) == 1, outs
+    got = ops.sumsq(xd, ws=ws).item()
+    assert abs(got - ref) <= 1e-6 * ref, (got, ref)
+    ws2 = ops.sumsq_workspace(xd)
+    assert ws2.data_ptr() != ws.data_ptr()
+    assert ops.sumsq(xd, ws=ws2).view(torch.int64).item() == outs[0]
+    assert ops.sumsq(xd).view(torch.int64).item() == outs[0]          # the workspace the wrapper allocates itself
+
+
+def test_losses_and_sumsq_replay_in_a_captured_graph(ops, dev):
+    """ssi_loss_fwd_saved + ssi_loss_bwd + sumsq captured in one graph (one stream): both replays equal the eager results bit for bit"""
+    B, H, W = 3, 40, 56
+    pred, tgt, mask, _, _ = _loss_case(B, H, W, 77, 2)
+    p, t, m = pred.to(dev).view(B, -1), tgt.to(dev).view(B, -1), mask.to(dev).view(B, -1).to(torch.uint8)
+    gout = torch.full((1,), 3.0, device=dev)
+    x = torch.randn(2243, generator=_g(78)).to(dev)
+
+    def call():
+        loss, ss, ws = ops.ssi_loss_fwd_saved(p, t, m)
+        return loss, ss, ops.ssi_loss_bwd(p, t, m, ss, ws, gout), ops.sumsq(x)
+
+    eager = [o.clone() for o in call()]
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = call()
+    for _ in range(2):
+        for o in outs:
+            o.fill_(7.0)          # a replay has to write every output again
+        graph.replay()
+        torch.cuda.synchronize()
+        for o, e in zip(outs, eager):
+            assert torch.equal(o, e)

@@ -2,7 +2,7 @@
 every tensor operand the Python entry accepts as a view IS a guarded view (inputs, residuals, out=), and torch.empty & co. hand out tensors full of the fill, so
 workspaces, partial-sum slabs, pad columns and self-allocated outputs start as NaN / as zero.  Asserted per case:
   (a) the output is finite and within the tolerance of the family's own parity test against the same fp64 CPU reference;
-  (b) the outputs of the two runs are torch.equal (identical layout and addresses; see INEXACT below for the exceptions);
+  (b) the outputs of the two runs are torch.equal (identical layout and addresses);
   (c) the guard bands of every guarded buffer, inputs included, still hold the fill, outside the allowed write set;
   (d) the kernel the case is meant to reach took the launch.  The library names a launch (ops._last_kernel(), e2eft_debug_*_launches) for igemm2 / igemm5 / igemm6,
       narrow.hip, convin.hip, the fp32 split routes and the two fp32 attention kernels: those cases assert the name (operand path and wave count of igemm2 included).
@@ -30,12 +30,8 @@ output of its own that must be all zero:
   e2eft_randn_fill, e2eft_pyramid_noise   "channels c..ldy untouched"                          no exception at all: guarded channel slices, bands intact
 Every other case allows the logical extent only.
 
-INEXACT — outputs exempt from bit-equality (b) because they are reduced through floating-point atomics, whose order differs from launch to launch; they are compared
-within the tolerance of their own parity test instead:
-  ssi_loss / ssi_loss_bwd          csrc/loss.hip block_atomic_add<5> / <2> (double atomicAdd into the per-image sums and the accumulator), csrc/bwd.hip ssi_bwd_sums_kernel
-  angular_loss / angular_loss_bwd  csrc/loss.hip block_atomic_add<2> (the backward reads the forward's accumulator)
-  sumsq                            csrc/bwd.hip sumsq_kernel (double atomicAdd of the block sums)
-The other atomicAdd calls of csrc/ are integer and exact: the histograms of dataprep.hip, normaleval.hip and hypersimprep.hip, the valid-pixel counts of evalprep.hip and
+No output is exempt from (b): no reduction of csrc/ goes through floating-point atomics (the losses and sumsq sum per-block partials in a fixed order).
+The atomicAdd calls of csrc/ are integer and exact: the histograms of dataprep.hip, normaleval.hip and hypersimprep.hip, the valid-pixel counts of evalprep.hip and
 normalprep.hip, and the per-frame statistics of hypersimprep.hip (unsigned 64-bit sums next to atomicMin / atomicMax)."""
 import ctypes
 import math
@@ -913,10 +909,7 @@ def test_flat_optimizer_kernels_on_the_interior_of_a_guarded_buffer(ops, dev, ta
             else:
                 assert rel_err(t, ref[name]) < 2e-6, (name, rel_err(t, ref[name]))
 
-        def sumsq_close(a, b):      # INEXACT: double atomicAdd of the block sums
-            assert abs(a.item() - b.item()) < 1e-6 * ss_ref
-
-        check_two_fills(run, check, inexact=dict(sumsq=sumsq_close), what="flat optimizer kernels misaligned=%s" % mis)
+        check_two_fills(run, check, what="flat optimizer kernels misaligned=%s" % mis)
 
 
 # ================================================================================================ entries that allocate their dense outputs themselves: poison only
@@ -955,14 +948,7 @@ def test_losses_forward_and_backward_poisoned(ops, dev):
         else:
             assert rel_err(t.view(B, 3, H, W), nr.grad) < 2e-4
 
-    def close(rel):
-        def cmp(a, b):
-            assert rel_err(a, b) <= rel, rel_err(a, b)
-        return cmp
-
-    # INEXACT: everything here is a function of double-precision atomic sums
-    check_two_fills(run, check, inexact=dict(ssi=close(2e-5), ssi_public=close(2e-5), angular=close(2e-5), angular_public=close(2e-5), ssi_dpred=close(2e-4), angular_dpred=close(2e-4)),
-                    what="losses")
+    check_two_fills(run, check, what="losses")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
