@@ -400,8 +400,9 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(long n, float* __res
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void cast_kernel(long n, float mul, int accumulate, const TI* __restrict__ x, TO* __restrict__ y) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        float v = to_f(x[i]) * mul;
-        if (accumulate) v += to_f(y[i]);
+        // accumulate: ONE rounding of y + x * mul (a separate product overflows where the sum does not, loses bits below the normal range, and its rounding
+        // error survives a cancellation against y)
+        const float v = accumulate ? __builtin_fmaf(to_f(x[i]), mul, to_f(y[i])) : to_f(x[i]) * mul;
         y[i] = from_f<TO>(v);
     }
 }
@@ -598,8 +599,9 @@ extern "C" int e2eft_adamw_step(int64_t n, float* param, const float* grad, floa
                                 float eps, float weight_decay, int32_t step, const double* grad_sumsq, float grad_scale, float max_norm, void* stream) {
     E2EFT_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step > 0, "adamw: bad args");
     hipStream_t s = (hipStream_t)stream;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    // in double and rounded once, as adamw_prepare_kernel does: half an fp32 ulp of beta2^step next to 1 is 1.5e-5 of 1 - beta2^step at step 2
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, s, (long)n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bc1,
                        bc2s, grad_sumsq, grad_scale, max_norm);
     return check_launch("adamw");

@@ -697,7 +697,10 @@ int e2eft_ensemble_normals(int32_t n_img, int64_t hw, const float* x, float* uni
  * parameters / gradients / moments are single fp32 buffers.  e2eft_sumsq: out[0] = sum g^2 (fp64), per-block partials in `workspace`
  * (e2eft_sumsq_workspace_bytes(n), 8-byte aligned, no clearing needed) summed by one block in a fixed order.  e2eft_adamw_step
  * scales the gradient by grad_scale * min(1, max_norm / (sqrt(grad_sumsq) * grad_scale + 1e-6)) when grad_sumsq != NULL
- * and max_norm > 0 (no host synchronisation), then applies decoupled-decay Adam with bias correction for `step` (>= 1). */
+ * and max_norm > 0 (no host synchronisation), then applies decoupled-decay Adam with bias correction for `step` (>= 1).
+ * Hyper-parameters travel as fp32: float32(0.999) is 1.29e-5 * (1 - beta2) above 0.999, so exp_avg_sq is systematically 1.29e-5
+ * relative below what torch.optim.AdamW computes from the Python double, and the update about 6.4e-6 relative above.  Both entry
+ * points compute 1 - beta1^step and sqrt(1 - beta2^step) in double from the fp32 betas and round once. */
 size_t e2eft_sumsq_workspace_bytes(int64_t n);
 int e2eft_sumsq(int64_t n, const float* g, double* out, void* workspace, size_t ws_bytes, void* stream);
 int e2eft_adamw_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
