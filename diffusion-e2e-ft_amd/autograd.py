@@ -142,6 +142,14 @@ def grad_sink(*params):
     return None if owner is None else owner._claim([t[1] for t in tags], params)
 
 
+def _from_sink(sink, t):
+    """t: a gradient whose producer was handed the sink's flat slot as its output (`out=sink[0]`).  The gradient is the sink's views; a fallback path that produced t
+    elsewhere costs one copy into the slot instead of AccumulateGrad's add.  -> the views, one per parameter of the sink"""
+    if t.data_ptr() != sink[0].data_ptr():
+        sink[0].view(t.shape).copy_(t)
+    return sink[1]
+
+
 def cached(owner, name, params, builder):
     cache = owner.__dict__.setdefault("_e2eft_cache", {})
     k = _key(*params)
@@ -362,9 +370,7 @@ class _Conv2dFn(torch.autograd.Function):
             # the gradient is handed to autograd in the PARAMETER's stride order (OIHW contiguous): AccumulateGrad then adds / stores it
             # without a strided pass, and a DistributedDataParallel wrap finds "grad strides == bucket view strides"
             if wsink is not None:
-                if dwp.data_ptr() != wsink[0].data_ptr():      # a fallback path produced it elsewhere: one copy instead of AccumulateGrad's add
-                    wsink[0].view(dwp.shape).copy_(dwp)
-                dw = wsink[1][0]
+                dw = _from_sink(wsink, dwp)[0]
             elif kh == 1 and kw == 1:
                 dw = dwp[:, :Ci].reshape(Co, Ci, 1, 1)
                 dw = dw if dw.dtype == weight.dtype else dw.to(weight.dtype)
@@ -480,9 +486,7 @@ class _LinearFn(torch.autograd.Function):
                 xT = ops.transpose(_rows(xp), rows_pad=nsplit * kc)     # [kp, Mp]
                 dw = ops.gemm_splitk(gT, xT, nsplit, kc, alpha=alpha)   # [N, kp]
             if wsink is not None:
-                if dw.data_ptr() != wsink[0].data_ptr():
-                    wsink[0].view(N, K).copy_(dw)
-                dws = list(wsink[1])
+                dws = list(_from_sink(wsink, dw))      # (dw is [N, kp] with kp == K here)
             else:
                 o = 0
                 for i, wgt in enumerate(weights):
@@ -517,6 +521,20 @@ def linear(x, weights, bias=None, residual=None, alpha=1.0, owner=None, name="w"
 
 
 # ------------------------------------------------------------------------------------------------------------
+def _groupnorm_bwd_tail(psrc, x, x2, gamma, beta, meta, g, ws, need_dx, need_g, need_b, add):
+    """The end of every backward through a GroupNorm: FlatAdamW's slots for gamma / beta (psrc: the Parameter objects, see _LinearFn), e2eft_groupnorm_bwd_add of the
+    gradient g of the norm's output, and the parameter gradients — the slots' views when the kernel wrote there.  -> (dx or None, dgamma, dbeta)"""
+    groups, eps, silu = meta
+    dt = x.dtype
+    gs = grad_sink(psrc[0]) if (need_g and need_b and gamma.dtype == torch.float32) else None
+    bs = grad_sink(psrc[1]) if (gs is not None and beta.dtype == torch.float32) else None
+    dx, dg, db = ops.groupnorm_bwd(x, x2, _vec(gamma, dt), _vec(beta, dt), groups, eps, silu, g, ws, need_dx=need_dx, need_dparams=need_g or need_b,
+                                   dx_add=add, dg_out=None if gs is None else gs[0], db_out=None if bs is None else bs[0])
+    dgam = None if not need_g else gs[1][0] if gs is not None else dg.to(gamma.dtype)
+    dbet = None if not need_b else bs[1][0] if bs is not None else db.to(beta.dtype)
+    return dx, dgam, dbet
+
+
 class _GroupNormFn(torch.autograd.Function):
     """GroupNorm(+SiLU).  split=True additionally returns an alias of x for the skip path of a residual block: the gradient that
     comes back over it is added inside the backward apply kernel (e2eft_groupnorm_bwd_add) instead of by a separate torch add."""
@@ -535,25 +553,17 @@ class _GroupNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, x2, gamma, beta, ws = ctx.saved_tensors
-        groups, eps, silu = ctx.meta
-        dt = x.dtype
         need = ctx.needs_input_grad
         c1 = x.shape[3]
         Cc = c1 + (0 if x2 is None else x2.shape[3])
         want_dx = need[0] or (x2 is not None and need[1])
-        want_p = need[2] or need[3]
         if dy is None:     # only the skip path was used downstream
             return dskip, None, None, None, None, None, None, None, None, None
         g = _dense_nhwc(dy, Cc)
         add = _dense_nhwc(dskip, Cc) if (dskip is not None and need[0] and x2 is None) else None
-        gs = grad_sink(ctx.psrc[0]) if (need[2] and need[3] and gamma.dtype == torch.float32) else None
-        bs = grad_sink(ctx.psrc[1]) if (gs is not None and beta.dtype == torch.float32) else None
-        dx, dg, db = ops.groupnorm_bwd(x, x2, _vec(gamma, dt), _vec(beta, dt), groups, eps, silu, g, ws, need_dx=want_dx, need_dparams=want_p,
-                                       dx_add=add, dg_out=None if gs is None else gs[0], db_out=None if bs is None else bs[0])
+        dx, dgam, dbet = _groupnorm_bwd_tail(ctx.psrc, x, x2, gamma, beta, ctx.meta, g, ws, want_dx, need[2], need[3], add)
         d1 = dx[..., :c1] if (need[0] and dx is not None) else None
         d2 = dx[..., c1:] if (x2 is not None and need[1]) else None
-        dgam = None if not need[2] else gs[1][0] if gs is not None else dg.to(gamma.dtype)
-        dbet = None if not need[3] else bs[1][0] if bs is not None else db.to(beta.dtype)
         return d1, d2, dgam, dbet, None, None, None, None, None, None
 
 
@@ -600,7 +610,6 @@ class _NormConvSplitFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, gamma, beta, ws = ctx.saved_tensors
-        groups, eps, silu = ctx.meta
         conv = ctx.conv
         dt = x.dtype
         need = ctx.needs_input_grad
@@ -615,13 +624,7 @@ class _NormConvSplitFn(torch.autograd.Function):
         if need[0] or need[1] or need[2]:
             dhn = ops.conv2d_dgrad(dyp, packed_conv_weight_dgrad(conv, dt), (B, H, W, c1), 0, 3, 3, 1, (1, 1, 1, 1), None, 1.0)
             add = _dense_nhwc(dskip, c1) if (dskip is not None and need[0]) else None
-            want_p = need[1] or need[2]
-            gs = grad_sink(ctx.psrc[0]) if (need[1] and need[2] and gamma.dtype == torch.float32) else None
-            bs = grad_sink(ctx.psrc[1]) if (gs is not None and beta.dtype == torch.float32) else None
-            dx, dg, db = ops.groupnorm_bwd(x, None, _vec(gamma, dt), _vec(beta, dt), groups, eps, silu, dhn, ws, need_dx=need[0], need_dparams=want_p,
-                                           dx_add=add, dg_out=None if gs is None else gs[0], db_out=None if bs is None else bs[0])
-            dgam = None if not need[1] else gs[1][0] if gs is not None else dg.to(gamma.dtype)
-            dbet = None if not need[2] else bs[1][0] if bs is not None else db.to(beta.dtype)
+            dx, dgam, dbet = _groupnorm_bwd_tail(ctx.psrc, x, None, gamma, beta, ctx.meta, dhn, ws, need[0], need[1], need[2], add)
             if not need[0]:
                 dx = None
         elif dskip is not None:

@@ -5,6 +5,7 @@ last dim is contiguous and whose pixel stride `ld = t.stride(-2)` may exceed C (
 Every function enqueues on torch's current stream and raises RuntimeError on any library error; there is no
 fallback path."""
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 
@@ -317,20 +318,88 @@ def f32_split_weight(w_packed, taps, c):
     return wsp, inv
 
 
-def _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, ldo, ldr, up_to=None):
-    """descriptor of a launch that reads split planes of c1 fp32 channels (pixel stride 2 c1); up_to = (hl, wl): the fused 2x upsample of e2eft_upconv2x_fwd_f32split"""
+# ---------------------------------------------------------------------------------------------------------
+# the descriptors of the C ABI (include/e2eft.h): each struct is created in one place
+def _conv_out_hw(hl, wl, kh, kw, stride, pad):
+    """output grid of a convolution over the logical (upsampled) hl x wl input, pad = (top, bottom, left, right)"""
     pt, pb, pl, pr = pad
+    return (hl + pt + pb - kh) // stride + 1, (wl + pl + pr - kw) // stride + 1
+
+
+def _conv_desc(x, x2, cout, kh, kw, stride, pad, up_to, alpha, ldo=0, ldr=0, ldw=0, dtype=None):
+    """x: the NHWC tensor [B,H,W,c1] the launch reads, or — for operands that are no such tensor (split planes, the shape a gradient will have) — the geometry
+    (B, H, W, c1, ldx1) with `dtype` the library's id; x2: the second source likewise, a tensor, (c2, ldx2) or None.  pad = (top, bottom, left, right), up_to = (hl, wl)
+    of a fused nearest upsample; hout / wout follow from them.  ldo / ldr / ldw stay 0 for the entries that take those strides as arguments of their own."""
+    if isinstance(x, torch.Tensor):
+        (B, H, W, c1), ldx1, dtype = x.shape, _nhwc_ld(x), dtype_id(x.dtype)
+    else:
+        B, H, W, c1, ldx1 = x
+    if isinstance(x2, torch.Tensor):
+        x2 = (x2.shape[3], _nhwc_ld(x2))
     hl, wl = (H, W) if up_to is None else up_to
     d = ConvDesc()
-    d.dtype = _lib.F32
+    d.dtype = dtype
     d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, hl, wl
-    d.c1, d.ldx1, d.c2, d.ldx2 = c1, 2 * c1, 0, 0
-    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-    d.hout = (hl + pt + pb - kh) // stride + 1
-    d.wout = (wl + pl + pr - kw) // stride + 1
-    d.cout, d.ldo, d.ldr, d.ldw = cout, ldo, ldr, kh * kw * 3 * c1
-    d.alpha = 1.0
+    d.c1, d.ldx1 = c1, ldx1
+    d.c2, d.ldx2 = (0, 0) if x2 is None else x2
+    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pad[0], pad[2]
+    d.hout, d.wout = _conv_out_hw(hl, wl, kh, kw, stride, pad)
+    d.cout, d.ldo, d.ldr, d.ldw = cout, ldo, ldr, ldw
+    d.alpha = alpha
     return d
+
+
+def _gemm_desc(dtype, m, n, k, lda, ldw, ldo, ldr=0, nz=(1, 1), sa=(0, 0), sw=(0, 0), so=(0, 0), bias_along_m=False, alpha=1.0):
+    """dtype: the library's id; nz = (outer, inner) batch counts, sa / sw / so = (outer, inner) batch strides in elements (the residual is not batched)"""
+    d = GemmDesc()
+    d.dtype = dtype
+    d.m, d.n, d.k = m, n, k
+    d.lda, d.ldw, d.ldo, d.ldr = lda, ldw, ldo, ldr
+    d.nzo, d.nzi = nz
+    d.sa_o, d.sa_i = sa
+    d.sw_o, d.sw_i = sw
+    d.so_o, d.so_i = so
+    d.sr_o = d.sr_i = 0
+    d.bias_along_m = 1 if bias_along_m else 0
+    d.alpha = alpha
+    return d
+
+
+def _gn_desc(x, x2, groups, eps, silu, ldy):
+    B, H, W, c1 = x.shape
+    d = GroupNormDesc()
+    d.dtype = dtype_id(x.dtype)
+    d.batch, d.hw = B, H * W
+    d.c1, d.ldx1 = c1, _nhwc_ld(x)
+    d.c2, d.ldx2 = (x2.shape[3], _nhwc_ld(x2)) if x2 is not None else (0, 0)
+    d.groups, d.ldy, d.silu, d.eps = groups, ldy, 1 if silu else 0, eps
+    return d
+
+
+def _gn_workspace(d, device, who="groupnorm", bwd=False):
+    """-> (fp32 workspace tensor of the norm `d` describes, its size in bytes as the library counts it); bwd: the backward's.  0 bytes is the library's refusal."""
+    lib = _lib.load()
+    nbytes = (lib.e2eft_groupnorm_bwd_workspace_bytes if bwd else lib.e2eft_groupnorm_workspace_bytes)(C.byref(d))
+    if nbytes == 0:
+        raise RuntimeError("%s: %s" % (who, lib.e2eft_last_error().decode()))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+
+
+def _gn_stats_args(s):
+    """optional GnStats of a norm's source -> the (partial, nslabs) argument pair; (null, 0): the norm makes its own statistics pass"""
+    return (_ptr(s.partial), s.nslabs) if s else (C.c_void_p(0), 0)
+
+
+def _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, ldo, ldr, up_to=None, alpha=1.0):
+    """descriptor of a launch that reads split planes of c1 fp32 channels (pixel stride 2 c1); up_to = (hl, wl): the fused 2x upsample of e2eft_upconv2x_fwd_f32split"""
+    return _conv_desc((B, H, W, c1, 2 * c1), None, cout, kh, kw, stride, pad, up_to, alpha, ldo, ldr, kh * kw * 3 * c1, dtype=_lib.F32)
+
+
+def _f32split_takes(dtype, cin, ldw, taps, alpha, bias, up_to=None, rowadd=None, sk=0):
+    """What every fp32 convolution must meet to go through split planes, whichever wrapper asks (conv2d, conv2d_norm_split, conv2d_dgrad), before the library judges its
+    descriptor: no fused upsample, row vector or split-K; an alpha other than 1 only without a bias; weight rows of exactly taps * cin columns (f32_split_weight splits
+    the packed tensor as it lies).  What a site asks beyond these — channel multiples: conv2d_norm_split leaves the input's to the library's query — stays at the site."""
+    return dtype == torch.float32 and not sk and up_to is None and rowadd is None and (alpha == 1.0 or bias is None) and ldw == taps * cin
 
 
 def f32split_shape_ok(B, H, W, c1, cout, kh=3, kw=3, stride=1, pad=(1, 1, 1, 1)):
@@ -365,25 +434,20 @@ def groupnorm_fwd_split_ws(x, gamma, beta, groups, eps, silu=False, s1=None):
     planes = torch.empty((B, H, W, 2 * c1), dtype=torch.float16, device=x.device)
     scale = torch.empty(4, dtype=torch.float32, device=x.device)
     d = _gn_desc(x, None, groups, eps, silu, c1)
-    lib = _lib.load()
-    nbytes = lib.e2eft_groupnorm_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError("groupnorm: %s" % lib.e2eft_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    ws, nbytes = _gn_workspace(d, x.device)
     if not GN_STATS_ENABLED:
         s1 = None
     with _timed("groupnorm", 0.0, 2.0 * B * H * W * c1 * 4, label="gn->split B%d %dx%d C%d" % (B, H, W, c1)):
-        check(lib.e2eft_groupnorm_fwd_split(C.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(planes), 2 * c1, _ptr(scale), _ptr(s1.partial) if s1 else C.c_void_p(0),
-                                            s1.nslabs if s1 else 0, _ptr(ws), nbytes, _stream()))
+        check(_lib.load().e2eft_groupnorm_fwd_split(C.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(planes), 2 * c1, _ptr(scale), *_gn_stats_args(s1), _ptr(ws), nbytes,
+                                                    _stream()))
     return planes, scale, ws
 
 
 def _f32split_conv_desc(B, H, W, c1, w_packed, bias, cout, residual, alpha, out, geom, sources):
     """The descriptor of e2eft_conv2d_fwd_f32split for an fp32 convolution (geom = kh, kw, stride, pads; no fused upsample) of [B,H,W,c1], or None when the route does
     not take it.  Host arithmetic only: nothing is launched.  sources: the fp32 tensors that will be split (none when the planes come from a producer)."""
-    d = _f32split_desc(B, H, W, c1, cout, *geom, _nhwc_ld(out), _nhwc_ld(residual) if residual is not None else 0)
+    d = _f32split_desc(B, H, W, c1, cout, *geom, _nhwc_ld(out), _nhwc_ld(residual) if residual is not None else 0, alpha=alpha)
     assert (d.hout, d.wout) == (out.shape[1], out.shape[2])
-    d.alpha = alpha
     if (_lib.load().e2eft_conv2d_fwd_f32split_supported(C.byref(d)) != 1 or not w_packed.is_contiguous()
             or not f32split_operands_ok(sources, (out, residual, bias))):
         return None
@@ -418,7 +482,7 @@ def conv2d_norm_split(x, norm, w_packed, bias, cout, residual=None, alpha=1.0, o
     convolution reads (csrc/f32split.hip) — no fp32 intermediate, no maximum pass.  s1: GnStats of x from its producer.  -> (out, the workspace groupnorm_bwd wants), or
     None when the route does not take the convolution: that is known before anything is launched."""
     B, H, W, c1 = x.shape
-    if x.dtype != torch.float32 or (alpha != 1.0 and bias is not None) or w_packed.shape[1] != 9 * c1 or cout % 8 != 0:
+    if not _f32split_takes(x.dtype, c1, w_packed.shape[1], 9, alpha, bias) or cout % 8 != 0:
         return None
     _check_cuda(x, w_packed, bias, residual, out)
     if out is None:
@@ -433,6 +497,128 @@ def conv2d_norm_split(x, norm, w_packed, bias, cout, residual=None, alpha=1.0, o
 
 
 # ---------------------------------------------------------------------------------------------------------
+# ops.conv2d: the validated call (a namespace `c`: operands, arguments, descriptor `d`, and `geom` = (B, H, W, cin, cout, kh, kw, stride, hout, wout) as plain
+# integers — reading them back from the ctypes struct costs more than everything else a route does on the host) is offered to the routes below in order.  A route
+# either takes the call and returns `out`, or returns None having launched nothing.
+def _conv_label(c, normed=False):
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    return c.label or "conv%dx%ds%d%s%s B%d %dx%d %d->%d" % (kh, kw, stride, "u" if c.up_to else "", "n" if normed else "", B, hout, wout, cin, cout)
+
+
+def _conv_timed(c, normed=False):
+    """the timer entry of a launch of the implicit-GEMM kernels on the operands as they lie"""
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    nb = (B * H * W * cin + B * hout * wout * cout * (2 if c.residual is not None else 1) + cout * kh * kw * cin) * c.x.element_size()
+    return _timed("igemm", 2.0 * B * hout * wout * cout * kh * kw * cin, nb, label=_conv_label(c, normed))
+
+
+def _upconv_phases_apply(c):
+    """nearest-2x upsample + 3x3 / stride 1 / pad 1: four 2x2 phase convolutions of the low-resolution input (4/9 of the multiply-adds)"""
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    return (c.w_phase is not None and UPCONV_PHASES_ENABLED and c.up_to is not None and c.x2 is None and c.rowadd is None and c.residual is None and c.norm is None
+            and c.alpha == 1.0 and (kh, kw, stride) == (3, 3, 1) and c.pad == (1, 1, 1, 1) and tuple(c.up_to) == (2 * H, 2 * W))
+
+
+def _conv_upconv_f32split(c):
+    """fp32: the four 2x2 phases on the f16 matrix pipe from split planes (csrc/f32split.hip)"""
+    x, d, out = c.x, c.d, c.out
+    B, H, W, c1, cout, kh, kw, stride, hout, wout = c.geom      # (one source: cin is c1)
+    if not (_upconv_phases_apply(c) and x.dtype == torch.float32 and c1 % 64 == 0 and f32split_operands_ok((x,), (out, c.bias))):
+        return None
+    lib = _lib.load()
+    ds = _f32split_desc(B, H, W, c1, cout, kh, kw, stride, c.pad, d.ldo, 0, up_to=c.up_to)
+    if lib.e2eft_upconv2x_fwd_f32split_supported(C.byref(ds)) != 1:
+        return None
+    wp = c.w_phase()
+    assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.dtype == torch.float32
+    wsp, inv_sw = f32_split_weight(wp, 4, c1)
+    planes, scale = f32_split2(x)
+    nbp = planes.numel() * 2 + B * hout * wout * cout * 4 + wsp.numel() * 2
+    with _timed("igemm", 6.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d f32split" % (B, hout, wout, c1, cout), launches=4,
+                flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
+        _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_upconv2x_fwd_f32split(
+            C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(c.bias), _ptr(out), buf, nbytes, slab, _stream()), out, c.want, B, hout * wout, cout)
+    return out
+
+
+def _conv_upconv(c):
+    """the four 2x2 phases in the operands' own dtype (e2eft_upconv2x_fwd)"""
+    x, d, out = c.x, c.d, c.out
+    lib = _lib.load()
+    if not (_upconv_phases_apply(c) and lib.e2eft_upconv2x_fwd_supported(C.byref(d)) == 1):
+        return None
+    B, H, W, c1, cout, kh, kw, stride, hout, wout = c.geom
+    wp = c.w_phase()
+    assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.is_contiguous() and wp.dtype == x.dtype, (wp.shape, wp.dtype)
+    nbp = (B * H * W * c1 + B * hout * wout * cout + 4 * cout * 4 * c1) * x.element_size()
+    with _timed("igemm", 2.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d" % (B, hout, wout, c1, cout), launches=4,
+                flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
+        _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_upconv2x_fwd(C.byref(d), _ptr(x), _ptr(wp), _ptr(c.bias), _ptr(out), buf, nbytes, slab, _stream()),
+                           out, c.want, B, hout * wout, cout)
+    return out
+
+
+def _conv_normed(c):
+    """GroupNorm(+SiLU) applied in the convolution's operand fetch (e2eft_conv2d_fwd_normed): only the norm's statistics are finalised beforehand"""
+    x, d, out = c.x, c.d, c.out
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    gamma, beta, groups, eps, silu = c.norm
+    lib = _lib.load()
+    # (the <= 4-output-channel route of the supported query, narrow.hip, takes neither a row vector nor a residual nor statistics: ADVICE r3)
+    narrow_ok = cout > 4 or (c.rowadd is None and c.residual is None and not c.want)
+    if not (NORM_FUSION_ENABLED and c.x2 is None and not c.sk and narrow_ok and lib.e2eft_conv2d_fwd_normed_supported(C.byref(d)) == 1):
+        return None
+    ws, coeff = groupnorm_stats(x, gamma, groups, eps)     # (a, mean) pairs; the apply pass is the convolution's operand fetch
+    with _conv_timed(c, normed=True):
+        _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_normed(
+            C.byref(d), _ptr(x), C.c_void_p(coeff), _ptr(beta), 1 if silu else 0, _ptr(c.w), _ptr(c.bias), _ptr(c.rowadd), _ptr(c.residual), _ptr(out), buf, nbytes, slab,
+            _stream()), out, c.want, B, hout * wout, cout)
+    out._e2eft_keep = ws            # (the coefficient workspace lives as long as the launch may: stream-ordered free after the output)
+    return out
+
+
+def _conv_norm_split(c):
+    """fp32 3x3 / stride 1 / pad 1: the norm's apply pass writes the f16 split planes the convolution reads (conv2d_norm_split)"""
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    if not (c.x2 is None and not c.sk and c.up_to is None and c.rowadd is None and (kh, kw, stride) == (3, 3, 1) and c.pad == (1, 1, 1, 1)):
+        return None
+    r = conv2d_norm_split(c.x, c.norm, c.w, c.bias, cout, c.residual, c.alpha, c.out, c.gn_stats, s1=getattr(c.x, "_e2eft_gn", None))      # (fp32; None: nothing was launched)
+    return None if r is None else r[0]
+
+
+def _conv_f32split(c):
+    """fp32 on the f16 matrix pipe from split planes of the input (of the concatenated input: one pair of planes)"""
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    if not (_f32split_takes(c.x.dtype, cin, c.w.shape[1], kh * kw, c.alpha, c.bias, c.up_to, c.rowadd, c.sk) and cin % 64 == 0):
+        return None
+    return _conv2d_f32split(c.x, c.w, c.bias, cout, c.residual, c.alpha, c.out, c.want, _conv_label(c), geom=(kh, kw, stride, c.pad), x2=c.x2)
+
+
+def _conv_direct(c):
+    """the implicit-GEMM kernels on the operands as they lie — split-K, with the statistics of `out`, or plain: takes every call that gets here"""
+    d, out = c.d, c.out
+    B, H, W, cin, cout, kh, kw, stride, hout, wout = c.geom
+    lib = _lib.load()
+    args = (C.byref(d), _ptr(c.x), _ptr(c.x2), _ptr(c.w), _ptr(c.bias), _ptr(c.rowadd), _ptr(c.residual), _ptr(out))
+    with _conv_timed(c):
+        if c.sk:   # few output tiles, long reduction: split-K (the consumer GroupNorm computes its own statistics)
+            ws = torch.empty(c.sk // c.x.element_size(), dtype=c.x.dtype, device=c.x.device)
+            check(lib.e2eft_conv2d_fwd_splitk(*args, _ptr(ws), c.sk, _stream()))
+        elif c.want:
+            _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_gnstats(*args, buf, nbytes, slab, _stream()), out, True, B, hout * wout, cout)
+        else:
+            check(lib.e2eft_conv2d_fwd(*args, _stream()))
+    return out
+
+
+def _first_taker(c, *routes):
+    for route in routes:
+        out = route(c)
+        if out is not None:
+            return out
+    return None
+
+
 def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None, up_to=None, rowadd=None,
            residual=None, alpha=1.0, out=None, gn_stats=False, norm=None, w_phase=None, _label=None):
     """Implicit-GEMM convolution. x: [B,H,W,C1] (C1 % epc == 0), x2: optional [B,H,W,C2] fused channel concat,
@@ -442,105 +628,53 @@ def conv2d(x, w_packed, bias, cout, kh, kw, stride=1, pad=(0, 0, 0, 0), x2=None,
     norm is never applied as a pass of its own: its statistics are finalised and the convolution reads x through them; otherwise groupnorm() runs first."""
     _check_cuda(x, w_packed, x2, bias, rowadd, residual, out)
     B, H, W, c1 = x.shape
-    hl, wl = (H, W) if up_to is None else up_to
-    pt, pb, pl, pr = pad
-    hout = (hl + pt + pb - kh) // stride + 1
-    wout = (wl + pl + pr - kw) // stride + 1
+    hout, wout = _conv_out_hw(*((H, W) if up_to is None else up_to), kh, kw, stride, pad)
     if out is None:
         out = new_nhwc(B, hout, wout, cout, x.dtype, x.device)
     assert tuple(out.shape) == (B, hout, wout, cout), (out.shape, (B, hout, wout, cout))
-    d = ConvDesc()
-    d.dtype = dtype_id(x.dtype)
-    d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, hl, wl
-    d.c1, d.ldx1 = c1, _nhwc_ld(x)
+    cin = c1 + (x2.shape[3] if x2 is not None else 0)
     if x2 is not None:
         assert x2.shape[:3] == x.shape[:3] and x2.dtype == x.dtype
-        d.c2, d.ldx2 = x2.shape[3], _nhwc_ld(x2)
-    else:
-        d.c2, d.ldx2 = 0, 0
-    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-    d.hout, d.wout, d.cout, d.ldo = hout, wout, cout, _nhwc_ld(out)
-    d.ldr = _nhwc_ld(residual) if residual is not None else 0
     if residual is not None:
         assert tuple(residual.shape) == tuple(out.shape) and residual.dtype == x.dtype
     assert w_packed.dim() == 2 and w_packed.shape[0] == cout and w_packed.is_contiguous() and w_packed.dtype == x.dtype
-    assert w_packed.shape[1] >= kh * kw * (d.c1 + d.c2), (w_packed.shape, kh, kw, d.c1, d.c2)
-    d.ldw = w_packed.shape[1]
-    d.alpha = alpha
+    assert w_packed.shape[1] >= kh * kw * cin, (w_packed.shape, kh, kw, c1, cin - c1)
     if bias is not None:
         assert bias.dtype == x.dtype and bias.numel() == cout and bias.is_contiguous()
     if rowadd is not None:
         assert rowadd.dtype == x.dtype and tuple(rowadd.shape) == (B, cout) and rowadd.is_contiguous()
-    want = gn_stats and GN_STATS_ENABLED and cout % 8 == 0
-    # nearest-2x upsample + 3x3 / stride 1 / pad 1: four 2x2 phase convolutions of the low-resolution input (4/9 of the multiply-adds)
-    phases = (w_phase is not None and UPCONV_PHASES_ENABLED and up_to is not None and x2 is None and rowadd is None and residual is None and norm is None and alpha == 1.0
-              and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1) and (hl, wl) == (2 * H, 2 * W))
-    if phases and x.dtype == torch.float32 and c1 % 64 == 0 and f32split_operands_ok((x,), (out, bias)):
-        # fp32: the four 2x2 phases on the f16 matrix pipe from split planes (csrc/f32split.hip)
-        lib = _lib.load()
-        ds = _f32split_desc(B, H, W, c1, cout, kh, kw, stride, pad, d.ldo, 0, up_to=up_to)
-        if lib.e2eft_upconv2x_fwd_f32split_supported(C.byref(ds)) == 1:
-            wp = w_phase()
-            assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.dtype == torch.float32
-            wsp, inv_sw = f32_split_weight(wp, 4, c1)
-            planes, scale = f32_split2(x)
-            nbp = planes.numel() * 2 + B * hout * wout * cout * 4 + wsp.numel() * 2
-            with _timed("igemm", 6.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d f32split" % (B, hout, wout, c1, cout), launches=4,
-                        flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
-                _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_upconv2x_fwd_f32split(
-                    C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(out), buf, nbytes, slab, _stream()), out, want, B, hout * wout, cout)
-            return out
-    if phases and _lib.load().e2eft_upconv2x_fwd_supported(C.byref(d)) == 1:
-        wp = w_phase()
-        assert tuple(wp.shape) == (4, cout, 4 * c1) and wp.is_contiguous() and wp.dtype == x.dtype, (wp.shape, wp.dtype)
-        nbp = (B * H * W * c1 + B * hout * wout * cout + 4 * cout * 4 * c1) * x.element_size()
-        with _timed("igemm", 2.0 * B * H * W * 4 * cout * 4 * c1, nbp, label="upconv2x(4 phases) B%d %dx%d %d->%d" % (B, hout, wout, c1, cout), launches=4,
-                    flops_nominal=2.0 * B * hout * wout * cout * 9 * c1):
-            _launch_with_stats(lambda buf, nbytes, slab: _lib.load().e2eft_upconv2x_fwd(C.byref(d), _ptr(x), _ptr(wp), _ptr(bias), _ptr(out), buf, nbytes, slab, _stream()),
-                               out, want, B, hout * wout, cout)
+    d = _conv_desc(x, x2, cout, kh, kw, stride, pad, up_to, alpha, _nhwc_ld(out), _nhwc_ld(residual) if residual is not None else 0, w_packed.shape[1])
+    c = SimpleNamespace(x=x, x2=x2, w=w_packed, bias=bias, rowadd=rowadd, residual=residual, out=out, d=d, geom=(B, H, W, cin, cout, kh, kw, stride, hout, wout),
+                        alpha=alpha, pad=tuple(pad), up_to=up_to, norm=norm, w_phase=w_phase, label=_label, gn_stats=gn_stats,
+                        want=gn_stats and GN_STATS_ENABLED and cout % 8 == 0, sk=0)
+    if _first_taker(c, _conv_upconv_f32split, _conv_upconv) is not None:
         return out
-    es = x.element_size()
-    nb = (B * H * W * (d.c1 + d.c2) + B * hout * wout * cout * (2 if residual is not None else 1) + cout * kh * kw * (d.c1 + d.c2)) * es
-    lib = _lib.load()
-    sk = lib.e2eft_conv2d_splitk_workspace_bytes(C.byref(d)) if SPLITK_ENABLED else 0
-    coeff = None
+    c.sk = _lib.load().e2eft_conv2d_splitk_workspace_bytes(C.byref(d)) if SPLITK_ENABLED else 0
     if norm is not None:
+        if _first_taker(c, _conv_normed, _conv_norm_split) is not None:      # these read x through the norm
+            return out
+        # neither: the norm runs as a pass of its own, and the routes below read its output
         gamma, beta, groups, eps, silu = norm
-        # (the <= 4-output-channel route of the supported query, narrow.hip, takes neither a row vector nor a residual nor statistics: ADVICE r3)
-        narrow_ok = cout > 4 or (rowadd is None and residual is None and not want)
-        if NORM_FUSION_ENABLED and x2 is None and not sk and narrow_ok and lib.e2eft_conv2d_fwd_normed_supported(C.byref(d)) == 1:
-            ws, coeff = groupnorm_stats(x, gamma, groups, eps)     # (a, mean) pairs; the apply pass is the convolution's operand fetch
-        else:
-            if x2 is None and not sk and up_to is None and rowadd is None and (kh, kw, stride) == (3, 3, 1) and tuple(pad) == (1, 1, 1, 1):
-                r = conv2d_norm_split(x, norm, w_packed, bias, cout, residual, alpha, out, gn_stats, s1=getattr(x, "_e2eft_gn", None))      # (fp32; None: nothing was launched)
-                if r is not None:
-                    return r[0]
-            x = groupnorm(x, gamma, beta, groups, eps, silu=silu, x2=x2)      # the norm of the CONCATENATED input; its output is one tensor
-            x2 = None
-            d.c1, d.ldx1, d.c2, d.ldx2 = x.shape[3], _nhwc_ld(x), 0, 0
-    label = _label or "conv%dx%ds%d%s%s B%d %dx%d %d->%d" % (kh, kw, stride, "u" if up_to else "", "n" if coeff is not None else "", B, hout, wout, d.c1 + d.c2, cout)
-    if (x.dtype == torch.float32 and coeff is None and not sk and up_to is None and rowadd is None
-            and (alpha == 1.0 or bias is None)
-            and (d.c1 + d.c2) % 64 == 0 and w_packed.shape[1] == kh * kw * (d.c1 + d.c2)):
-        r = _conv2d_f32split(x, w_packed, bias, cout, residual, alpha, out, want, label, geom=(kh, kw, stride, tuple(pad)), x2=x2)
-        if r is not None:
-            return r
-    with _timed("igemm", 2.0 * B * hout * wout * cout * kh * kw * (d.c1 + d.c2), nb, label=label):
-        if coeff is not None:
-            _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_normed(
-                C.byref(d), _ptr(x), C.c_void_p(coeff), _ptr(beta), 1 if silu else 0, _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out), buf, nbytes, slab,
-                _stream()), out, want, B, hout * wout, cout)
-            out._e2eft_keep = ws            # (the coefficient workspace lives as long as the launch may: stream-ordered free after the output)
-        elif sk:   # few output tiles, long reduction: split-K (the consumer GroupNorm computes its own statistics)
-            ws = torch.empty(sk // x.element_size(), dtype=x.dtype, device=x.device)
-            check(lib.e2eft_conv2d_fwd_splitk(C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out),
-                                              _ptr(ws), sk, _stream()))
-        elif want:
-            _launch_with_stats(lambda buf, nbytes, slab: lib.e2eft_conv2d_fwd_gnstats(
-                C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd), _ptr(residual), _ptr(out), buf, nbytes, slab, _stream()), out, True, B, hout * wout, cout)
-        else:
-            check(_lib.load().e2eft_conv2d_fwd(C.byref(d), _ptr(x), _ptr(x2), _ptr(w_packed), _ptr(bias), _ptr(rowadd),
-                                               _ptr(residual), _ptr(out), _stream()))
+        c.x = groupnorm(x, gamma, beta, groups, eps, silu=silu, x2=x2)      # the norm of the CONCATENATED input; its output is one tensor
+        c.x2 = None
+        c.d = _conv_desc(c.x, None, cout, kh, kw, stride, pad, up_to, alpha, d.ldo, d.ldr, d.ldw)
+    return _first_taker(c, _conv_f32split, _conv_direct)
+
+
+def _gemm_f32split(a, w, bias, residual, out, alpha, ldo, ldr):
+    """fp32 nn.Linear of whole 256-row tiles: two-term f16 split planes on the f16 matrix pipe (csrc/f32split.hip; igemm5's GEMM mode), or None having launched nothing"""
+    (M, K), N = a.shape, w.shape[0]
+    if not ((alpha == 1.0 or bias is None) and K % 64 == 0 and M > 256 and N % 8 == 0 and w.is_contiguous() and f32split_operands_ok((a,), (out, residual, bias))):
+        return None
+    ds = _gemm_desc(_lib.F32, M, N, K, 2 * K, 3 * K, ldo, ldr, alpha=alpha)
+    lib = _lib.load()
+    if lib.e2eft_gemm_f32split_supported(C.byref(ds)) != 1:
+        return None
+    wsp, inv_sw = f32_split_weight(w, 1, K)
+    planes, scale = f32_split2(a)
+    with _timed("igemm", 6.0 * M * N * K, (M * 2 * K * 2 + N * 3 * K * 2 + M * N * 4 * (2 if residual is not None else 1)), label="gemm M%d N%d K%d f32split" % (M, N, K),
+                flops_nominal=2.0 * M * N * K):
+        check(lib.e2eft_gemm_f32split(C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(residual), _ptr(out), _stream()))
     return out
 
 
@@ -554,37 +688,14 @@ def gemm(a, w, bias=None, residual=None, out=None, alpha=1.0, bias_along_m=False
     if out is None:
         out = torch.empty((M, N), dtype=a.dtype, device=a.device)
     assert tuple(out.shape) == (M, N) and out.dtype == a.dtype
-    d = GemmDesc()
-    d.dtype = dtype_id(a.dtype)
-    d.m, d.n, d.k = M, N, K
-    d.lda, d.ldw, d.ldo = _rows_ld(a), _rows_ld(w), _rows_ld(out)
-    d.ldr = _rows_ld(residual) if residual is not None else 0
-    d.nzo = d.nzi = 1
-    d.bias_along_m = 1 if bias_along_m else 0
-    d.alpha = alpha
+    d = _gemm_desc(dtype_id(a.dtype), M, N, K, _rows_ld(a), _rows_ld(w), _rows_ld(out), _rows_ld(residual) if residual is not None else 0, bias_along_m=bias_along_m, alpha=alpha)
     if bias is not None:
         assert bias.dtype == a.dtype and bias.is_contiguous() and bias.numel() == (M if bias_along_m else N)
     if residual is not None:
         assert tuple(residual.shape) == (M, N) and residual.dtype == a.dtype
     want = gn_rows_per_image > 0 and GN_STATS_ENABLED and N % 8 == 0 and M % gn_rows_per_image == 0 and not bias_along_m
-    if (a.dtype == torch.float32 and not want and not bias_along_m and (alpha == 1.0 or bias is None) and K % 64 == 0 and M > 256 and N % 8 == 0 and w.is_contiguous()
-            and f32split_operands_ok((a,), (out, residual, bias))):
-        # fp32 nn.Linear of whole 256-row tiles: two-term f16 split planes on the f16 matrix pipe (csrc/f32split.hip; igemm5's GEMM mode)
-        ds = GemmDesc()
-        ds.dtype = _lib.F32
-        ds.m, ds.n, ds.k = M, N, K
-        ds.lda, ds.ldw, ds.ldo, ds.ldr = 2 * K, 3 * K, d.ldo, d.ldr
-        ds.nzo = ds.nzi = 1
-        ds.bias_along_m = 0
-        ds.alpha = alpha
-        lib = _lib.load()
-        if lib.e2eft_gemm_f32split_supported(C.byref(ds)) == 1:
-            wsp, inv_sw = f32_split_weight(w, 1, K)
-            planes, scale = f32_split2(a)
-            with _timed("igemm", 6.0 * M * N * K, (M * 2 * K * 2 + N * 3 * K * 2 + M * N * 4 * (2 if residual is not None else 1)), label="gemm M%d N%d K%d f32split" % (M, N, K),
-                        flops_nominal=2.0 * M * N * K):
-                check(lib.e2eft_gemm_f32split(C.byref(ds), _ptr(planes), _ptr(scale), _ptr(wsp), _ptr(inv_sw), _ptr(bias), _ptr(residual), _ptr(out), _stream()))
-            return out
+    if a.dtype == torch.float32 and not want and not bias_along_m and _gemm_f32split(a, w, bias, residual, out, alpha, d.ldo, d.ldr) is not None:
+        return out
     with _timed("igemm", 2.0 * M * N * K, (M * K + N * K + M * N * (2 if residual is not None else 1)) * a.element_size(), label="gemm M%d N%d K%d" % (M, N, K)):
         if want:
             _launch_with_stats(lambda buf, nbytes, slab: _lib.load().e2eft_gemm_gnstats(
@@ -598,17 +709,7 @@ def bgemm_raw(dtype, m, n, k, a, lda, sa, w, ldw, sw, out, ldo, so, nzo, nzi, bi
     """Batched NT GEMM on raw base tensors with explicit element strides. sa/sw/so = (outer, inner) batch strides.
     a / w / out are tensors whose data_ptr() is the z = 0 base."""
     _check_cuda(a, w, out, bias)
-    d = GemmDesc()
-    d.dtype = dtype_id(dtype)
-    d.m, d.n, d.k = m, n, k
-    d.lda, d.ldw, d.ldo, d.ldr = lda, ldw, ldo, 0
-    d.nzo, d.nzi = nzo, nzi
-    d.sa_o, d.sa_i = sa
-    d.sw_o, d.sw_i = sw
-    d.so_o, d.so_i = so
-    d.sr_o = d.sr_i = 0
-    d.bias_along_m = 1 if bias_along_m else 0
-    d.alpha = alpha
+    d = _gemm_desc(dtype_id(dtype), m, n, k, lda, ldw, ldo, 0, (nzo, nzi), sa, sw, so, bias_along_m, alpha)
     with _timed("igemm", 2.0 * m * n * k * nzo * nzi, float(nzo * nzi) * (m * k + n * k + m * n) * dtype_size(dtype), label="bgemm z%d M%d N%d K%d" % (nzo * nzi, m, n, k)):
         check(_lib.load().e2eft_gemm(C.byref(d), _ptr(a), _ptr(w), _ptr(bias), _ptr(None), _ptr(out), _stream()))
     return out
@@ -650,33 +751,31 @@ def _as_rows(t):
 
 
 # ---------------------------------------------------------------------------------------------------------
-def groupnorm(x, gamma, beta, groups, eps, silu=False, x2=None, out=None):
-    """GroupNorm(+SiLU) over NHWC x [B,H,W,C1] (optionally concatenated with x2 along C)."""
+def groupnorm_fwd_ws(x, gamma, beta, groups, eps, silu=False, x2=None, s1=None, s2=None, out=None):
+    """GroupNorm(+SiLU) over NHWC x [B,H,W,C1] (optionally concatenated with x2 along C) -> (out, its workspace: mean / rstd live there for groupnorm_bwd).
+    s1 / s2: GnStats of x / x2 emitted by their producers (statistics pass skipped for that source)."""
     _check_cuda(x, gamma, beta, x2, out)
     B, H, W, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[3]
     if out is None:
         out = torch.empty((B, H, W, c1 + c2), dtype=x.dtype, device=x.device)
-    d = GroupNormDesc()
-    d.dtype = dtype_id(x.dtype)
-    d.batch, d.hw = B, H * W
-    d.c1, d.ldx1 = c1, _nhwc_ld(x)
-    d.c2, d.ldx2 = (c2, _nhwc_ld(x2)) if x2 is not None else (0, 0)
-    d.groups, d.ldy, d.silu, d.eps = groups, _nhwc_ld(out), 1 if silu else 0, eps
-    lib = _lib.load()
-    nbytes = lib.e2eft_groupnorm_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError("groupnorm: %s" % lib.e2eft_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    d = _gn_desc(x, x2, groups, eps, silu, _nhwc_ld(out))
+    ws, nbytes = _gn_workspace(d, x.device)
     if gamma is not None:
         assert gamma.dtype == x.dtype and gamma.numel() == c1 + c2
-    s1 = getattr(x, "_e2eft_gn", None) if GN_STATS_ENABLED else None
-    s2 = getattr(x2, "_e2eft_gn", None) if (x2 is not None and GN_STATS_ENABLED) else None
+    if not GN_STATS_ENABLED:
+        s1 = s2 = None
+    if x2 is None:
+        s2 = None
     with _timed("groupnorm", 0.0, 2.0 * B * H * W * (c1 + c2) * x.element_size(), label="gn B%d %dx%d C%d" % (B, H, W, c1 + c2)):
-        check(lib.e2eft_groupnorm_fwd_pre(C.byref(d), _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), _ptr(out),
-                                          _ptr(s1.partial) if s1 else C.c_void_p(0), s1.nslabs if s1 else 0,
-                                          _ptr(s2.partial) if s2 else C.c_void_p(0), s2.nslabs if s2 else 0, _ptr(ws), nbytes, _stream()))
-    return out
+        check(_lib.load().e2eft_groupnorm_fwd_pre(C.byref(d), _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), _ptr(out), *_gn_stats_args(s1), *_gn_stats_args(s2), _ptr(ws), nbytes,
+                                                  _stream()))
+    return out, ws
+
+
+def groupnorm(x, gamma, beta, groups, eps, silu=False, x2=None, out=None):
+    """groupnorm_fwd_ws with the statistics the producers of x / x2 left on them, into `out` if given, without the workspace"""
+    return groupnorm_fwd_ws(x, gamma, beta, groups, eps, silu, x2, getattr(x, "_e2eft_gn", None), getattr(x2, "_e2eft_gn", None), out)[0]
 
 
 NORM_FUSION_ENABLED = True    # conv2d(norm=...): GroupNorm(+SiLU) applied inside the consuming convolution where the library supports it
@@ -686,20 +785,12 @@ def groupnorm_stats(x, gamma, groups, eps):
     """The statistics half of groupnorm() alone -> (workspace, device address of the fp32 (a, mean) pairs [B][C][2] inside it)."""
     _check_cuda(x, gamma)
     B, H, W, c1 = x.shape
-    d = GroupNormDesc()
-    d.dtype = dtype_id(x.dtype)
-    d.batch, d.hw = B, H * W
-    d.c1, d.ldx1, d.c2, d.ldx2 = c1, _nhwc_ld(x), 0, 0
-    d.groups, d.ldy, d.silu, d.eps = groups, c1, 0, eps
-    lib = _lib.load()
-    nbytes = lib.e2eft_groupnorm_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError("groupnorm_stats: %s" % lib.e2eft_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    d = _gn_desc(x, None, groups, eps, False, c1)
+    ws, nbytes = _gn_workspace(d, x.device, "groupnorm_stats")
     s1 = getattr(x, "_e2eft_gn", None) if GN_STATS_ENABLED else None
+    lib = _lib.load()
     with _timed("groupnorm_stats", 0.0, 0.0, label="gn stats B%d %dx%d C%d" % (B, H, W, c1)):
-        check(lib.e2eft_groupnorm_fwd_stats(C.byref(d), _ptr(x), C.c_void_p(0), _ptr(gamma), _ptr(s1.partial) if s1 else C.c_void_p(0), s1.nslabs if s1 else 0,
-                                            C.c_void_p(0), 0, _ptr(ws), nbytes, _stream()))
+        check(lib.e2eft_groupnorm_fwd_stats(C.byref(d), _ptr(x), C.c_void_p(0), _ptr(gamma), *_gn_stats_args(s1), C.c_void_p(0), 0, _ptr(ws), nbytes, _stream()))
     return ws, ws.data_ptr() + lib.e2eft_groupnorm_coeff_offset(C.byref(d))
 
 
@@ -977,23 +1068,6 @@ def angular_loss(pred, target, mask):
 
 # =========================================================================================================
 # backward-pass kernels (include/e2eft.h "Backward pass of the E2E-FT training step"); used by autograd.py
-def _conv_desc(x, x2, cout, kh, kw, stride, pad, up_to, alpha, ldo=0):
-    B, H, W, c1 = x.shape
-    hl, wl = (H, W) if up_to is None else up_to
-    pt, pb, pl, pr = pad
-    d = ConvDesc()
-    d.dtype = dtype_id(x.dtype)
-    d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, hl, wl
-    d.c1, d.ldx1 = c1, _nhwc_ld(x)
-    d.c2, d.ldx2 = (x2.shape[3], _nhwc_ld(x2)) if x2 is not None else (0, 0)
-    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-    d.hout = (hl + pt + pb - kh) // stride + 1
-    d.wout = (wl + pl + pr - kw) // stride + 1
-    d.cout, d.ldo, d.ldr, d.ldw = cout, ldo, 0, 0
-    d.alpha = alpha
-    return d
-
-
 def transpose(x, rows_pad=None, out=None):
     """x: [Z, R, C] (or [R, C]) row-strided view -> [Z, C, rows_pad] with zeros in [R, rows_pad) (rows_pad multiple of 64 by default
     so that the result is a FAST-path K operand of e2eft_gemm)."""
@@ -1091,22 +1165,21 @@ WGRAD_DIRECT = True   # tests / A-B: False keeps every weight gradient on the tr
 WGRAD_DIRECT_FP32 = True   # round 6: strict-fp32 weight gradients straight from the NHWC tensors too (csrc/wgrad.hip::wgrad32_kernel); False: the round-5 path
 
 
+def _wgrad_batch_step(per_img, pixels_per_img, B):
+    """images per launch of a weight gradient cut along the batch: the kernel addresses each operand through ONE 32-bit buffer descriptor (per_img: bytes of one image
+    of the larger operand) and counts fewer than 2^24 output pixels"""
+    return max(1, min(B, (0xFFFF0000 - 1) // max(per_img, 1), ((1 << 24) - 1) // max(pixels_per_img, 1)))
+
+
 def _wgrad_split_serves(dy, x, cin, cout, kh, kw, stride, pad):
     """pure host arithmetic: does the 16-bit kernel serve the f16 split planes of this fp32 weight gradient (dY planes of pixel stride 2 c0, ONE source of cin channels
     at pixel stride 2 cin), in every launch of conv2d_wgrad's cut along the batch?  Asked before anything is split: a shape it refuses goes to wgrad32_kernel."""
     B, H, W, _ = x.shape
     c0 = dy.shape[3]
-    per_img = max(dy.shape[1] * dy.shape[2] * 2 * c0, H * W * 2 * cin) * 2
-    step = max(1, min(B, (0xFFFF0000 - 1) // max(per_img, 1), ((1 << 24) - 1) // max(dy.shape[1] * dy.shape[2], 1)))
-    pt, pb, pl, pr = pad
+    step = _wgrad_batch_step(max(dy.shape[1] * dy.shape[2] * 2 * c0, H * W * 2 * cin) * 2, dy.shape[1] * dy.shape[2], B)
     for nb in {step, B % step or step}:
-        d = ConvDesc()
-        d.dtype = _lib.F16
-        d.batch, d.hin, d.win, d.hl, d.wl = nb, H, W, H, W
-        d.c1, d.ldx1, d.c2, d.ldx2 = cin, 2 * cin, 0, 0
-        d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-        d.hout, d.wout = dy.shape[1], dy.shape[2]
-        d.cout, d.alpha = cout, 1.0
+        d = _conv_desc((nb, H, W, cin, 2 * cin), None, cout, kh, kw, stride, pad, None, 1.0, dtype=_lib.F16)
+        assert (d.hout, d.wout) == (dy.shape[1], dy.shape[2]), (dy.shape, d.hout, d.wout)
         if _lib.load().e2eft_conv2d_wgrad_workspace_bytes(C.byref(d), 2 * c0) == 0:
             return False
     return True
@@ -1151,8 +1224,7 @@ def conv2d_wgrad(dy, x, x2, cout, kh, kw, stride, pad, alpha, out=None):
     lddy = _nhwc_ld(dy)
     es = dy.element_size()
     per_img = max(dy.shape[1] * dy.shape[2] * lddy, x.shape[1] * x.shape[2] * max(_nhwc_ld(x), _nhwc_ld(x2) if x2 is not None else 0)) * es
-    pix_img = max(dy.shape[1] * dy.shape[2], 1)
-    step = max(1, min(B, (0xFFFF0000 - 1) // max(per_img, 1), ((1 << 24) - 1) // pix_img))
+    step = _wgrad_batch_step(per_img, dy.shape[1] * dy.shape[2], B)
     lib = _lib.load()
     parts = []
     N = kh * kw * cin
@@ -1204,22 +1276,14 @@ def conv2d_dgrad(dy, w_dgrad, x_shape, c2, kh, kw, stride, pad, up_to, alpha):
     _check_cuda(dy, w_dgrad)
     B, H, W, c1 = x_shape
     hl, wl = (H, W) if up_to is None else up_to
-    pt, pb, pl, pr = pad
-    d = ConvDesc()
-    d.dtype = dtype_id(dy.dtype)
-    d.batch, d.hin, d.win, d.hl, d.wl = B, H, W, hl, wl
-    d.c1, d.ldx1, d.c2, d.ldx2 = c1, c1, c2, c2
-    d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, pt, pl
-    d.hout, d.wout = dy.shape[1], dy.shape[2]
-    assert d.hout == (hl + pt + pb - kh) // stride + 1 and d.wout == (wl + pl + pr - kw) // stride + 1
-    cop = dy.shape[3]
-    d.cout, d.alpha = cop, alpha
-    cin = c1 + c2
+    cop, cin = dy.shape[3], c1 + c2
+    d = _conv_desc((B, H, W, c1, c1), (c2, c2), cop, kh, kw, stride, pad, up_to, alpha, dtype=dtype_id(dy.dtype))      # (the forward's descriptor over a dense dX)
+    assert (d.hout, d.wout) == (dy.shape[1], dy.shape[2])
     assert w_dgrad.shape == (cin, kh * kw * cop) and w_dgrad.is_contiguous() and w_dgrad.dtype == dy.dtype
     label = "dgrad%dx%ds%d B%d %dx%d %d->%d" % (kh, kw, stride, B, hl, wl, cop, cin)
     dx = new_nhwc(B, hl, wl, cin, dy.dtype, dy.device)
-    if (dy.dtype == torch.float32 and ((kh, kw, stride, tuple(pad)) == (3, 3, 1, (1, 1, 1, 1)) or (kh, kw, stride, tuple(pad)) == (1, 1, 1, (0, 0, 0, 0)))
-            and up_to is None and cop % 64 == 0 and cin % 8 == 0):
+    if (_f32split_takes(dy.dtype, cop, w_dgrad.shape[1], kh * kw, alpha, None, up_to) and cop % 64 == 0 and cin % 8 == 0
+            and ((kh, kw, stride, tuple(pad)) == (3, 3, 1, (1, 1, 1, 1)) or (kh, kw, stride, tuple(pad)) == (1, 1, 1, (0, 0, 0, 0)))):
         # the data gradient of a 3x3 / stride-1 / pad-1 (or 1x1) convolution IS such a convolution of dY with the flipped, transposed weights: the f16-split route of conv2d
         if _conv2d_f32split(dy, w_dgrad, None, cin, None, alpha, dx, False, label, geom=(kh, kw, 1, tuple(pad))) is not None:
             return dx
@@ -1254,40 +1318,6 @@ def upsample_nearest_bwd(dy, H, W):
     return dx
 
 
-def groupnorm_fwd_ws(x, gamma, beta, groups, eps, silu=False, x2=None, s1=None, s2=None):
-    """GroupNorm forward that also returns its workspace (mean / rstd live there) for groupnorm_bwd.  s1 / s2: GnStats of x / x2
-    emitted by their producers (statistics pass skipped for that source)."""
-    _check_cuda(x, gamma, beta, x2)
-    B, H, W, c1 = x.shape
-    c2 = 0 if x2 is None else x2.shape[3]
-    out = torch.empty((B, H, W, c1 + c2), dtype=x.dtype, device=x.device)
-    d = _gn_desc(x, x2, groups, eps, silu, _nhwc_ld(out))
-    lib = _lib.load()
-    nbytes = lib.e2eft_groupnorm_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError("groupnorm: %s" % lib.e2eft_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-    if not GN_STATS_ENABLED:
-        s1 = s2 = None
-    with _timed("groupnorm", 0.0, 2.0 * B * H * W * (c1 + c2) * x.element_size(), label="gn B%d %dx%d C%d" % (B, H, W, c1 + c2)):
-        check(lib.e2eft_groupnorm_fwd_pre(C.byref(d), _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), _ptr(out),
-                                          _ptr(s1.partial) if s1 else C.c_void_p(0), s1.nslabs if s1 else 0,
-                                          _ptr(s2.partial) if (s2 and x2 is not None) else C.c_void_p(0), s2.nslabs if (s2 and x2 is not None) else 0,
-                                          _ptr(ws), nbytes, _stream()))
-    return out, ws
-
-
-def _gn_desc(x, x2, groups, eps, silu, ldy):
-    B, H, W, c1 = x.shape
-    d = GroupNormDesc()
-    d.dtype = dtype_id(x.dtype)
-    d.batch, d.hw = B, H * W
-    d.c1, d.ldx1 = c1, _nhwc_ld(x)
-    d.c2, d.ldx2 = (x2.shape[3], _nhwc_ld(x2)) if x2 is not None else (0, 0)
-    d.groups, d.ldy, d.silu, d.eps = groups, ldy, 1 if silu else 0, eps
-    return d
-
-
 def groupnorm_bwd(x, x2, gamma, beta, groups, eps, silu, dy, fwd_ws, need_dx=True, need_dparams=True, dx_add=None, dg_out=None, db_out=None):
     """-> (dx [B,H,W,C] or None, dgamma fp32 [C] or None, dbeta fp32 [C] or None); dx_add: a [B,H,W,C] gradient added into dx;
     dg_out / db_out: dense fp32 [C] tensors that receive dgamma / dbeta"""
@@ -1295,20 +1325,15 @@ def groupnorm_bwd(x, x2, gamma, beta, groups, eps, silu, dy, fwd_ws, need_dx=Tru
     B, H, W, c1 = x.shape
     Cc = c1 + (0 if x2 is None else x2.shape[3])
     d = _gn_desc(x, x2, groups, eps, silu, Cc)
-    lib = _lib.load()
-    nbytes = lib.e2eft_groupnorm_bwd_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError("groupnorm_bwd: %s" % lib.e2eft_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    ws, nbytes = _gn_workspace(d, x.device, "groupnorm_bwd", bwd=True)
     dx = torch.empty((B, H, W, Cc), dtype=x.dtype, device=x.device) if need_dx else None
     for o_ in (dg_out, db_out):
         assert o_ is None or (o_.dtype == torch.float32 and tuple(o_.shape) == (Cc,) and o_.is_contiguous())
     dg = (dg_out if dg_out is not None else torch.empty(Cc, dtype=torch.float32, device=x.device)) if need_dparams else None
     db = (db_out if db_out is not None else torch.empty(Cc, dtype=torch.float32, device=x.device)) if need_dparams else None
     with _timed("groupnorm_bwd", 0.0, 5.0 * B * H * W * Cc * x.element_size(), label="gn_bwd B%d %dx%d C%d" % (B, H, W, Cc)):
-        check(lib.e2eft_groupnorm_bwd_add(C.byref(d), _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), _ptr(dy), _nhwc_ld(dy), _ptr(dx_add),
-                                          _nhwc_ld(dx_add) if dx_add is not None else 0, _ptr(dx), Cc, _ptr(dg), _ptr(db), _ptr(fwd_ws), _ptr(ws), nbytes,
-                                          _stream()))
+        check(_lib.load().e2eft_groupnorm_bwd_add(C.byref(d), _ptr(x), _ptr(x2), _ptr(gamma), _ptr(beta), _ptr(dy), _nhwc_ld(dy), _ptr(dx_add),
+                                                  _nhwc_ld(dx_add) if dx_add is not None else 0, _ptr(dx), Cc, _ptr(dg), _ptr(db), _ptr(fwd_ws), _ptr(ws), nbytes, _stream()))
     return dx, dg, db
 
 

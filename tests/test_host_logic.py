@@ -537,3 +537,60 @@ def test_ema_model_follows_the_diffusers_definition_and_round_trips(tmp_path):
     assert all(torch.equal(a, b) for a, b in zip(back.shadow_params, e2.shadow_params))
     with pytest.raises(ValueError):
         EMAModel(net.parameters()).save_pretrained(str(tmp_path / "x"))
+
+
+def test_conv_desc_builder_output_size_and_every_field():
+    """ops._conv_desc is the one place a ConvDesc is made.  Its output grid is torch's convolution over the explicitly padded (and nearest-upsampled) tensor, and for
+    the arguments of each of the five former fill sites — ops.conv2d, the split-plane descriptor, the tensor form of the backward wrappers, the weight gradient's
+    16-bit planes, conv2d_dgrad — every field is what that site set, the fields it left to ctypes' zero initialisation included."""
+    import itertools
+    from diffusion_e2e_ft_amd import _lib, ops
+
+    def fields(d):
+        return {n: getattr(d, n) for n, _ in _lib.ConvDesc._fields_}
+
+    B, c1, c2, cout = 2, 8, 16, 24
+    for H, W, k, stride, pad, up in itertools.product((7, 8, 9), (7, 8, 9), (1, 3, 4), (1, 2), ((0, 0, 0, 0), (1, 1, 1, 1), (0, 1, 0, 1)), (False, True)):
+        pt, pb, pl, pr = pad
+        up_to = (2 * H, 2 * W) if up else None
+        hl, wl = up_to or (H, W)
+        x = torch.zeros(B, H, W, 12)[..., :c1]                 # a channel slice of a wider buffer: pixel stride 12
+        x2 = torch.zeros(B, H, W, c2)
+        t = x.permute(0, 3, 1, 2)
+        if up:
+            t = torch.nn.functional.interpolate(t, size=up_to, mode="nearest")
+        want = torch.nn.functional.conv2d(torch.nn.functional.pad(t, (pl, pr, pt, pb)), torch.zeros(cout, c1, k, k), stride=stride).shape
+        hout, wout = want[2], want[3]
+        case = (H, W, k, stride, pad, up)
+        # 1. ops.conv2d: operands as tensors, every stride set
+        d = ops._conv_desc(x, x2, cout, k, k, stride, pad, up_to, 0.5, 32, 40, k * k * (c1 + c2) + 8)
+        assert (d.hout, d.wout) == (hout, wout), case
+        assert fields(d) == dict(dtype=0, batch=B, hin=H, win=W, hl=hl, wl=wl, c1=c1, ldx1=12, c2=c2, ldx2=c2, kh=k, kw=k, stride=stride, pad_t=pt, pad_l=pl,
+                                 hout=hout, wout=wout, cout=cout, ldo=32, ldr=40, ldw=k * k * (c1 + c2) + 8, alpha=0.5), case
+        # 2. split planes of c1 fp32 channels (f16 pairs at pixel stride 2 c1, weight rows [w0 | w1 | w0]), one source, alpha 1 unless given
+        d = ops._f32split_desc(B, H, W, c1, cout, k, k, stride, pad, 32, 40, up_to=up_to)
+        assert fields(d) == dict(dtype=0, batch=B, hin=H, win=W, hl=hl, wl=wl, c1=c1, ldx1=2 * c1, c2=0, ldx2=0, kh=k, kw=k, stride=stride, pad_t=pt, pad_l=pl,
+                                 hout=hout, wout=wout, cout=cout, ldo=32, ldr=40, ldw=k * k * 3 * c1, alpha=1.0), case
+        # 3. the tensor form of the backward wrappers and the tests: ldr / ldw stay zero, one source
+        d = ops._conv_desc(x.half(), None, cout, k, k, stride, pad, up_to, 1.0, ldo=cout)
+        assert fields(d) == dict(dtype=1, batch=B, hin=H, win=W, hl=hl, wl=wl, c1=c1, ldx1=c1, c2=0, ldx2=0, kh=k, kw=k, stride=stride, pad_t=pt, pad_l=pl,
+                                 hout=hout, wout=wout, cout=cout, ldo=cout, ldr=0, ldw=0, alpha=1.0), case
+        if not up:
+            # 4. the weight gradient's 16-bit planes of an fp32 tensor: geometry, f16, nothing but the source's stride
+            d = ops._conv_desc((3, H, W, c1, 2 * c1), None, cout, k, k, stride, pad, None, 1.0, dtype=_lib.F16)
+            assert fields(d) == dict(dtype=1, batch=3, hin=H, win=W, hl=H, wl=W, c1=c1, ldx1=2 * c1, c2=0, ldx2=0, kh=k, kw=k, stride=stride, pad_t=pt, pad_l=pl,
+                                     hout=hout, wout=wout, cout=cout, ldo=0, ldr=0, ldw=0, alpha=1.0), case
+        # 5. conv2d_dgrad: the forward's geometry over a dense dX of c1 + c2 channels
+        d = ops._conv_desc((B, H, W, c1, c1), (c2, c2), 32, k, k, stride, pad, up_to, 0.25, dtype=_lib.BF16)
+        assert fields(d) == dict(dtype=2, batch=B, hin=H, win=W, hl=hl, wl=wl, c1=c1, ldx1=c1, c2=c2, ldx2=c2, kh=k, kw=k, stride=stride, pad_t=pt, pad_l=pl,
+                                 hout=hout, wout=wout, cout=32, ldo=0, ldr=0, ldw=0, alpha=0.25), case
+    assert ops._conv_out_hw(64, 64, 3, 3, 1, (1, 1, 1, 1)) == (64, 64)
+
+
+def test_wgrad_batch_step_limits():
+    """ops._wgrad_batch_step: images per launch so that neither operand reaches the 4 GB of one 32-bit buffer descriptor nor the launch 2^24 output pixels"""
+    from diffusion_e2e_ft_amd import ops
+    assert ops._wgrad_batch_step(1 << 20, 64 * 64, 32) == 32                       # everything fits: the whole batch
+    assert ops._wgrad_batch_step(576 * 576 * 256 * 2, 576 * 576, 32) == 25          # 170 MB per image: 25 images stay below 0xFFFF0000 bytes
+    assert ops._wgrad_batch_step(1 << 10, 1 << 22, 32) == 3                         # 2^22 pixels per image: three images stay below 2^24
+    assert ops._wgrad_batch_step(1 << 33, 1, 4) == 1 and ops._wgrad_batch_step(0, 0, 4) == 4
