@@ -3,158 +3,87 @@
 //   valid = near < depth < far;  (lo, hi) = 2 % / 98 % quantiles of the valid depths (torch.quantile, linear interpolation);
 //   depth -> clamp to [lo, hi], invalid pixels = hi (the metric target), then mapped to [-1, 1] and stacked x3 for the VAE;
 //   rgb, normals -> [-1, 1], normals renormalised, invalid pixels zeroed; lo == hi or no valid pixel -> zeros and an empty mask.
-// The quantiles are EXACT order statistics: a three-level radix select (11 + 11 + 10 key bits) over integer histograms, four ranks
-// per image at once (below / above neighbour of both quantiles) — integer atomics only, so the result is deterministic.
+// The quantiles are EXACT order statistics: the radix select of select.h over order_key(depth), two selections per image (the floor neighbour of
+// each quantile, its successor where the rank has a fraction) — integer atomics only, so the result is deterministic.
 #include "common.h"
+#include "select.h"
 #include <math.h>
 
 namespace e2eft {
 
-constexpr int DP_RANKS = 4;
-constexpr int DP_BINS = 2048;
+constexpr int DP_SEL = 2;             // selections per image: q_lo, q_hi
+constexpr int DP_MAX_BLOCKS = 256;    // blocks per image of the digit and successor passes
 
-struct DpSel {            // per (image, rank) selection state carried between levels
-    unsigned prefix;      // key bits fixed so far (left-aligned)
-    unsigned remaining;   // rank inside the elements that share the prefix
+struct DpLayout {
+    SelState* state;      // [B][DP_SEL]
+    uint32_t* hist;       // [B][DP_SEL][SEL_BINS]
+    uint32_t* mpart;      // [B][DP_SEL][DP_MAX_BLOCKS] successor partials
 };
-struct DpHead {           // per image
-    unsigned count;       // number of valid pixels
-    float w_lo, w_hi;     // interpolation weights of the two quantiles
-};
-
-__device__ __forceinline__ unsigned dp_key(float v) {   // order-preserving float -> uint32
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dp_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+static size_t dp_ws_bytes(int batch) { return (size_t)batch * DP_SEL * (sizeof(SelState) + (SEL_BINS + DP_MAX_BLOCKS) * sizeof(uint32_t)); }
+static DpLayout dp_layout(void* ws, int batch) {
+    DpLayout l;
+    l.state = (SelState*)ws;
+    l.hist = (uint32_t*)(l.state + (size_t)batch * DP_SEL);
+    l.mpart = l.hist + (size_t)batch * DP_SEL * SEL_BINS;
+    return l;
 }
 
-// level 0: count + histogram of the top 11 key bits of the valid pixels.  grid (blocks, B)
-__global__ __launch_bounds__(256) void dp_hist0(long n, float near, float far, const float* __restrict__ depth, unsigned* __restrict__ hist /* [B][2048] */) {
-    __shared__ unsigned h[DP_BINS];
-    for (int i = threadIdx.x; i < DP_BINS; i += 256) h[i] = 0;
-    __syncthreads();
+// torch.quantile: rank = q * (n - 1) in float32, floor / ceil neighbours, weight = the fractional part
+struct DpQuantileRank {
+    float q[DP_SEL];
+    __device__ SelRank operator()(int64_t n, int sel) const {
+        const float r = ((sel & 1) ? q[1] : q[0]) * (float)(n - 1);
+        const float f = floorf(r);
+        return SelRank{(int64_t)(unsigned)f, (unsigned)ceilf(r) != (unsigned)f, (double)(r - f)};
+    }
+};
+
+__global__ void dp_init_kernel(int nsel, SelState* __restrict__ state, uint32_t* __restrict__ hist) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)nsel * SEL_BINS) hist[i] = 0;
+    if (i < nsel) select_init(state + i, true);
+}
+
+// digit p of both selections over the valid pixels of image blockIdx.y.  grid (blocks, B)
+__global__ __launch_bounds__(256) void dp_hist_kernel(int p, long n, float near, float far, const float* __restrict__ depth, const SelState* __restrict__ state,
+                                                      uint32_t* __restrict__ hist) {
+    DigitHist<uint32_t, DP_SEL> h(p, state + blockIdx.y * DP_SEL);
+    if (!h.any) return;
+    h.zero();
     const float* d = depth + (long)blockIdx.y * n;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float v = d[i];
-        if (v > near && v < far) atomicAdd(&h[dp_key(v) >> 21], 1u);
+        if (v > near && v < far) h.add(order_key(v));
     }
-    __syncthreads();
-    unsigned* g = hist + (long)blockIdx.y * DP_BINS;
-    for (int i = threadIdx.x; i < DP_BINS; i += 256)
-        if (h[i]) atomicAdd(&g[i], h[i]);
+    h.flush(hist + (long)blockIdx.y * DP_SEL * SEL_BINS);
 }
 
-// one block per image: total count, the four ranks (torch.quantile: rank = q * (n - 1) in float32, floor / ceil neighbours, weight =
-// fractional part), then the bin of every rank in the level-0 histogram
-__global__ __launch_bounds__(256) void dp_scan0(float q_lo, float q_hi, const unsigned* __restrict__ hist, DpHead* __restrict__ head,
-                                                DpSel* __restrict__ sel /* [B][4] */) {
-    __shared__ unsigned cum[DP_BINS];
-    const unsigned* g = hist + (long)blockIdx.x * DP_BINS;
-    for (int i = threadIdx.x; i < DP_BINS; i += 256) cum[i] = g[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int i = 0; i < DP_BINS; ++i) { const unsigned c = cum[i]; cum[i] = run; run += c; }   // exclusive prefix (2048 adds, once per image)
-        DpHead hd;
-        hd.count = run;
-        unsigned ranks[DP_RANKS] = {0, 0, 0, 0};
-        hd.w_lo = hd.w_hi = 0.f;
-        if (run > 0) {
-            const float last = (float)(run - 1);
-            const float r_lo = q_lo * last, r_hi = q_hi * last;
-            const float f_lo = floorf(r_lo), f_hi = floorf(r_hi);
-            hd.w_lo = r_lo - f_lo;
-            hd.w_hi = r_hi - f_hi;
-            ranks[0] = (unsigned)f_lo; ranks[1] = (unsigned)ceilf(r_lo);
-            ranks[2] = (unsigned)f_hi; ranks[3] = (unsigned)ceilf(r_hi);
-        }
-        head[blockIdx.x] = hd;
-        for (int r = 0; r < DP_RANKS; ++r) {
-            int lo = 0, hi = DP_BINS - 1;            // last bin whose exclusive prefix <= rank
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (cum[mid] <= ranks[r]) lo = mid; else hi = mid - 1;
-            }
-            DpSel s;
-            s.prefix = (unsigned)lo << 21;
-            s.remaining = ranks[r] - cum[lo];
-            sel[blockIdx.x * DP_RANKS + r] = s;
-        }
-    }
-}
-
-// levels 1 / 2: histogram of the next SHIFT-window of key bits among the pixels matching each rank's prefix.  grid (blocks, B)
-template <int LEVEL>
-__global__ __launch_bounds__(256) void dp_hist(long n, float near, float far, const float* __restrict__ depth, const DpSel* __restrict__ sel,
-                                               unsigned* __restrict__ hist /* [B][4][2048] */) {
-    constexpr unsigned PMASK = LEVEL == 1 ? 0xFFE00000u : 0xFFFFFC00u;   // 11 / 22 fixed bits
-    constexpr int SHIFT = LEVEL == 1 ? 10 : 0;
-    constexpr unsigned BMASK = LEVEL == 1 ? 0x7FFu : 0x3FFu;
-    __shared__ unsigned h[DP_RANKS][DP_BINS];
-    for (int i = threadIdx.x; i < DP_RANKS * DP_BINS; i += 256) (&h[0][0])[i] = 0;
-    __syncthreads();
-    unsigned pre[DP_RANKS];
-#pragma unroll
-    for (int r = 0; r < DP_RANKS; ++r) pre[r] = sel[blockIdx.y * DP_RANKS + r].prefix;
+__global__ __launch_bounds__(256) void dp_min_kernel(long n, float near, float far, const float* __restrict__ depth, const SelState* __restrict__ state,
+                                                     uint32_t* __restrict__ mpart) {
+    SuccMin<uint32_t, DP_SEL> m(state + blockIdx.y * DP_SEL);
+    if (!m.any()) return;
     const float* d = depth + (long)blockIdx.y * n;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float v = d[i];
-        if (v > near && v < far) {
-            const unsigned k = dp_key(v);
-#pragma unroll
-            for (int r = 0; r < DP_RANKS; ++r)
-                if ((k & PMASK) == pre[r]) atomicAdd(&h[r][(k >> SHIFT) & BMASK], 1u);
-        }
+        if (v > near && v < far) m.take(order_key(v));
     }
-    __syncthreads();
-    unsigned* g = hist + (long)blockIdx.y * DP_RANKS * DP_BINS;
-    for (int i = threadIdx.x; i < DP_RANKS * DP_BINS; i += 256) {
-        const unsigned c = (&h[0][0])[i];
-        if (c) atomicAdd(&g[i], c);
-    }
+    m.store(mpart + (long)blockIdx.y * DP_SEL * DP_MAX_BLOCKS + blockIdx.x, DP_MAX_BLOCKS);
 }
 
-// one block per image, one wave per rank: locate the rank inside its histogram, extend the prefix.  The last level turns the four keys
-// into the two interpolated quantiles (torch.lerp's two-branch formula) and the ok flag.
-template <int LEVEL>
-__global__ __launch_bounds__(256) void dp_scan(const unsigned* __restrict__ hist, DpSel* __restrict__ sel, const DpHead* __restrict__ head,
-                                               float* __restrict__ out /* [B][4] = lo, hi, count, ok */) {
-    constexpr int SHIFT = LEVEL == 1 ? 10 : 0;
-    constexpr int NB = LEVEL == 1 ? 2048 : 1024;
-    __shared__ float val[DP_RANKS];
-    const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned* g = hist + ((long)blockIdx.x * DP_RANKS + r) * DP_BINS;
-    DpSel s = sel[blockIdx.x * DP_RANKS + r];
-    if (lane == 0) {
-        unsigned run = 0;
-        int b = 0;
-        for (; b < NB; ++b) {
-            const unsigned c = g[b];
-            if (run + c > s.remaining) break;
-            run += c;
-        }
-        if (b == NB) b = NB - 1;   // empty image: nothing selected, value unused
-        s.prefix |= (unsigned)b << SHIFT;
-        s.remaining -= run;
-        sel[blockIdx.x * DP_RANKS + r] = s;
-        if (LEVEL == 2) val[r] = dp_unkey(s.prefix);
+// one wave per image: the two interpolated quantiles and the ok flag
+__global__ __launch_bounds__(64) void dp_finish_kernel(int nblk, const SelState* __restrict__ state, const uint32_t* __restrict__ mpart,
+                                                       float* __restrict__ out /* [B][4] = lo, hi, count, ok */) {
+    const SelState* st = state + blockIdx.x * DP_SEL;
+    float q[DP_SEL];
+#pragma unroll
+    for (int j = 0; j < DP_SEL; ++j) {
+        const uint32_t b = select_successor(st[j], mpart + ((long)blockIdx.x * DP_SEL + j) * DP_MAX_BLOCKS, nblk);
+        q[j] = st[j].n ? quantile_lerp(order_value((uint32_t)st[j].prefix), order_value(b), (float)st[j].weight) : 0.f;
     }
-    if (LEVEL == 2) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const DpHead hd = head[blockIdx.x];
-            auto lerp = [](float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w); };
-            float lo = 0.f, hi = 0.f;
-            if (hd.count > 0) {
-                lo = lerp(val[0], val[1], hd.w_lo);
-                hi = lerp(val[2], val[3], hd.w_hi);
-            }
-            float* o = out + blockIdx.x * 4;
-            o[0] = lo; o[1] = hi; o[2] = (float)hd.count; o[3] = (hd.count > 0 && lo != hi) ? 1.f : 0.f;
-        }
-    }
+    if (threadIdx.x != 0) return;
+    const unsigned count = (unsigned)st[0].n;
+    float* o = out + blockIdx.x * 4;
+    o[0] = q[0]; o[1] = q[1]; o[2] = (float)count; o[3] = (count > 0 && q[0] != q[1]) ? 1.f : 0.f;
 }
 
 // the fused elementwise pass.  grid (blocks, B)
@@ -231,10 +160,6 @@ __global__ __launch_bounds__(256) void dp_align_normals(int h, int w, const uint
     }
 }
 
-static size_t dp_ws_bytes(int batch) {
-    return (size_t)batch * (DP_BINS + 2 * DP_RANKS * DP_BINS) * sizeof(unsigned) + (size_t)batch * (sizeof(DpHead) + DP_RANKS * sizeof(DpSel));
-}
-
 }  // namespace e2eft
 
 using namespace e2eft;
@@ -253,20 +178,16 @@ extern "C" int e2eft_masked_quantiles(int32_t batch, int64_t n, const float* dep
     E2EFT_REQUIRE(q_lo >= 0.f && q_lo <= 1.f && q_hi >= 0.f && q_hi <= 1.f, "masked_quantiles: quantiles must lie in [0, 1]");
     E2EFT_REQUIRE(ws_bytes >= dp_ws_bytes(batch), "masked_quantiles: workspace %zu < %zu bytes", ws_bytes, dp_ws_bytes(batch));
     hipStream_t s = (hipStream_t)stream;
-    unsigned* h0 = (unsigned*)workspace;
-    unsigned* h1 = h0 + (size_t)batch * DP_BINS;
-    unsigned* h2 = h1 + (size_t)batch * DP_RANKS * DP_BINS;
-    DpHead* head = (DpHead*)(h2 + (size_t)batch * DP_RANKS * DP_BINS);
-    DpSel* sel = (DpSel*)(head + batch);
-    if (hipMemsetAsync(workspace, 0, (size_t)batch * (DP_BINS + 2 * DP_RANKS * DP_BINS) * sizeof(unsigned), s) != hipSuccess)
-        return fail(E2EFT_ERR_LAUNCH, "masked_quantiles: memset failed");
-    const int blocks = cdiv(n, 256 * 16) < 256 ? cdiv(n, 256 * 16) : 256;
-    hipLaunchKernelGGL(dp_hist0, dim3(blocks, batch), dim3(256), 0, s, (long)n, near_plane, far_plane, depth, h0);
-    hipLaunchKernelGGL(dp_scan0, dim3(batch), dim3(256), 0, s, q_lo, q_hi, (const unsigned*)h0, head, sel);
-    hipLaunchKernelGGL((dp_hist<1>), dim3(blocks, batch), dim3(256), 0, s, (long)n, near_plane, far_plane, depth, (const DpSel*)sel, h1);
-    hipLaunchKernelGGL((dp_scan<1>), dim3(batch), dim3(256), 0, s, (const unsigned*)h1, sel, (const DpHead*)head, out);
-    hipLaunchKernelGGL((dp_hist<2>), dim3(blocks, batch), dim3(256), 0, s, (long)n, near_plane, far_plane, depth, (const DpSel*)sel, h2);
-    hipLaunchKernelGGL((dp_scan<2>), dim3(batch), dim3(256), 0, s, (const unsigned*)h2, sel, (const DpHead*)head, out);
+    const DpLayout l = dp_layout(workspace, batch);
+    const int blocks = cdiv(n, 256 * 16) < DP_MAX_BLOCKS ? cdiv(n, 256 * 16) : DP_MAX_BLOCKS;
+    const int nsel = batch * DP_SEL;
+    hipLaunchKernelGGL(dp_init_kernel, dim3(nsel * (SEL_BINS / 256)), dim3(256), 0, s, nsel, l.state, l.hist);
+    for (int p = 0; p < select_digits(32); ++p) {
+        hipLaunchKernelGGL(dp_hist_kernel, dim3(blocks, batch), dim3(256), 0, s, p, (long)n, near_plane, far_plane, depth, (const SelState*)l.state, l.hist);
+        hipLaunchKernelGGL((select_scan_kernel<uint32_t, DpQuantileRank>), dim3(nsel), dim3(SEL_BINS / 2), 0, s, p, l.hist, l.state, DpQuantileRank{{q_lo, q_hi}});
+    }
+    hipLaunchKernelGGL(dp_min_kernel, dim3(blocks, batch), dim3(256), 0, s, (long)n, near_plane, far_plane, depth, (const SelState*)l.state, l.mpart);
+    hipLaunchKernelGGL(dp_finish_kernel, dim3(batch), dim3(64), 0, s, blocks, (const SelState*)l.state, (const uint32_t*)l.mpart, out);
     return check_launch("masked_quantiles");
 }
 

@@ -9,31 +9,27 @@
 //                training loader makes of the file.
 //   record       invalid ratio, mean / std / min / max of the uint8 image and of u16 / 1000, the count of ids equal to 0 (the reference asserts
 //                there are none), a flag for a NaN among the valid brightness values, n, the percentile and the scale.
-// The percentile is an exact selection, not a sort: an MSB-first radix select over the order-preserving 64-bit image of the fp64 brightness, six
-// digits (11 11 11 11 11 9 bits), for every frame of the batch in the same launches.  The keys are never stored: each pass recomputes the
-// brightness from colour and id (10 B per pixel for fp16 colour, less than writing and re-reading an 8 B key would cost over six passes, and no
-// workspace that grows with the image).  Per pass: hp_hist_kernel (integer histogram of the digit in LDS over the keys that match the prefix
-// found so far, added to the frame's histogram with integer atomics: any order gives the same counts) and hp_select_kernel (one block per frame
-// scans the 2048 counts, fixes the digit that holds rank k_lo, clears the histogram).  After the last digit the key a of rank k_lo is known with
-// its multiplicity; rank k_lo + 1 is a again when a's run reaches it, otherwise the smallest key above a (hp_min_kernel, skipped by frames
-// that do not need it).  hp_scale_kernel turns a, b and the weight into the frame's scale; hp_apply_kernel writes the images and integer partial
+// The percentile is an exact selection, not a sort: the radix select of select.h over order_key(brightness), 64-bit keys in six digits, for every
+// frame of the batch in the same launches.  The keys are never stored: each pass recomputes the brightness from colour and id (10 B per pixel for
+// fp16 colour, less than writing and re-reading an 8 B key would cost over six passes, and no workspace that grows with the image).
+// hp_hist_kernel is the digit pass (the first one also counts the zero ids and the NaNs), hp_min_kernel the successor pass (skipped by frames that
+// do not need it).  hp_scale_kernel turns a, b and the weight into the frame's scale; hp_apply_kernel writes the images and integer partial
 // sums; hp_record_kernel writes the fp64 record.  All on the caller's stream, no host read-back: capturable in a graph.
 // Built with -ffp-contract=off: no FMA may fuse a product the reference rounds.
 #include "common.h"
+#include "select.h"
 
 namespace e2eft {
 
-constexpr int HP_THREADS = 256, HP_BINS = 2048, HP_TARGET_BLOCKS = 2048, HP_NSTATE = 8, HP_NSTAT = 10, HP_NREC = E2EFT_HYPERSIM_RECORD;
-constexpr uint64_t HP_SIGN = 0x8000000000000000ull;
-// state[frame]: 0 n (valid pixels), 1 rank still to resolve inside the prefix, 2 prefix = key of rank k_lo once complete, 3 b must come from the min pass,
-//               4 weight gamma (fp64 bits), 5 k_hi == k_lo
+constexpr int HP_THREADS = 256, HP_TARGET_BLOCKS = 2048, HP_NSTAT = 10, HP_NREC = E2EFT_HYPERSIM_RECORD;
+// state[frame]: the percentile's selection; n = the frame's valid pixels
 // stats[frame]: 0 ids equal to 0, 1 NaN brightness among valid, 2 sum u8, 3 sum u8^2, 4 min u8, 5 max u8, 6 sum u16, 7 sum u16^2, 8 min u16, 9 max u16
 
 struct HpLayout {
-    int64_t* state;
+    SelState* state;
     unsigned long long* stats;
     uint32_t* hist;
-    unsigned long long* mpart;
+    uint64_t* mpart;
     double* scale;
     size_t bytes;
 };
@@ -53,53 +49,49 @@ static inline HpLayout hp_layout(void* ws, int batch, int nblk) {
         o += (bytes + 15) & ~(size_t)15;
         return r;
     };
-    l.state = (int64_t*)take(sizeof(int64_t) * HP_NSTATE * batch);
+    l.state = (SelState*)take(sizeof(SelState) * batch);
     l.stats = (unsigned long long*)take(sizeof(unsigned long long) * HP_NSTAT * batch);
-    l.hist = (uint32_t*)take(sizeof(uint32_t) * HP_BINS * batch);
-    l.mpart = (unsigned long long*)take(sizeof(unsigned long long) * (size_t)nblk * batch);
+    l.hist = (uint32_t*)take(sizeof(uint32_t) * SEL_BINS * batch);
+    l.mpart = (uint64_t*)take(sizeof(uint64_t) * (size_t)nblk * batch);
     l.scale = (double*)take(sizeof(double) * batch);
     l.bytes = o;
     return l;
 }
 
-__device__ __forceinline__ uint64_t hp_key(double v) {      // unsigned order == numeric order (NaNs beyond the infinities, by sign)
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u & HP_SIGN) ? ~u : (u | HP_SIGN);
-}
-__device__ __forceinline__ double hp_unkey(uint64_t k) {
-    const uint64_t u = (k & HP_SIGN) ? (k & ~HP_SIGN) : ~k;
-    return __longlong_as_double((long long)u);
-}
 template <typename T> __device__ __forceinline__ double hp_brightness(const T* __restrict__ c) {     // hypersim_util.py:24-26, left to right
     return (0.3 * (double)c[0] + 0.59 * (double)c[1]) + 0.11 * (double)c[2];
 }
 
-__global__ void hp_init_kernel(int batch, int64_t* __restrict__ state, unsigned long long* __restrict__ stats, uint32_t* __restrict__ hist) {
+// numpy's "linear" percentile: virtual index 0.9 (n - 1) in fp64, k = its floor, gamma = the fraction; rank k + 1 is read unless k is the last
+struct HpPercentileRank {
+    __device__ SelRank operator()(int64_t n, int) const {
+        const double v = (double)(n - 1) * 0.9;
+        const double fl = floor(v);
+        return SelRank{(int64_t)fl, (int64_t)fl + 1 <= n - 1, v - fl};
+    }
+};
+
+__global__ void hp_init_kernel(int batch, SelState* __restrict__ state, unsigned long long* __restrict__ stats, uint32_t* __restrict__ hist) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int64_t)batch * HP_BINS) hist[i] = 0;
-    if (i < (int64_t)batch * HP_NSTATE) state[i] = 0;
+    if (i < (int64_t)batch * SEL_BINS) hist[i] = 0;
+    if (i < batch) select_init(state + i, true);
     if (i < (int64_t)batch * HP_NSTAT) {
         const int k = (int)(i % HP_NSTAT);
         stats[i] = (k == 4 || k == 8) ? ~0ull : 0ull;
     }
 }
 
-// histogram of the `width`-bit digit (key >> shift) over the valid pixels of frame blockIdx.y whose key bits from shift + width up equal the prefix's.
-// first pass (shift + width == 64): every valid pixel counts, and the ids equal to 0 and the NaN keys are counted for the record.
+// digit p of the keys of the valid pixels of frame blockIdx.y.  First pass: the ids equal to 0 and the NaN keys are counted for the record.
 template <typename T>
-__global__ __launch_bounds__(HP_THREADS) void hp_hist_kernel(int64_t n, int shift, int width, const T* __restrict__ color, const int32_t* __restrict__ ids,
-                                                             const int64_t* __restrict__ state, uint32_t* __restrict__ hist, unsigned long long* __restrict__ stats) {
-    __shared__ uint32_t h[HP_BINS];
+__global__ __launch_bounds__(HP_THREADS) void hp_hist_kernel(int64_t n, int p, const T* __restrict__ color, const int32_t* __restrict__ ids,
+                                                             const SelState* __restrict__ state, uint32_t* __restrict__ hist, unsigned long long* __restrict__ stats) {
     __shared__ uint32_t extra[2];
     const int f = blockIdx.y, t = threadIdx.x;
-    const int hi = shift + width;
-    const bool first = hi >= 64;
-    if (!first && state[(int64_t)f * HP_NSTATE] == 0) return;         // no valid pixel: nothing to select
-    for (int j = t; j < HP_BINS; j += HP_THREADS) h[j] = 0;
+    const bool first = p == 0;
+    DigitHist<uint64_t, 1> h(p, state + f);
+    if (!h.any) return;                                               // no valid pixel: nothing to select
     if (t < 2) extra[t] = 0;
-    __syncthreads();
-    const uint64_t prefix = first ? 0 : (uint64_t)state[(int64_t)f * HP_NSTATE + 2];
-    const uint32_t mask = (1u << width) - 1;
+    h.zero();
     const T* c = color + (int64_t)f * n * 3;
     const int32_t* id = ids + (int64_t)f * n;
     uint32_t zeros = 0, nans = 0;
@@ -109,131 +101,42 @@ __global__ __launch_bounds__(HP_THREADS) void hp_hist_kernel(int64_t n, int shif
         if (e == -1) continue;
         const double b = hp_brightness(c + i * 3);
         nans += b != b;
-        const uint64_t k = hp_key(b);
-        if (!first && (k >> hi) != (prefix >> hi)) continue;
-        atomicAdd(&h[(uint32_t)(k >> shift) & mask], 1u);
+        h.add(order_key(b));
     }
     if (first) {
         if (zeros) atomicAdd(&extra[0], zeros);
         if (nans) atomicAdd(&extra[1], nans);
     }
-    __syncthreads();
-    uint32_t* o = hist + (int64_t)f * HP_BINS;
-    for (int j = t; j < HP_BINS; j += HP_THREADS)
-        if (h[j]) atomicAdd(&o[j], h[j]);
+    h.flush(hist + (int64_t)f * SEL_BINS);
     if (first && t < 2 && extra[t]) atomicAdd(&stats[(int64_t)f * HP_NSTAT + t], (unsigned long long)extra[t]);
 }
 
-// one block per frame: scan the frame's histogram, find the digit that holds the rank, extend the prefix; clear the histogram for the next pass.
-// first pass: n = the total, k_lo = floor(0.9 (n - 1)), gamma = 0.9 (n - 1) - k_lo (numpy's "linear": (n - 1) * quantile in fp64).
-// last pass (shift == 0): the bin is the run of keys equal to a; b = a when the run reaches rank k_lo + 1.
-__global__ __launch_bounds__(1024) void hp_select_kernel(int shift, int width, uint32_t* __restrict__ hist, int64_t* __restrict__ state) {
-    __shared__ uint32_t wsum[16];
-    __shared__ int64_t pick[3];
-    const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t* hh = hist + (int64_t)f * HP_BINS;
-    int64_t* st = state + (int64_t)f * HP_NSTATE;
-    const bool first = shift + width >= 64;
-    if (!first && st[0] == 0) return;                                  // (its histogram was never touched: still clear)
-    const uint32_t c0 = hh[2 * t], c1 = hh[2 * t + 1];
-    hh[2 * t] = 0;
-    hh[2 * t + 1] = 0;
-    if (t == 0) pick[0] = pick[1] = pick[2] = 0;
-    uint32_t incl = c0 + c1;                                           // counts fit 32 bits: height * width < 2^31 (checked by the host)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < 16; ++w) {
-        if (w < wave) before += wsum[w];
-        total += wsum[w];
-    }
-    const uint32_t excl = before + incl - (c0 + c1);
-    int64_t k = st[1];
-    double gamma = 0.0;
-    if (first) {
-        if (total == 0) {
-            if (t == 0) st[0] = 0;
-            return;
-        }
-        const double v = (double)((int64_t)total - 1) * 0.9;
-        const double fl = floor(v);
-        k = (int64_t)fl;
-        gamma = v - fl;
-    }
-    if (k >= (int64_t)excl && k < (int64_t)excl + c0 + c1) {
-        const bool lo = k < (int64_t)excl + c0;
-        pick[0] = 2 * t + (lo ? 0 : 1);
-        pick[1] = k - excl - (lo ? 0 : c0);
-        pick[2] = lo ? c0 : c1;
-    }
-    __syncthreads();
-    if (t == 0) {
-        const uint64_t prefix = (first ? 0ull : (uint64_t)st[2]) | ((uint64_t)pick[0] << shift);
-        if (first) {
-            st[0] = total;
-            st[4] = __double_as_longlong(gamma);
-            st[5] = k + 1 > (int64_t)total - 1;                        // n == 1: both ranks are the one value
-        }
-        st[1] = pick[1];
-        st[2] = (int64_t)prefix;
-        if (shift == 0) st[3] = (st[5] == 0 && pick[1] + 1 >= pick[2]) ? 1 : 0;
-    }
-}
-
-// b where a's run ends at rank k_lo: the smallest key above a among the valid pixels, per block
+// b where a's run ends at rank k and the last histogram holds nothing above it: the smallest key above a among the valid pixels, per block
 template <typename T>
-__global__ __launch_bounds__(HP_THREADS) void hp_min_kernel(int64_t n, const T* __restrict__ color, const int32_t* __restrict__ ids, const int64_t* __restrict__ state,
-                                                            unsigned long long* __restrict__ mpart) {
-    const int f = blockIdx.y, t = threadIdx.x;
-    const int64_t* st = state + (int64_t)f * HP_NSTATE;
-    if (st[0] == 0 || st[3] == 0) return;
-    const uint64_t a = (uint64_t)st[2];
+__global__ __launch_bounds__(HP_THREADS) void hp_min_kernel(int64_t n, const T* __restrict__ color, const int32_t* __restrict__ ids, const SelState* __restrict__ state,
+                                                            uint64_t* __restrict__ mpart) {
+    const int f = blockIdx.y;
+    SuccMin<uint64_t, 1> mn(state + f);
+    if (!mn.any()) return;
     const T* c = color + (int64_t)f * n * 3;
     const int32_t* id = ids + (int64_t)f * n;
-    unsigned long long mn = ~0ull;
-    for (int64_t i = (int64_t)blockIdx.x * HP_THREADS + t; i < n; i += (int64_t)gridDim.x * HP_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * HP_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * HP_THREADS) {
         if (id[i] == -1) continue;
-        const uint64_t k = hp_key(hp_brightness(c + i * 3));
-        if (k > a && k < mn) mn = k;
+        mn.take(order_key(hp_brightness(c + i * 3)));
     }
-    mn = wave_min(mn);
-    __shared__ unsigned long long red[HP_THREADS / 64];
-    if ((t & 63) == 0) red[t >> 6] = mn;
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < HP_THREADS / 64; ++w) mn = red[w] < mn ? red[w] : mn;
-        mpart[(int64_t)f * gridDim.x + blockIdx.x] = mn;
-    }
+    mn.store(mpart + (int64_t)f * gridDim.x + blockIdx.x, 0);
 }
 
 // one wave per frame: percentile (numpy's _lerp: a + (b - a) t, or b - (b - a) (1 - t) where t >= 0.5; NaN when a valid brightness is NaN) -> scale
-__global__ __launch_bounds__(64) void hp_scale_kernel(int nblk, double numerator, const int64_t* __restrict__ state, const unsigned long long* __restrict__ stats,
-                                                      const unsigned long long* __restrict__ mpart, double* __restrict__ scale, double* __restrict__ record) {
-    const int f = blockIdx.x, t = threadIdx.x;
-    const int64_t* st = state + (int64_t)f * HP_NSTATE;
-    const bool need = st[0] != 0 && st[3] != 0;
-    unsigned long long mn = ~0ull;
-    if (need)
-        for (int j = t; j < nblk; j += 64) {
-            const unsigned long long u = mpart[(int64_t)f * nblk + j];
-            mn = u < mn ? u : mn;
-        }
-    mn = wave_min(mn);
-    if (t != 0) return;
+__global__ __launch_bounds__(64) void hp_scale_kernel(int nblk, double numerator, const SelState* __restrict__ state, const unsigned long long* __restrict__ stats,
+                                                      const uint64_t* __restrict__ mpart, double* __restrict__ scale, double* __restrict__ record) {
+    const int f = blockIdx.x;
+    const SelState* st = state + f;
+    const uint64_t bkey = select_successor(*st, mpart + (int64_t)f * nblk, nblk);
+    if (threadIdx.x != 0) return;
     double p = __longlong_as_double(0x7ff8000000000000LL), s = 1.0;
-    if (st[0] != 0) {
-        if (stats[(int64_t)f * HP_NSTAT + 1] == 0) {
-            const double a = hp_unkey((uint64_t)st[2]);
-            const double b = need ? hp_unkey(mn) : a;
-            const double g = __longlong_as_double(st[4]);
-            const double diff = b - a;
-            p = g >= 0.5 ? b - diff * (1.0 - g) : a + diff * g;
-        }
+    if (st->n != 0) {
+        if (stats[(int64_t)f * HP_NSTAT + 1] == 0) p = quantile_lerp(order_value(st->prefix), order_value(bkey), st->weight);
         s = p < 1e-4 ? 0.0 : numerator / p;
     }
     scale[f] = s;
@@ -320,12 +223,12 @@ __device__ __forceinline__ double hp_std(unsigned long long cnt, unsigned long l
     return sqrt(d) / (double)cnt;
 }
 
-__global__ void hp_record_kernel(int batch, int64_t n, const int64_t* __restrict__ state, const unsigned long long* __restrict__ stats, double* __restrict__ record) {
+__global__ void hp_record_kernel(int batch, int64_t n, const SelState* __restrict__ state, const unsigned long long* __restrict__ stats, double* __restrict__ record) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= batch) return;
     const unsigned long long* s = stats + (int64_t)f * HP_NSTAT;
     double* r = record + (int64_t)f * HP_NREC;
-    const int64_t nv = state[(int64_t)f * HP_NSTATE];
+    const int64_t nv = state[f].n;
     r[0] = (double)(n - nv) / (double)n;
     r[1] = (double)s[2] / (double)(3 * n);
     r[2] = hp_std(3ull * n, s[2], s[3]);
@@ -361,23 +264,22 @@ static void hp_launch(const e2eft_hypersim_desc& d, const HpLayout& l, int nblk,
     const int64_t n = (int64_t)d.height * d.width;
     const TC* c = (const TC*)color;
     const dim3 grid(nblk, d.batch);
-    const int64_t ninit = (int64_t)d.batch * HP_BINS;
+    const int64_t ninit = (int64_t)d.batch * SEL_BINS;
     hipLaunchKernelGGL(hp_init_kernel, dim3((unsigned)((ninit + 255) / 256)), dim3(256), 0, s, d.batch, l.state, l.stats, l.hist);
-    static const int shifts[6] = {53, 42, 31, 20, 9, 0}, widths[6] = {11, 11, 11, 11, 11, 9};
-    for (int p = 0; p < 6; ++p) {
-        hipLaunchKernelGGL((hp_hist_kernel<TC>), grid, dim3(HP_THREADS), 0, s, n, shifts[p], widths[p], c, ids, (const int64_t*)l.state, l.hist, l.stats);
-        hipLaunchKernelGGL(hp_select_kernel, dim3(d.batch), dim3(1024), 0, s, shifts[p], widths[p], l.hist, l.state);
+    for (int p = 0; p < select_digits(64); ++p) {
+        hipLaunchKernelGGL((hp_hist_kernel<TC>), grid, dim3(HP_THREADS), 0, s, n, p, c, ids, (const SelState*)l.state, l.hist, l.stats);
+        hipLaunchKernelGGL((select_scan_kernel<uint64_t, HpPercentileRank>), dim3(d.batch), dim3(SEL_BINS / 2), 0, s, p, l.hist, l.state, HpPercentileRank{});
     }
-    hipLaunchKernelGGL((hp_min_kernel<TC>), grid, dim3(HP_THREADS), 0, s, n, c, ids, (const int64_t*)l.state, l.mpart);
-    hipLaunchKernelGGL(hp_scale_kernel, dim3(d.batch), dim3(64), 0, s, nblk, d.scale_numerator, (const int64_t*)l.state, (const unsigned long long*)l.stats,
-                       (const unsigned long long*)l.mpart, l.scale, record);
+    hipLaunchKernelGGL((hp_min_kernel<TC>), grid, dim3(HP_THREADS), 0, s, n, c, ids, (const SelState*)l.state, l.mpart);
+    hipLaunchKernelGGL(hp_scale_kernel, dim3(d.batch), dim3(64), 0, s, nblk, d.scale_numerator, (const SelState*)l.state, (const unsigned long long*)l.stats,
+                       (const uint64_t*)l.mpart, l.scale, record);
     if (d.depth_format == E2EFT_HYPERSIM_DEPTH_U16)
         hipLaunchKernelGGL((hp_apply_kernel<TC, TD, uint16_t>), grid, dim3(HP_THREADS), 0, s, d.height, d.width, d.focal, c, (const TD*)dist, ids,
                            (const double*)l.scale, rgb, (uint16_t*)depth, l.stats);
     else
         hipLaunchKernelGGL((hp_apply_kernel<TC, TD, float>), grid, dim3(HP_THREADS), 0, s, d.height, d.width, d.focal, c, (const TD*)dist, ids,
                            (const double*)l.scale, rgb, (float*)depth, l.stats);
-    hipLaunchKernelGGL(hp_record_kernel, dim3((d.batch + 63) / 64), dim3(64), 0, s, d.batch, n, (const int64_t*)l.state, (const unsigned long long*)l.stats, record);
+    hipLaunchKernelGGL(hp_record_kernel, dim3((d.batch + 63) / 64), dim3(64), 0, s, d.batch, n, (const SelState*)l.state, (const unsigned long long*)l.stats, record);
 }
 
 }  // namespace e2eft

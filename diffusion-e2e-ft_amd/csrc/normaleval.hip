@@ -6,10 +6,11 @@
 // Update (HBM-bound): one pass over (pred, gt, mask) with arbitrary element strides writes the errors into a dense fp32 buffer (a masked-out pixel
 // gets +inf, which sorts above every valid value as an unsigned bit pattern) and reduces the update's totals over fixed per-block partials in a
 // fixed order (no atomics: bit-reproducible), then adds them to the running totals on the device.
-// Finalize: the exact median by a radix select on the fp32 bit patterns (11 / 11 / 10 bit digits, LDS histograms, one-block scans), the second
-// middle element of an even count from the last histogram or one unsigned-min pass, and the fp64 record.  Nothing is read back to the host: the
-// launch sequence is fixed and capturable in a graph; the kernels read the counts they need from device memory.
+// Finalize: the exact median by the radix select of select.h with the fp32 bit patterns as keys (the errors are >= 0), the second middle element
+// of an even count as its successor, and the fp64 record.  Nothing is read back to the host: the launch sequence is fixed and capturable in a
+// graph; the kernels read the counts they need from device memory.
 #include "common.h"
+#include "select.h"
 
 namespace e2eft {
 
@@ -18,37 +19,26 @@ constexpr int NE_UTHREADS = 256;
 constexpr int NE_NTOT = 9;            // totals: int64 n, nan, count[5]; double sum, sumsq
 constexpr int NE_HBLK = 512;          // finalize: histogram / min partial blocks
 constexpr int NE_HTHREADS = 512;
-constexpr int NE_BINS = 2048;
 constexpr uint32_t NE_INF_BITS = 0x7f800000u;
-
-// select state in the workspace (8-byte words)
-//   0 active (n > 0 and no NaN)   1 rank of a inside the current prefix   2 prefix bits of a (after the last pass: a itself)
-//   3 b bits (valid when 4 == 0)  4 b still unknown: the min pass finds it   5 even n
-constexpr int NE_NSTATE = 8;
 
 struct NeLayout {
     int64_t* upart;       // [NE_UBLK][NE_NTOT] update partials (counts as int64, sums as double bit patterns)
-    uint32_t* hpart;      // [NE_HBLK][NE_BINS] histogram partials
-    uint32_t* hsum;       // [NE_BINS] summed histogram
-    uint32_t* mpart;      // [NE_HBLK] min partials
-    int64_t* state;       // [NE_NSTATE]
+    SelState* state;      // the median's selection
+    uint32_t* hist;       // [SEL_BINS]
+    uint32_t* mpart;      // [NE_HBLK] successor partials
 };
 
-static size_t ne_bytes() {
-    return (size_t)NE_UBLK * NE_NTOT * 8 + (size_t)NE_HBLK * NE_BINS * 4 + (size_t)NE_BINS * 4 + (size_t)NE_HBLK * 4 + NE_NSTATE * 8;
-}
+static size_t ne_bytes() { return (size_t)NE_UBLK * NE_NTOT * 8 + sizeof(SelState) + (size_t)SEL_BINS * 4 + (size_t)NE_HBLK * 4; }
 
 static NeLayout ne_layout(void* ws) {
     NeLayout l;
     char* p = (char*)ws;
     l.upart = (int64_t*)p;
     p += (size_t)NE_UBLK * NE_NTOT * 8;
-    l.state = (int64_t*)p;
-    p += NE_NSTATE * 8;
-    l.hpart = (uint32_t*)p;
-    p += (size_t)NE_HBLK * NE_BINS * 4;
-    l.hsum = (uint32_t*)p;
-    p += (size_t)NE_BINS * 4;
+    l.state = (SelState*)p;
+    p += sizeof(SelState);
+    l.hist = (uint32_t*)p;
+    p += (size_t)SEL_BINS * 4;
     l.mpart = (uint32_t*)p;
     return l;
 }
@@ -159,154 +149,57 @@ __global__ __launch_bounds__(256) void ne_update_reduce_kernel(int nblk, const i
     }
 }
 
-// select setup: rank (n-1)/2 of the n valid values; nothing to select when n == 0 or a NaN is among them (the record is NaN)
-__global__ void ne_select_init_kernel(const int64_t* __restrict__ totals, int64_t* __restrict__ state) {
-    if (threadIdx.x != 0) return;
-    const int64_t n = totals[0], nan = totals[1];
-    state[0] = n > 0 && nan == 0;
-    state[1] = n > 0 ? (n - 1) / 2 : 0;
-    state[2] = 0;
-    state[3] = 0;
-    state[4] = 0;
-    state[5] = n > 0 && (n & 1) == 0;
+// the median's rank rule: rank (n - 1) / 2 of the n valid values, and its successor when n is even
+struct NeMedianRank {
+    __device__ SelRank operator()(int64_t n, int) const { return SelRank{(n - 1) / 2, (n & 1) == 0, 0.0}; }
+};
+
+// select setup: nothing to select when n == 0 or a NaN is among the valid values (the record is NaN).  grid SEL_BINS / 256 x 256
+__global__ void ne_init_kernel(const int64_t* __restrict__ totals, SelState* __restrict__ state, uint32_t* __restrict__ hist) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    hist[i] = 0;
+    if (i == 0) select_init(state, totals[0] > 0 && totals[1] == 0);
 }
 
-// histogram of the WIDTH-bit digit (u >> SHIFT) over the values u < +inf whose bits from SHIFT + WIDTH up equal the prefix's
-template <int SHIFT, int WIDTH>
-__global__ __launch_bounds__(NE_HTHREADS) void ne_hist_kernel(int64_t m, const uint32_t* __restrict__ bits, const int64_t* __restrict__ state,
-                                                              uint32_t* __restrict__ hpart) {
-    __shared__ uint32_t h[NE_BINS];
-    for (int j = threadIdx.x; j < NE_BINS; j += NE_HTHREADS) h[j] = 0;
-    __syncthreads();
-    const bool active = state[0] != 0;
-    constexpr int HI = SHIFT + WIDTH;
-    const uint32_t prefix = (uint32_t)state[2];
-    if (active) {
-        auto take = [&](uint32_t u) {
-            if (u >= NE_INF_BITS) return;
-            if (HI < 32 && (u >> (HI & 31)) != (prefix >> (HI & 31))) return;
-            atomicAdd(&h[(u >> SHIFT) & ((1u << WIDTH) - 1)], 1u);
-        };
-        const int64_t m4 = m >> 2;
-        const u32x4* b4 = reinterpret_cast<const u32x4*>(bits);
-        for (int64_t i = (int64_t)blockIdx.x * NE_HTHREADS + threadIdx.x; i < m4; i += (int64_t)gridDim.x * NE_HTHREADS) {
-            const u32x4 v = b4[i];
-            take(v.x);
-            take(v.y);
-            take(v.z);
-            take(v.w);
-        }
-        if (blockIdx.x == 0 && threadIdx.x < (m & 3)) take(bits[m4 * 4 + threadIdx.x]);
+// digit p of the values u < +inf
+__global__ __launch_bounds__(NE_HTHREADS) void ne_hist_kernel(int p, int64_t m, const uint32_t* __restrict__ bits, const SelState* __restrict__ state,
+                                                              uint32_t* __restrict__ hist) {
+    DigitHist<uint32_t, 1> h(p, state);
+    if (!h.any) return;
+    h.zero();
+    auto take = [&](uint32_t u) {
+        if (u < NE_INF_BITS) h.add(u);
+    };
+    const int64_t m4 = m >> 2;
+    const u32x4* b4 = reinterpret_cast<const u32x4*>(bits);
+    for (int64_t i = (int64_t)blockIdx.x * NE_HTHREADS + threadIdx.x; i < m4; i += (int64_t)gridDim.x * NE_HTHREADS) {
+        const u32x4 v = b4[i];
+        take(v.x);
+        take(v.y);
+        take(v.z);
+        take(v.w);
     }
-    __syncthreads();
-    uint32_t* o = hpart + (int64_t)blockIdx.x * NE_BINS;
-    for (int j = threadIdx.x; j < NE_BINS; j += NE_HTHREADS) o[j] = h[j];
+    if (blockIdx.x == 0 && threadIdx.x < (m & 3)) take(bits[m4 * 4 + threadIdx.x]);
+    h.flush(hist);
 }
 
-// column sums of the histogram partials: block j owns 64 bins, its 16 waves take every 16th partial (integer sums: any order gives the same)
-__global__ __launch_bounds__(1024) void ne_hist_sum_kernel(int nblk, const uint32_t* __restrict__ hpart, uint32_t* __restrict__ hsum) {
-    __shared__ uint32_t red[16][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, bin = blockIdx.x * 64 + lane;
-    uint32_t v = 0;
-#pragma unroll 8
-    for (int j = wave; j < nblk; j += 16) v += hpart[(int64_t)j * NE_BINS + bin];
-    red[wave][lane] = v;
-    __syncthreads();
-    if (wave == 0) {
-        for (int w = 1; w < 16; ++w) v += red[w][lane];
-        hsum[bin] = v;
-    }
-}
-
-// one-block scan of the summed histogram: the digit that holds the current rank, the rank inside it, the new prefix.  After the last digit
-// (SHIFT == 0) the prefix is a; for an even count, b is a again when the bin holds the next rank, else the next non-empty bin, else the min pass.
-template <int SHIFT, int WIDTH>
-__global__ __launch_bounds__(1024) void ne_select_kernel(const uint32_t* __restrict__ hsum, int64_t* __restrict__ state) {
-    if (state[0] == 0) return;
-    __shared__ uint32_t wsum[16];
-    __shared__ int64_t pick[3];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) pick[0] = pick[1] = pick[2] = 0;              // (not reached while the counts are consistent)
-    const uint32_t c0 = hsum[2 * t], c1 = hsum[2 * t + 1];
-    uint32_t incl = c0 + c1;                                  // inclusive scan over the threads' bin pairs (counts fit 32 bits: m < 2^32 checked by the host)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    const uint32_t excl = before + incl - (c0 + c1);
-    __syncthreads();
-    const int64_t k = state[1];
-    if (k >= (int64_t)excl && k < (int64_t)excl + c0 + c1) {
-        const bool first = k < (int64_t)excl + c0;
-        const uint32_t dig = 2 * t + (first ? 0 : 1);
-        const int64_t r = k - excl - (first ? 0 : c0);
-        pick[0] = dig;
-        pick[1] = r;
-        pick[2] = first ? c0 : c1;
-    }
-    __syncthreads();
-    const uint32_t dig = (uint32_t)pick[0];
-    const uint32_t prefix = (uint32_t)state[2] | (dig << SHIFT);
-    if (SHIFT == 0 && state[5]) {
-        // b = rank k + 1: inside a's bin, or the first non-empty bin above it (a wave-wide search from thread 0's view), else unknown
-        __shared__ int next;
-        if (t == 0) next = NE_BINS;
-        __syncthreads();
-        if (c0 && 2 * t > (int)dig) atomicMin(&next, 2 * t);
-        else if (c1 && 2 * t + 1 > (int)dig) atomicMin(&next, 2 * t + 1);
-        __syncthreads();
-        if (t == 0) {
-            if (pick[1] + 1 < pick[2]) {
-                state[3] = prefix;
-                state[4] = 0;
-            } else if (next < NE_BINS) {
-                state[3] = (prefix & ~((1u << WIDTH) - 1)) | (uint32_t)next;
-                state[4] = 0;
-            } else {
-                state[4] = 1;
-            }
-        }
-    }
-    if (t == 0) {
-        state[1] = pick[1];
-        state[2] = prefix;
-    }
-}
-
-// b when it lies outside a's last histogram: the unsigned minimum of the values above a (and below +inf)
-__global__ __launch_bounds__(NE_HTHREADS) void ne_min_kernel(int64_t m, const uint32_t* __restrict__ bits, const int64_t* __restrict__ state,
+// b when it lies outside a's last histogram: the smallest value above a (and below +inf)
+__global__ __launch_bounds__(NE_HTHREADS) void ne_min_kernel(int64_t m, const uint32_t* __restrict__ bits, const SelState* __restrict__ state,
                                                              uint32_t* __restrict__ mpart) {
-    if (state[0] == 0 || state[4] == 0) return;
-    const uint32_t a = (uint32_t)state[2];
-    uint32_t mn = NE_INF_BITS;
+    SuccMin<uint32_t, 1> mn(state);
+    if (!mn.any()) return;
     for (int64_t i = (int64_t)blockIdx.x * NE_HTHREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * NE_HTHREADS) {
         const uint32_t u = bits[i];
-        if (u > a && u < mn) mn = u;
+        if (u < NE_INF_BITS) mn.take(u);
     }
-    mn = wave_min(mn);
-    __shared__ uint32_t red[NE_HTHREADS / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < NE_HTHREADS / 64; ++w) mn = min(mn, red[w]);
-        mpart[blockIdx.x] = mn;
-    }
+    mn.store(mpart + blockIdx.x, 0);
 }
 
 // the record [mean, median, rmse, a1..a5, n] (utils.py:167-177; NaN as numpy: a NaN error makes mean, median, rmse NaN, the a_i count it in n)
-__global__ __launch_bounds__(64) void ne_finish_kernel(int nblk, const int64_t* __restrict__ totals, const int64_t* __restrict__ state,
+__global__ __launch_bounds__(64) void ne_finish_kernel(int nblk, const int64_t* __restrict__ totals, const SelState* __restrict__ state,
                                                        const uint32_t* __restrict__ mpart, double* __restrict__ out) {
-    const int t = threadIdx.x;
-    uint32_t mn = NE_INF_BITS;
-    if (state[0] && state[4])
-        for (int j = t; j < nblk; j += 64) mn = min(mn, mpart[j]);
-    mn = wave_min(mn);
-    if (t != 0) return;
+    const uint32_t bkey = select_successor(*state, mpart, nblk);
+    if (threadIdx.x != 0) return;
     const int64_t n = totals[0], nan = totals[1];
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     const double dn = (double)n;
@@ -314,9 +207,9 @@ __global__ __launch_bounds__(64) void ne_finish_kernel(int nblk, const int64_t* 
     if (n > 0 && nan == 0) {
         mean = __longlong_as_double(totals[7]) / dn;
         rmse = sqrt(__longlong_as_double(totals[8]) / dn);
-        const float a = __uint_as_float((uint32_t)state[2]);
-        if (state[5]) {
-            const float b = __uint_as_float(state[4] ? mn : (uint32_t)state[3]);
+        const float a = __uint_as_float((uint32_t)state->prefix);
+        if (state->succ_needed) {
+            const float b = __uint_as_float(bkey);
             median = (double)(__fmul_rn(__fadd_rn(a, b), 0.5f));     // np.median of float32: the float32 mean of the two middle values
         } else {
             median = (double)a;
@@ -369,17 +262,12 @@ extern "C" int e2eft_normal_eval_finalize(const float* err, int64_t count, const
     hipStream_t s = (hipStream_t)stream;
     const NeLayout l = ne_layout(workspace);
     const uint32_t* bits = (const uint32_t*)err;
-    hipLaunchKernelGGL(ne_select_init_kernel, dim3(1), dim3(64), 0, s, totals, l.state);
-    hipLaunchKernelGGL((ne_hist_kernel<21, 11>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
-    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
-    hipLaunchKernelGGL((ne_select_kernel<21, 11>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
-    hipLaunchKernelGGL((ne_hist_kernel<10, 11>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
-    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
-    hipLaunchKernelGGL((ne_select_kernel<10, 11>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
-    hipLaunchKernelGGL((ne_hist_kernel<0, 10>), dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.hpart);
-    hipLaunchKernelGGL(ne_hist_sum_kernel, dim3(NE_BINS / 64), dim3(1024), 0, s, NE_HBLK, (const uint32_t*)l.hpart, l.hsum);
-    hipLaunchKernelGGL((ne_select_kernel<0, 10>), dim3(1), dim3(1024), 0, s, (const uint32_t*)l.hsum, l.state);
-    hipLaunchKernelGGL(ne_min_kernel, dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const int64_t*)l.state, l.mpart);
-    hipLaunchKernelGGL(ne_finish_kernel, dim3(1), dim3(64), 0, s, NE_HBLK, totals, (const int64_t*)l.state, l.mpart, out);
+    hipLaunchKernelGGL(ne_init_kernel, dim3(SEL_BINS / 256), dim3(256), 0, s, totals, l.state, l.hist);
+    for (int p = 0; p < select_digits(32); ++p) {
+        hipLaunchKernelGGL(ne_hist_kernel, dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, p, count, bits, (const SelState*)l.state, l.hist);
+        hipLaunchKernelGGL((select_scan_kernel<uint32_t, NeMedianRank>), dim3(1), dim3(SEL_BINS / 2), 0, s, p, l.hist, l.state, NeMedianRank{});
+    }
+    hipLaunchKernelGGL(ne_min_kernel, dim3(NE_HBLK), dim3(NE_HTHREADS), 0, s, count, bits, (const SelState*)l.state, l.mpart);
+    hipLaunchKernelGGL(ne_finish_kernel, dim3(1), dim3(64), 0, s, NE_HBLK, totals, (const SelState*)l.state, (const uint32_t*)l.mpart, out);
     return check_launch("normal_eval_finalize");
 }
