@@ -105,6 +105,8 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
     auto epi_rofs = [&](const int r) -> long { return (long)(r & 31) + (long)(r >> 5) * W; };
     auto epi_rows_left = [&]() -> int { return 0x40000000; };
     constexpr int EPI_DEP = WIN;
+    constexpr bool EPI_M16 = false;      // (the 32x32 accumulator layout)
+    auto epi_srow = [&](const int s) -> int { return 8 * s; };
 #define EPI_STAMP(i) do { } while (0)
 #include "igemm_persistent_epilogue.inc"
 #undef EPI_STAMP

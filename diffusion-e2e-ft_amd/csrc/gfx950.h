@@ -9,7 +9,6 @@ namespace e2eft {
 template <int V> using IConst = std::integral_constant<int, V>;      // a compile-time int as a lambda argument (static stage / piece / slice indices)
 
 // ---- v_mfma_f32_32x32x16_{f16,bf16}: A and B are 8 sixteen-bit k-slots per lane in four dwords, C / D 16 fp32 per lane.
-// (narrow.hip's v_mfma_f32_16x16x32 is another instruction with another layout and keeps its own wrapper.)
 template <typename T> struct Mma32x32x16;
 template <> struct Mma32x32x16<f16> {
     __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
@@ -19,6 +18,20 @@ template <> struct Mma32x32x16<f16> {
 template <> struct Mma32x32x16<bf16> {
     __device__ static __forceinline__ floatx16 run(const u32x4& a, const u32x4& b, floatx16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
+    }
+};
+
+// ---- v_mfma_f32_16x16x32_{f16,bf16}: A and B as above (lane = row / column lane & 15, k-slots 8 (lane >> 4) .. + 7), C / D 4 fp32 per lane: column lane & 15,
+// rows 4 (lane >> 4) + register.  Same flops per matrix-pipe cycle as the 32x32x16 form; it holds the SIMD's vector issue for 8 of its 16 cycles.
+template <typename T> struct Mma16x16x32;
+template <> struct Mma16x16x32<f16> {
+    __device__ static __forceinline__ floatx4 run(const u32x4& a, const u32x4& b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
+    }
+};
+template <> struct Mma16x16x32<bf16> {
+    __device__ static __forceinline__ floatx4 run(const u32x4& a, const u32x4& b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
     }
 };
 

@@ -434,6 +434,8 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         return (long)r + (long)(fast_div(c_mb + r, p.out_seg) - c_seg0) * p.out_seg;
     };
     constexpr int EPI_DEP = RING;
+    constexpr bool EPI_M16 = false;      // (the 32x32 accumulator layout)
+    auto epi_srow = [&](const int s) -> int { return 8 * s; };
 #define EPI_STAMP(i) STAMP5(tseq, i)
 #include "igemm_persistent_epilogue.inc"
 #undef EPI_STAMP

@@ -29,6 +29,10 @@
 // 1065 -> 1182, 256->128 @768^2 1011 -> 1138: +10.7 ... +13.8 %; the step of BASELINE configs[1] 107.0 -> 99.1 ms.
 // NORM variant (inference, cout <= 128; template flag): the input is read through a GroupNorm(+SiLU) that was never applied — see the kernel's comment.
 // LDS: 2 x 43 KiB patch buffers + 3 x 16 KiB weight ring + 6 KiB statistics deposits + 8 KiB dump = 148 KiB (+ 5 KiB coefficient table with NORM).
+// MFMA form (template flag M16, chosen per launch by the planner's table below; E2EFT_OPT_PATCH_MFMA): v_mfma_f32_32x32x16, or v_mfma_f32_16x16x32 at the same output tile
+// per wave.  Under back-to-back launches the chip holds its clock down (the package sits at its power cap), and the clock it holds depends on the MFMA shape: 512 -> 512
+// @192^2 runs at 1745 MHz instead of 1579 with +1.8 % cycles, 128 -> 128 @768^2 at 1666 instead of 1541 with +4.5 % (GRBM_GUI_ACTIVE / 8 / kernel time) — 4 to 8 % less
+// wall time per shape, the step 88.6 -> 86.5 ms (profiles/mfma_shape_ab.txt).  The fused-norm variants and the fp32-from-splits variant stay on 32x32x16.
 // Summation order: per output element k runs (chunk, tap) instead of (tap, chunk) — fp32 accumulation, results differ from igemm5 in the
 // last bits (documented in include/e2eft.h; deterministic run to run).
 #include "igemm.h"
@@ -68,12 +72,17 @@ template <int KT> struct Geo {
 // arithmetic of gn_apply_kernel (norm.hip) — the convolution's result is bit-identical to GroupNorm followed by igemm6.  Padding rows stay zero.
 // F32O (round 6, e2eft_conv2d_fwd_f32split): an fp32 convolution whose products are formed on the f16 matrix pipe — A is the two-plane f16 split of an fp32 tensor,
 // the weights are split the same way, K runs over the three blocks (x0, w0), (x0, w1), (x1, w0) (IgemmParams::split_c), bias / residual / output are fp32 (epilogue_f32).
-template <typename T, bool RES, bool NORM, int KT, bool F32O = false>
+// M16: the MFMA form.  false: v_mfma_f32_32x32x16, a wave's 64 x 64 block as 2 x 2 accumulators; true: v_mfma_f32_16x16x32 — 4 x 4 accumulators of four registers (64, as
+// before), a k-tile = two k-steps of 32 channels, each four A and four B fragments (one ds_read_b128 each: the same LDS bytes per flop) and 16 MFMAs.  Lane (r = lane & 15,
+// q = lane >> 4) takes the 16-byte chunk 4 ks + q of a row for A and B alike.  The 16-row fragment read wants another patch swizzle than the 32-row one (no XOR swizzle serves
+// both: tests/test_patch_swizzle_banks.py holds the bank model): chunk ^ (((row >> 1) & 3) << 1) — it enters where a lane picks the source chunk it fetches (jc16; the fused
+// norm's units follow from that) and in the fragment address.  The weight stage keeps its swizzle (fragments start at multiples of 16 rows: conflict-free as it is).
+template <typename T, bool RES, bool NORM, int KT, bool F32O = false, bool M16 = false>
 __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const int total_tiles) {
     using namespace patchk;
     using G = Geo<KT>;
     static_assert(KT == 3 || (KT == 2 && !NORM), "taps: 3x3, or 2x2 without the fused GroupNorm");
-    static_assert(!F32O || (RES && !NORM && std::is_same<T, f16>::value), "fp32 output: the fp32-window epilogue, f16 split operands");
+    static_assert(!F32O || (RES && !NORM && !M16 && std::is_same<T, f16>::value), "fp32 output: the fp32-window epilogue, f16 split operands, the 32x32x16 form");
     constexpr int NT = G::NT, PW = G::PW, PROWS = G::PROWS, PPIECES = G::PPIECES, NPI = G::NPI, PATCH = G::PATCH, OFF_B = G::OFF_B, OFF_DEP = G::OFF_DEP, OFF_DUMP = G::OFF_DUMP;
     constexpr int OFF_TAB = G::OFF_TAB, OFF_TABM = G::OFF_TABM;
     __shared__ __attribute__((aligned(128))) char smem[NORM ? G::LDS_NORM : G::LDS];
@@ -84,6 +93,7 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, h = lane >> 5;
+    const int r15 = lane & 15, q4 = lane >> 4;   // (M16)
     const int nch = p.cin >> 6;              // 64-channel chunks, host: >= 2
     const int H = p.hl, W = p.wl;            // the convolution's (logical) input = output size; with the fused 2x nearest upsample the source is hin x win = H/2 x W/2
     const int Hs = p.hin, Ws = p.win;
@@ -104,7 +114,9 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
 
     // ---- loader state
     // A: piece j = wave + 8 i (i = 0..5) covers patch rows 8 j .. 8 j + 7; this lane's row and its swizzled 16-byte chunk are fixed
-    const int jc16 = ((lane & 7) ^ ((4 * wave + (lane >> 4)) & 7)) * 16;   // ((patch row >> 1) & 7 = (4 j + (lane >> 4)) & 7, 32 i = 0 mod 8)
+    // (M16: (patch row >> 1) & 3 = (lane >> 4) & 3)
+    const int jc16 = M16 ? ((lane & 7) ^ (((lane >> 4) & 3) << 1)) * 16
+                         : ((lane & 7) ^ ((4 * wave + (lane >> 4)) & 7)) * 16;   // ((patch row >> 1) & 7 = (4 j + (lane >> 4)) & 7, 32 i = 0 mod 8)
     int pyx[NPI];                             // (patch y << 16) | patch x of the lane's row in piece i; y = 0x4000 for rows beyond the patch
     int pix[NPI];                             // pixel index of that row inside the loader's image, -1 = padding / no tile
 #pragma unroll
@@ -274,6 +286,23 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
         }
     };
+    // M16: a group is eight MFMAs of 16 cycles, each holding the vector issue for 8 of them: two VALU behind each of the first five, one behind each of the last three
+    auto interleave = [&]() {
+        if constexpr (M16) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+            }
+        } else {
+            interleave4();
+        }
+    };
     auto norm_store = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
         // padding rows (zeros from the out-of-range fetch) stay zero and pieces beyond the 43rd do not exist: their results go to the dump kilobyte.  An address
@@ -295,20 +324,37 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         case 7: asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory"); break;
         case 8: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
         case 9: asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory"); break;
+        case 10: asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;   // (M16 without a residual: four bias and four row-vector columns per lane)
+        case 11: asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory"); break;
         default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
         }
     };
-    floatx16 acc[2][2];
+    std::conditional_t<M16, floatx4[4][4], floatx16[2][2]> acc;
     // B fragment byte offsets inside a stage (read-side swizzle as igemm2.hip); A: computed per k-tile from the patch row
     int bofs[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) bofs[g] = (wn * 64 + l31) * 128 + (((g * 2 + h) ^ ((l31 >> 1) & 7)) * 16);
-    const int rbase = 2 * wm * PW + l31;      // patch row of this lane's first output pixel at tap (0, 0)
+    const int rbase = 2 * wm * PW + (M16 ? r15 : l31);      // patch row of this lane's first output pixel at tap (0, 0)
+    // M16: B fragment j (16 weight rows) of k-step ks = (b16 ^ (ks << 6)) + 2048 j — (row >> 1) & 7 = r15 >> 1 for every j
+    const int b16 = (wn * 64 + r15) * 128 + ((q4 ^ (r15 >> 1)) << 4);
+    // rows i0, i0 + 1 of the wave's 4 x 4 accumulators: two A fragments against the four B fragments of one k-step
+    auto mma_rows = [&](auto i0c, const u32x4& a0, const u32x4& a1, const u32x4 (&b)[4], auto zc) {
+        constexpr int i0 = decltype(i0c)::value;
+        if constexpr (M16) {
+            const floatx4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i0][j] = Mma16x16x32<T>::run(a0, b[j], decltype(zc)::value ? z : acc[i0][j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i0 + 1][j] = Mma16x16x32<T>::run(a1, b[j], decltype(zc)::value ? z : acc[i0 + 1][j]);
+        }
+    };
     auto mma_group = [&](const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
-        acc[0][0] = Mma32x32x16<T>::run(a0, b0, acc[0][0]);
-        acc[0][1] = Mma32x32x16<T>::run(a0, b1, acc[0][1]);
-        acc[1][0] = Mma32x32x16<T>::run(a1, b0, acc[1][0]);
-        acc[1][1] = Mma32x32x16<T>::run(a1, b1, acc[1][1]);
+        if constexpr (!M16) {
+            acc[0][0] = Mma32x32x16<T>::run(a0, b0, acc[0][0]);
+            acc[0][1] = Mma32x32x16<T>::run(a0, b1, acc[0][1]);
+            acc[1][0] = Mma32x32x16<T>::run(a1, b0, acc[1][0]);
+            acc[1][1] = Mma32x32x16<T>::run(a1, b1, acc[1][1]);
+        }
     };
 
     // ---- epilogue operands requested ahead of their use (as igemm5)
@@ -318,11 +364,15 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
     constexpr bool has_res = RES && !F32O;      // (F32O requests its fp32 bias / residual inside epilogue_f32)
     const bool has_ra = rowadd != nullptr, stats = p.gn_partial != nullptr;
     Vec16<T> pre_res[4], pre_bias, pre_ra;
-    T col_bias[2], col_ra[2];
+    T col_bias[M16 ? 4 : 2], col_ra[M16 ? 4 : 2];
     long c_orow = 0, c_rrow = 0;              // element offsets of output / residual pixel (image row 2 wm of the tile, column er) at this lane's chunk
     int c_n0 = 0, c_img = 0, c_mt = 0, c_ncl = 0;
     bool c_colok = false;
-    const int npre = F32O ? 0 : has_res ? 4 + (bias ? 1 : 0) + (has_ra ? 1 : 0) : 2 * ((bias ? 1 : 0) + (has_ra ? 1 : 0));
+    const int npre = F32O ? 0 : has_res ? 4 + (bias ? 1 : 0) + (has_ra ? 1 : 0) : (M16 ? 4 : 2) * ((bias ? 1 : 0) + (has_ra ? 1 : 0));
+    // M16 with a residual: slice s of the fp32-window epilogue holds rows 4 (er >> 1) + (er & 1) + epi_srow(s) of the wave's block (igemm_persistent_epilogue.inc)
+    const int er_row = (M16 && RES) ? 4 * (er >> 1) + (er & 1) : er;
+    constexpr bool EPI_M16 = M16;
+    auto epi_srow = [&](const int s) -> int { return M16 ? 16 * (s >> 1) + 2 * (s & 1) : 8 * s; };
     bool nxt = false;
 
     auto enter_tile = [&]() {   // the MFMA side enters the tile the loader is on; then the loader's coordinates move to the workgroup's next tile
@@ -330,8 +380,8 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         c_colok = c_n0 + wn * 64 + ec * 8 < p.N;
         c_ncl = c_colok ? c_n0 + wn * 64 + ec * 8 : c_n0;
         const long py0 = (long)d_img * H + d_oy0 + 2 * wm;
-        c_orow = (py0 * Wo + d_ox0 + er) * p.ldo + c_ncl;
-        c_rrow = (py0 * W + d_ox0 + er) * p.ldr + c_ncl;
+        c_orow = (py0 * Wo + d_ox0 + er_row) * p.ldo + c_ncl;
+        c_rrow = (py0 * W + d_ox0 + er_row) * p.ldr + c_ncl;
         nxt = u_dma + nslots < cend;
         if (nxt) tile_coords(u_dma + nslots);
     };
@@ -360,18 +410,43 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             b0[sl] = *reinterpret_cast<const u32x4*>(smem + sb + bofs[g]);
             b1[sl] = *reinterpret_cast<const u32x4*>(smem + sb + bofs[g] + 32 * 128);
         };
+        // M16: fragment i of the wave's four 16-row blocks = image row i >> 1 of its two, pixels 16 (i & 1) .. + 15: 16 rows further on the swizzle key is the same one.
+        // Fourteen fragment slots: the eight of k-step 0, the four B of k-step 1, and two more A — k-step 1's A fragments are requested behind the first eight MFMAs, into
+        // the two slots those are done with and the two spare ones, so that (as in the other form) every read of the stage is out one group ahead of the barrier
+        const int P0 = pcur + pr0 * 128 + ((q4 ^ (((pr0 >> 1) & 3) << 1)) << 4);
+        const int P1 = pcur + pr1 * 128 + ((q4 ^ (((pr1 >> 1) & 3) << 1)) << 4);
+        u32x4 fa[6], fb[2][4];
+        auto rd_a = [&](auto ksc, auto ic, auto slotc) {
+            constexpr int ks = decltype(ksc)::value, i = decltype(ic)::value, sl = decltype(slotc)::value;
+            fa[sl] = *reinterpret_cast<const u32x4*>(smem + (((i >> 1) ? P1 : P0) ^ (ks << 6)) + (i & 1) * 2048);
+        };
+        auto rd_b = [&](auto ksc) {
+            constexpr int ks = decltype(ksc)::value;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fb[ks][j] = *reinterpret_cast<const u32x4*>(smem + ((sb + b16) ^ (ks << 6)) + j * 2048);
+        };
         constexpr bool NRM = NORM && t >= 2 && t <= 7;      // this k-tile normalises piece t - 2 of the next patch (landed since the previous k-tile's wait)
         // the unit and the coefficients of its first four channels are requested FIRST: LDS returns in order, so the wait the compiler puts in front of group 0's
         // first MFMA (for fragments requested after these) covers them
         if constexpr (NRM) norm_issue(IConst<t - 2>{}, pnext);
-        rd(IConst<0>{}, IConst<0>{});
-        rd(IConst<1>{}, IConst<1>{});
+        if constexpr (M16) {
+            rd_a(IConst<0>{}, IConst<0>{}, IConst<0>{}); rd_a(IConst<0>{}, IConst<1>{}, IConst<1>{});
+            rd_a(IConst<0>{}, IConst<2>{}, IConst<2>{}); rd_a(IConst<0>{}, IConst<3>{}, IConst<3>{});
+            rd_b(IConst<0>{});
+        } else {
+            rd(IConst<0>{}, IConst<0>{});
+            rd(IConst<1>{}, IConst<1>{});
+        }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NRM) norm_ready();
-        rd(IConst<2>{}, IConst<2>{});
+        if constexpr (M16) rd_b(IConst<1>{});
+        else rd(IConst<2>{}, IConst<2>{});
         if constexpr (!(CK == 2 && t == NT - 2)) fire_b(bs_dst, kofs);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (CK == 1 && t == 0) {
+        constexpr bool ZI = CK == 1 && t == 0;      // the tile's first k-tile multiplies into the constant 0
+        if constexpr (M16) {
+            mma_rows(IConst<0>{}, fa[0], fa[1], fb[0], std::bool_constant<ZI>{});
+        } else if constexpr (CK == 1 && t == 0) {
             const floatx16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             acc[0][0] = Mma32x32x16<T>::run(a0[0], b0[0], z);
             acc[0][1] = Mma32x32x16<T>::run(a0[0], b1[0], z);
@@ -380,7 +455,7 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         } else {
             mma_group(a0[0], a1[0], b0[0], b1[0]);
         }
-        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<0>{}); interleave4(); }
+        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<0>{}); interleave(); }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (CK == 1 && t == 0) enter_tile();
         if constexpr (t == 0) {
@@ -392,9 +467,16 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             if constexpr (F32O) {
             } else if (has_res) {
 #pragma unroll
-                for (int s = 0; s < 4; ++s) pre_res[s] = ld16((const T*)p.residual + c_rrow + (long)(s * 8) * p.ldr);
+                for (int s = 0; s < 4; ++s) pre_res[s] = ld16((const T*)p.residual + c_rrow + (long)epi_srow(s) * p.ldr);   // (slices 0-3: the wave's first image row)
                 if (bias) pre_bias = ld16(bias + c_ncl);
                 if (has_ra) pre_ra = ld16(rowadd + (long)c_img * p.N + c_ncl);
+            } else if constexpr (M16) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int cj = c_n0 + wn * 64 + 16 * j + r15, nj = cj < p.N ? cj : c_n0;
+                    if (bias) col_bias[j] = bias[nj];
+                    if (has_ra) col_ra[j] = rowadd[(long)c_img * p.N + nj];
+                }
             } else {
                 const int cA = c_n0 + wn * 64 + l31, cB = cA + 32;
                 const int nA = cA < p.N ? cA : c_n0, nB = cB < p.N ? cB : c_n0;
@@ -407,12 +489,18 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             __builtin_amdgcn_sched_barrier(0);
             fire_b(bs_dst, kofs);
         }
-        rd(IConst<3>{}, IConst<0>{});
+        if constexpr (M16) {
+            rd_a(IConst<1>{}, IConst<0>{}, IConst<0>{}); rd_a(IConst<1>{}, IConst<1>{}, IConst<1>{});
+            rd_a(IConst<1>{}, IConst<2>{}, IConst<4>{}); rd_a(IConst<1>{}, IConst<3>{}, IConst<5>{});
+        } else {
+            rd(IConst<3>{}, IConst<0>{});
+        }
         if constexpr (AN >= 1) fire_a(IConst<AF>{}, pnext);   // (3x3: k-tiles 6-8 of a chunk issue the two weight pieces only)
         if constexpr (AN >= 2) fire_a(IConst<AF + 1>{}, pnext);
         __builtin_amdgcn_sched_barrier(0);
         mma_group(a0[1], a1[1], b0[1], b1[1]);
-        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<1>{}); interleave4(); }
+        mma_rows(IConst<2>{}, fa[2], fa[3], fb[0], std::bool_constant<ZI>{});
+        if constexpr (NRM) { norm_pair(IConst<0>{}, IConst<1>{}); interleave(); }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NRM) norm_issue2();                // coefficients of the last four channels: back before the barrier (its lgkmcnt(0))
         // lgkmcnt(0): this wave's reads of the current stage have RETURNED before the barrier lets others overwrite it
@@ -424,9 +512,11 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         if constexpr (NRM) norm_mark();
         __builtin_amdgcn_sched_barrier(0);
         mma_group(a0[2], a1[2], b0[2], b1[2]);
-        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<0>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); }
+        mma_rows(IConst<0>{}, fa[0], fa[1], fb[1], std::false_type{});
+        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<0>{}); interleave(); __builtin_amdgcn_sched_barrier(0); }
         mma_group(a0[0], a1[0], b0[0], b1[0]);
-        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<1>{}); interleave4(); __builtin_amdgcn_sched_barrier(0); norm_store(IConst<t - 2>{}); }
+        mma_rows(IConst<2>{}, fa[4], fa[5], fb[1], std::false_type{});
+        if constexpr (NRM) { norm_pair(IConst<1>{}, IConst<1>{}); interleave(); __builtin_amdgcn_sched_barrier(0); norm_store(IConst<t - 2>{}); }
         asm volatile("" ::: "memory");
         { const int x = bs_cur; bs_cur = bs_nxt; bs_nxt = bs_dst; bs_dst = x; }
         if constexpr (t == NT - 1) { const int x = pcur; pcur = pnext; pnext = x; }
@@ -484,7 +574,44 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
 
 static std::atomic<long> g_patch_launches{0};
 
+// the planner's table: which classes of launch run the 16x16x32 form by default — each adopted by wall time on random data, beyond the spread of the 32x32x16 form's own
+// repeats (profiles/mfma_shape_ab.txt, fp16, batch 8, three alternations on one box; spreads <= 0.6 %):
+//   3x3, cout >= 256 (512 -> 512 @192^2 -8.0 %, @96^2 -7.8 %, 256 -> 256 @384^2 -6.6 %), the 320 / 640-channel layers (640 -> 640 @96^2 -7.7 %, 320 -> 320 @96^2 -4 %),
+//   the 2x2 parity phases (256 -> 256, 384^2 -> 768^2: -3.3 %).  Every class that was measured won, so the table has no shape bounds; what keeps a 3x3 launch on the other
+//   form is the fused-norm rule of patch_form16 alone (128 -> 128 and 256 -> 128 @768^2 would gain 5.9 / 7.4 % as plain launches).
+static bool patch_form16_table(int dtype, int taps, int cin, int cout, long pixels) {
+    (void)cin; (void)cout; (void)pixels;
+    return (dtype == E2EFT_F16 || dtype == E2EFT_BF16) && (taps == 9 || taps == 4);
+}
+
+// ---- the MFMA form of a launch.  By default (E2EFT_OPT_PATCH_MFMA = 0) a function of dtype, taps, input channels, output channels and pixel count, and of nothing else —
+// in particular NOT of whether the GroupNorm is fused into the read: the fused launch is bit-equal to GroupNorm + the plain launch of the same problem
+// (tests/test_fused_norm_conv_gpu.py), and the two forms of one problem differ in the last bits.  The fused-norm variants are NOT instantiated in the 16x16x32 form: its
+// fourteen fragment slots (twelve in the other form) on top of the norm's registers do not fit (256 registers and 1 / 6 spilled ones without / with a residual).  So the
+// problems a fused-norm launch can have (3x3, cin <= NORM_CMAX, one N tile) keep the 32x32x16 form for their plain launches too.
+// Option 1: always 32x32x16.  Option 2 (A/B measurements, tests): 16x16x32 for every launch whose variant is instantiated — all but the fused-norm ones.
+static bool patch_form16(int dtype, const IgemmParams& p) {
+    if (p.split_c > 0) return false;                                   // the fp32-from-splits variant: its accuracy bars were measured on 32x32x16
+    const int mode = option(E2EFT_OPT_PATCH_MFMA);
+    if (mode == 1) return false;
+    if (mode == 2) return !p.nrm_ad;
+    if (p.kh == 3 && p.cin <= patchk::NORM_CMAX && p.N <= patchk::BN) return false;
+    return patch_form16_table(dtype, p.kh * p.kw, p.cin, p.N, (long)p.M);
+}
+
 template <typename T> static int launch6(IgemmParams& p, int total, int grid, hipStream_t s) {
+    const char* tn = std::is_same<T, f16>::value ? "_Float16" : "__bf16";
+    if (patch_form16(std::is_same<T, f16>::value ? E2EFT_F16 : E2EFT_BF16, p)) {
+        if (p.kh == 2) {
+            hipLaunchKernelGGL((igemm6_kernel<T, false, false, 2, false, true>), dim3(grid), dim3(512), 0, s, p, total);
+            tag_kernel("igemm6_kernel<%s, m16, false, false, 2>", tn);
+            return check_launch("igemm6");
+        }
+        if (p.residual) hipLaunchKernelGGL((igemm6_kernel<T, true, false, 3, false, true>), dim3(grid), dim3(512), 0, s, p, total);
+        else hipLaunchKernelGGL((igemm6_kernel<T, false, false, 3, false, true>), dim3(grid), dim3(512), 0, s, p, total);
+        tag_kernel("igemm6_kernel<%s, m16, %s, false>", tn, p.residual ? "true" : "false");
+        return check_launch("igemm6");
+    }
     if constexpr (std::is_same<T, f16>::value) {
         if (p.split_c > 0) {   // an fp32 convolution from f16 split planes (patch_eligible): 3x3, or a 2x2 parity phase of an upsampler convolution
             if (p.kh == 2) hipLaunchKernelGGL((igemm6_kernel<f16, true, false, 2, true>), dim3(grid), dim3(512), 0, s, p, total);

@@ -1,9 +1,10 @@
 // igemm_persistent_epilogue.inc — the two epilogues and the statistics merge of the persistent implicit-GEMM kernels, included INSIDE the kernel
-// body of igemm5.hip (rows of a tile = 256 consecutive GEMM rows) and igemm6.hip (rows = an 8 x 32-pixel block of one image).  It defines the
+// body of igemm5.hip and convin.hip (rows of a tile = 256 consecutive GEMM rows) and igemm6.hip (rows = an 8 x 32-pixel block of one image).  It defines the
 // lambdas epilogue_packed(sfree, zoff_o), epilogue(sfree, zoff_o), epilogue_f32(sfree, al) (fp32 bias / residual / output: csrc/f32split.hip), combine(img, slab, n0) over names the including kernel provides:
 //   smem, wave, lane, l31, h, er, ec, acc[2][2], p, T, f2, bias, rowadd, has_res, has_ra, stats, pre_res[4], pre_bias, pre_ra, col_bias[2],
 //   col_ra[2], c_orow / c_rrow (element offsets of row `er` of the wave's 64-row block at this lane's 8-column chunk), c_colok, tid, BN,
-//   EPI_DEP (LDS offset of the per-wave statistics deposits), EPI_STAMP(i), and
+//   EPI_DEP (LDS offset of the per-wave statistics deposits), EPI_STAMP(i), EPI_M16 (constexpr bool: acc is the 4 x 4 x floatx4 layout of v_mfma_f32_16x16x32 —
+//   lane owns columns 16 j + lane & 15, rows 4 (lane >> 4) + e of 16-row block i), epi_srow(s): first row of slice s of the fp32-window epilogue (8 s; EPI_M16: see there), and
 //   epi_rofs(r): pixel-row offset of row r (a multiple of 8) of the wave's 64-row block relative to its row 0 — r in igemm5, (r & 31) + (r >> 5) * W in igemm6.
     // ---- the epilogue of the MFMA-side tile (c_m0, c_n0): out = alpha * (acc + bias + rowadd[img]) + residual, eight slices per wave
     // Tiles WITHOUT a residual: everything that is per column (alpha, bias, row vector, GroupNorm statistics) is done in the accumulator layout,
@@ -15,9 +16,10 @@
         const float al = p.alpha;
         T* __restrict__ out = (T*)p.out + zoff_o;
         const f2 al2 = {al, al};
-        f2 bva[2], rav[2], pv[2], sm[2], sq[2];   // per owned column j: bias * alpha, row vector, pivot, shifted sums (pairs = two rows at a time)
+        constexpr int NJ = EPI_M16 ? 4 : 2;      // columns a lane owns: 32 j + l31, or (EPI_M16) 16 j + (lane & 15)
+        f2 bva[NJ], rav[NJ], pv[NJ], sm[NJ], sq[NJ];   // per owned column j: bias * alpha, row vector, pivot, shifted sums (pairs = two rows at a time)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             // association as in the fp32 epilogue below and igemm2's vector row pass: fma(rowadd, alpha, fma(acc, alpha, bias * alpha))
             const float bj = bias ? to_f(col_bias[j]) * al : 0.f, rj = has_ra ? to_f(col_ra[j]) : 0.f;
             bva[j] = f2{bj, bj}; rav[j] = f2{rj, rj};
@@ -25,10 +27,37 @@
         }
         // physical dword of (row pair rp8, column x) inside a window: ((x >> 2) & 1) * 256 + rp8 * 32 + (x >> 3) * 4 + (x & 3): readers take the
         // 16-byte units `lane` and `64 + lane`
-        const int wofs = ((l31 >> 2) & 1) * 256 + h * 64 + (l31 >> 3) * 4 + (l31 & 3);   // + qq * 128 + t * 32 + j * 16
+        int wofs = ((l31 >> 2) & 1) * 256 + h * 64 + (l31 >> 3) * 4 + (l31 & 3);   // + qq * 128 + t * 32 + j * 16
+        // EPI_M16 (the 16x16x32 accumulators: a lane owns columns 16 j + lane & 15, rows 4 (lane >> 4) + e of the 16-row block i): a round is one block, the lane's
+        // row pairs are 2 (lane >> 4) + t — same window, same readers; + t * 32 + j * 8
+        if constexpr (EPI_M16) wofs = (((lane & 15) >> 2) & 1) * 256 + (lane >> 4) * 64 + ((lane & 15) >> 3) * 4 + (lane & 3);
         auto wr = [&](auto rc_) {
             constexpr int r = decltype(rc_)::value, i = r >> 1;
             unsigned* wb = win + (r & 1) * 512 + wofs;
+            if constexpr (EPI_M16) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        f2 x = {acc[r][j][2 * t], acc[r][j][2 * t + 1]};
+                        x = __builtin_elementwise_fma(x, al2, bva[j]);
+                        if (has_ra) x = __builtin_elementwise_fma(rav[j], al2, x);
+                        if (stats) {
+                            if (r == 0 && t == 0) {   // pivot of a column: its first value in the wave (held by the lane >> 4 = 0 lane)
+                                const float p0 = __shfl(x[0], lane & 15, 64);
+                                pv[j] = f2{p0, p0};
+                            }
+                            const f2 d = x - pv[j];
+                            sm[j] += d;
+                            sq[j] = __builtin_elementwise_fma(d, d, sq[j]);
+                        }
+                        T e2[2] = {from_f<T>(x[0]), from_f<T>(x[1])};
+                        unsigned u;
+                        __builtin_memcpy(&u, e2, 4);
+                        wb[t * 32 + j * 8] = u;
+                    }
+                return;
+            }
 #pragma unroll
             for (int qq = 0; qq < 2; ++qq) {
                 constexpr int dummy = 0; (void)dummy;
@@ -79,6 +108,20 @@
         round(IConst<0>{}); round(IConst<1>{}); round(IConst<2>{}); round(IConst<3>{});
         if (stats) {   // uniform: per column totals = both halves of the pair accumulators + the other half-wave; h = 0 lanes deposit their two columns
             float* dep = reinterpret_cast<float*>(smem + EPI_DEP);
+            if constexpr (EPI_M16) {   // the four lanes lane & 15 of a column: a fixed butterfly; lane >> 4 = 0 deposits its four columns
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    float su = sm[j][0] + sm[j][1], s2 = sq[j][0] + sq[j][1];
+                    su += __shfl_xor(su, 16, 64);
+                    s2 += __shfl_xor(s2, 16, 64);
+                    su += __shfl_xor(su, 32, 64);
+                    s2 += __shfl_xor(s2, 32, 64);
+                    if (lane < 16) {
+                        float* d3 = dep + (wave * 64 + 16 * j + lane) * 3;
+                        d3[0] = su; d3[1] = s2; d3[2] = pv[j][0];
+                    }
+                }
+            } else
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 float su = sm[j][0] + sm[j][1], s2 = sq[j][0] + sq[j][1];
@@ -97,7 +140,11 @@
         float* win = reinterpret_cast<float*>(smem + sfree + wave * 4096);   // two 2-KiB slice windows
         // window layout: 16-byte unit U = ((x >> 2) & 1) * 64 + row * 8 + (x >> 3) for logical (row, column x): the row-wise readers take
         // units `lane` and `64 + lane` (two conflict-free contiguous kilobytes), the accumulator lanes write 2-way (free on ds_write_b32)
-        const int wofs = ((l31 >> 2) & 1) * 256 + h * 128 + (l31 >> 3) * 4 + (l31 & 3);   // in floats; + e * 32 + j * 16
+        int wofs = ((l31 >> 2) & 1) * 256 + h * 128 + (l31 >> 3) * 4 + (l31 & 3);   // in floats; + e * 32 + j * 16
+        // EPI_M16: all lanes write every slice when slice s = rows 4 q + 2 (s & 1) + e (q = 0 .. 3, e = 0, 1) of the 16-row block s >> 1: window row 2 q + e, so the reader
+        // of window row `er` holds row 4 (er >> 1) + (er & 1) + epi_srow(s) of the wave's block (c_orow / c_rrow are that row's; epi_srow(s) = 16 (s >> 1) + 2 (s & 1), else 8 s).
+        // + e * 32 + j * 8.  (These writes are 4-way on a bank, twice the 2-way ones' time: 64 writes per tile.)
+        if constexpr (EPI_M16) wofs = (((lane & 15) >> 2) & 1) * 256 + (lane >> 4) * 64 + ((lane & 15) >> 3) * 4 + (lane & 3);
         const float al = p.alpha;
         T* __restrict__ out = (T*)p.out + zoff_o;
         const T* __restrict__ res = (const T*)p.residual;   // c_rrow carries the batch offset
@@ -112,6 +159,12 @@
         auto wr = [&](auto sc_) {
             constexpr int s = decltype(sc_)::value, i = s >> 2, q = s & 3;
             float* wb = win + (s & 1) * 512 + wofs;
+            if constexpr (EPI_M16) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) wb[e * 32 + j * 8] = acc[s >> 1][j][2 * (s & 1) + e];
+            } else
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -123,7 +176,7 @@
             if constexpr (s == 0) {
                 if (has_res) {   // residual rows of slices 4-7: consumed four slices from now
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) late_res[t] = ld16(res + c_rrow + epi_rofs((4 + t) * 8) * p.ldr);
+                    for (int t = 0; t < 4; ++t) late_res[t] = ld16(res + c_rrow + epi_rofs(epi_srow(4 + t)) * p.ldr);
                 }
             }
             if constexpr (s < 7) wr(IConst<s + 1>{});
@@ -148,7 +201,7 @@
             Vec16<T> o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(x2[e >> 1][e & 1]);
-            if (c_colok) st16(out + c_orow + epi_rofs(s * 8) * p.ldo, o);
+            if (c_colok) st16(out + c_orow + epi_rofs(epi_srow(s)) * p.ldo, o);
             if (stats) {
                 if constexpr (s == 0) {   // pivot: the wave's first row, broadcast down the eight row-lanes of every chunk
 #pragma unroll
@@ -238,6 +291,7 @@
         auto wr = [&](auto sc_) {
             constexpr int s = decltype(sc_)::value, i = s >> 2, q = s & 3;
             float* wb = win + (s & 1) * 512 + wofs;
+            if constexpr (!EPI_M16)      // (the fp32-output variants exist in the 32x32 layout only)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll

@@ -5,7 +5,7 @@
 // leaves HBM/L2 ~1.27 times, and a thread finishes one output pixel with packed 2-way dot products (v_dot2_f32_f16 / _bf16, fp32
 // accumulate).  Measured (8 x 768^2, 128 -> 3, fp16): 0.68 ms vs 1.36 ms on the implicit-GEMM kernel; the HBM floor is 0.2 ms — the
 // remaining time is the weight stream (scalar loads share lgkmcnt with the LDS reads, so every halo read waits for both).
-#include "common.h"
+#include "gfx950.h"
 
 namespace e2eft {
 
@@ -125,18 +125,6 @@ __global__ __launch_bounds__(256) void conv3x3_narrow_kernel(const NarrowParams 
 // pixel, lane >> 4 = 8-channel group), the weight fragments of a 64-channel chunk (9 taps x 2 slabs, zero rows beyond cout) sit in 72
 // registers.  The dot-product form issues 864 v_dot2 per thread and chunk (~7k VALU cycles per wave) and streams the weights through the
 // scalar cache; here a wave issues 72 MFMAs (1.2k matrix-pipe cycles) per chunk and the kernel is bound by the halo traffic.
-template <typename T> struct Mma16;
-template <> struct Mma16<f16> {
-    __device__ static __forceinline__ floatx4 run(const u32x4& a, const u32x4& b, floatx4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma16<bf16> {
-    __device__ static __forceinline__ floatx4 run(const u32x4& a, const u32x4& b, floatx4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bhalf8, a), __builtin_bit_cast(bhalf8, b), c, 0, 0, 0);
-    }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void conv3x3_narrow_mfma_kernel(const NarrowParams p, const T* __restrict__ wg) {
     __shared__ __attribute__((aligned(16))) char halo[NR_H * NR_H * NR_PIX];
@@ -224,8 +212,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_narrow_mfma_kernel(const Narro
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
                     const char* px = halo + ((ty + ky) * NR_H + m + kx) * NR_PIX + kq * 16;
-                    acc[rb] = Mma16<T>::run(*reinterpret_cast<const u32x4*>(px), bf[ky * 3 + kx][0], acc[rb]);
-                    if (nch > 32) acc[rb] = Mma16<T>::run(*reinterpret_cast<const u32x4*>(px + 64), bf[ky * 3 + kx][1], acc[rb]);
+                    acc[rb] = Mma16x16x32<T>::run(*reinterpret_cast<const u32x4*>(px), bf[ky * 3 + kx][0], acc[rb]);
+                    if (nch > 32) acc[rb] = Mma16x16x32<T>::run(*reinterpret_cast<const u32x4*>(px + 64), bf[ky * 3 + kx][1], acc[rb]);
                 }
         }
     }

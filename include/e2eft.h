@@ -74,7 +74,8 @@ enum {
     E2EFT_OPT_GN_APPLY_ITERS = 13,   /* 0 (default): the GroupNorm apply pass picks its pixels per thread (4 x n sixteen-byte loads) by tensor size; 1 .. 16: forced n */
     E2EFT_OPT_F32_SPLIT = 14,        /* 1 (default, round 6): e2eft_conv2d_fwd_f32split_supported may answer 1 (fp32 3x3 convolutions from two-term f16 splits on the f16 matrix pipe); 0: it answers 0 (v_mfma_f32_32x32x2_f32 on igemm2) */
     E2EFT_OPT_F32_SPLIT_ATTN = 15,   /* 0 (default): fp32 fused attention (e2eft_attn_fwd / _lse / e2eft_attn_bwd) on v_mfma_f32_32x32x2_f32 (attn32.hip); 1: e2eft_attn_f32split_supported may answer 1 (every fp32 product from two-term f16 splits on v_mfma_f32_32x32x16_f16, attn_f32split.hip) */
-    E2EFT_OPT_COUNT = 16
+    E2EFT_OPT_PATCH_MFMA = 16,       /* the MFMA form of the halo-patch kernel (igemm6).  0 (default): the planner's table decides per class of launch (dtype, taps, channels, pixels; never by whether a GroupNorm is fused into the read); 1: always v_mfma_f32_32x32x16; 2: v_mfma_f32_16x16x32 wherever a variant is instantiated.  Summation order: both forms sum k in the same (chunk, tap, channel) order per output element, but inside a 64-channel k-tile the 32x32x16 form adds four 16-channel partial sums, the 16x16x32 form two 32-channel ones — results of the two forms differ in the last bits; the GroupNorm partials sum their rows in another (fixed) order.  Each form is deterministic run to run. */
+    E2EFT_OPT_COUNT = 17
 };
 int e2eft_set_option(int32_t key, int32_t value);
 int e2eft_get_option(int32_t key);
