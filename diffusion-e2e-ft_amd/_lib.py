@@ -83,6 +83,14 @@ class DsineRgbDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "out_layout")]
 
 
+class DiffusionDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "dtype_out", "prediction", "rows", "hw", "c", "batch", "ldx0", "ldn", "ldy", "n_timesteps")]
+
+
+DIFFUSION_ADD_NOISE, DIFFUSION_VELOCITY = range(2)      # e2eft_diffusion_mix kind
+PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1}    # e2eft_diffusion_desc.prediction (train_depth_normal.py:677-682: anything else is refused)
+
+
 RGB_HWC, RGB_CHW = range(2)                 # e2eft_dsine_rgb_desc.out_layout
 DSINE_RGB_WS_INTS = 6                       # E2EFT_DSINE_RGB_WS_INTS
 
@@ -214,6 +222,12 @@ SIGNATURES = {
     "e2eft_pyramid_noise_workspace_bytes": (_Z, [_I, _I, _I]),
     "e2eft_pyramid_noise": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _F, _I, C.POINTER(C.c_int32), _P, _P, _Z, _P]),
     "e2eft_latent_x0": (_I, [_I, _L, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
+    # diffusion objective of the GeoWizard trainer (csrc/diffusion.hip)
+    "e2eft_latent_valid_mask": (_I, [_I, _I, _I, _P, _P, _P]),
+    "e2eft_diffusion_mix": (_I, [C.POINTER(DiffusionDesc), _I, _P, _P, _P, _P, _P, _P]),
+    "e2eft_masked_mse_workspace_bytes": (_Z, [_I, _I, _I]),
+    "e2eft_masked_mse_fwd": (_I, [C.POINTER(DiffusionDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "e2eft_masked_mse_bwd": (_I, [C.POINTER(DiffusionDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 

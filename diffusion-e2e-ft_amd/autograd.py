@@ -976,3 +976,34 @@ class _AngularLossFn(torch.autograd.Function):
 def angular_loss(pred, target, mask):
     """AngularLoss (training/util/loss.py:51-67) with its gradient"""
     return _AngularLossFn.apply(pred, target, mask) if needs_grad(pred) else ops.angular_loss(pred, target, mask)
+
+
+class _MaskedMseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, x0, noise, t, abar, latent_mask, prediction_type, want_target):
+        p = _nhwc_view(pred)
+        loss, nsel, target = ops.masked_mse_fwd(p, x0, noise, t, abar, latent_mask, prediction_type, want_target=want_target)
+        ctx.save_for_backward(p, x0, noise, t, abar, latent_mask, nsel)
+        ctx.prediction_type = prediction_type
+        ctx.mark_non_differentiable(nsel)
+        if target is None:
+            return loss[0], nsel
+        ctx.mark_non_differentiable(target)
+        return loss[0], nsel, target
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        p, x0, noise, t, abar, latent_mask, nsel = ctx.saved_tensors
+        dp = ops.masked_mse_bwd(p, x0, noise, t, abar, latent_mask, ctx.prediction_type, nsel, g.reshape(1).float().contiguous())
+        return dp.permute(0, 3, 1, 2), None, None, None, None, None, None, None
+
+
+def masked_mse(pred, x0, noise, t, abar, latent_mask, prediction_type, want_target=False):
+    """The diffusion loss of GeoWizard/geowizard/training/train_depth_normal.py:677-682,713-717 with its gradient: the mean over the selected elements of
+    (pred - target)^2, target = noise (epsilon) or sqrt(abar_t) * noise - sqrt(1 - abar_t) * x0 (v_prediction) recomputed inside the kernels.
+    pred: logical NCHW [R,C,h,w] (the UNet's prediction); x0, noise: NHWC views [R,h,w,C]; t int64 [R], abar fp32 [T] on the device; latent_mask uint8 [B,h,w]
+    (ops.latent_valid_mask), row r uses image r % B.  -> (loss, n_selected int64 [1][, target fp32 NHWC]); no selected element: loss 0 and a zero gradient."""
+    if needs_grad(pred):
+        return _MaskedMseFn.apply(pred, x0, noise, t, abar, latent_mask, prediction_type, want_target)
+    loss, nsel, target = ops.masked_mse_fwd(_nhwc_view(pred), x0, noise, t, abar, latent_mask, prediction_type, want_target=want_target)
+    return (loss[0], nsel) if target is None else (loss[0], nsel, target)

@@ -983,6 +983,95 @@ def latent_x0(x_t, v, c_x, c_v, out=None):
     return out
 
 
+# ---- diffusion objective of the GeoWizard trainer (csrc/diffusion.hip; train_depth_normal.py:606-609, 671, 677-682, 713-717) ----------------------------
+def latent_valid_mask(val_mask, out=None):
+    """val_mask bool / uint8 [B,1,H,W] or [B,H,W] (nonzero = valid) -> uint8 [B,H/8,W/8]: 1 where all 64 pixels of the 8 x 8 cell are valid
+    (`~max_pool2d((~val_mask).float(), 8, 8).bool()`, :607-608)"""
+    _check_cuda(val_mask, out)
+    if val_mask.dim() == 4:
+        if val_mask.shape[1] != 1:
+            raise ValueError("latent_valid_mask: val_mask must be [B,1,H,W] or [B,H,W], got %s" % (tuple(val_mask.shape),))
+        val_mask = val_mask[:, 0]
+    if val_mask.dim() != 3:
+        raise ValueError("latent_valid_mask: val_mask must be [B,1,H,W] or [B,H,W], got %s" % (tuple(val_mask.shape),))
+    if val_mask.dtype == torch.bool:
+        vm = val_mask.contiguous().view(torch.uint8)
+    elif val_mask.dtype == torch.uint8:
+        vm = val_mask.contiguous()
+    else:
+        raise TypeError("latent_valid_mask: val_mask must be bool or uint8, got %s" % val_mask.dtype)
+    B, H, W = vm.shape
+    if out is None:
+        out = torch.empty((B, H // 8, W // 8), dtype=torch.uint8, device=vm.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (B, H // 8, W // 8), (out.dtype, out.shape)
+    check(_lib.load().e2eft_latent_valid_mask(B, H, W, _ptr(vm), _ptr(out), _stream()))
+    return out
+
+
+def _diffusion_args(x0, noise, t, abar, y, latent_mask=None, prediction_type=None):
+    """the descriptor of one call over NHWC views [R,h,w,c]: x0 and noise of one dtype, y (x_t / pred / dpred) of its own"""
+    R, h, w, c = x0.shape
+    assert noise.shape == x0.shape and y.shape == x0.shape and noise.dtype == x0.dtype, (x0.shape, noise.shape, y.shape, x0.dtype, noise.dtype)
+    assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == R, (t.dtype, t.shape, R)
+    assert abar.dtype == torch.float32 and abar.is_contiguous() and abar.dim() == 1
+    d = _lib.DiffusionDesc()
+    d.dtype, d.dtype_out = dtype_id(x0.dtype), dtype_id(y.dtype)
+    d.rows, d.hw, d.c, d.batch = R, h * w, c, 1
+    d.ldx0, d.ldn, d.ldy = _nhwc_ld(x0), _nhwc_ld(noise), _nhwc_ld(y)
+    d.n_timesteps = abar.numel()
+    if latent_mask is not None:
+        if prediction_type not in _lib.PREDICTION_TYPES:
+            raise ValueError("Unknown prediction type %s" % prediction_type)
+        assert latent_mask.dtype == torch.uint8 and latent_mask.is_contiguous() and tuple(latent_mask.shape[1:]) == (h, w), (latent_mask.dtype, latent_mask.shape)
+        d.batch = latent_mask.shape[0]
+        d.prediction = _lib.PREDICTION_TYPES[prediction_type]
+    return d
+
+
+def diffusion_mix_(x0, noise, t, abar, out, kind=_lib.DIFFUSION_ADD_NOISE):
+    """out[r, ..., :] = sqrt(abar[t_r]) * x0 + sqrt(1 - abar[t_r]) * noise (kind DIFFUSION_ADD_NOISE: `add_noise`, :671) or sqrt(abar[t_r]) * noise -
+    sqrt(1 - abar[t_r]) * x0 (DIFFUSION_VELOCITY: `get_velocity`, :680) for NHWC views [R,h,w,c]; t int64 [R] and abar fp32 [T] on the device.  `out` may be a
+    channel slice of a wider buffer (the noise channels of the UNet input) and of another dtype (rounded once).  One launch, nothing read back."""
+    _check_cuda(x0, noise, t, abar, out)
+    d = _diffusion_args(x0, noise, t, abar, out)
+    check(_lib.load().e2eft_diffusion_mix(C.byref(d), int(kind), _ptr(t), _ptr(abar), _ptr(x0), _ptr(noise), _ptr(out), _stream()))
+    return out
+
+
+def masked_mse_workspace(rows, hw, c, device):
+    nbytes = _lib.load().e2eft_masked_mse_workspace_bytes(rows, hw, c)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def masked_mse_fwd(pred, x0, noise, t, abar, latent_mask, prediction_type, want_target=False, ws=None):
+    """masked mean squared error of `pred` against the diffusion target (:677-682, :717) over NHWC views [R,h,w,c]; latent_mask uint8 [B,h,w], row r uses image
+    r % B.  -> (loss fp32 [1], n_selected int64 [1], target fp32 [R,h,w,c] or None).  Two launches, nothing read back."""
+    _check_cuda(pred, x0, noise, t, abar, latent_mask, ws)
+    d = _diffusion_args(x0, noise, t, abar, pred, latent_mask, prediction_type)
+    if ws is None:
+        ws = masked_mse_workspace(d.rows, d.hw, d.c, pred.device)
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    nsel = torch.empty(1, dtype=torch.int64, device=pred.device)
+    target = torch.empty(tuple(pred.shape), dtype=torch.float32, device=pred.device) if want_target else None
+    check(_lib.load().e2eft_masked_mse_fwd(C.byref(d), _ptr(t), _ptr(abar), _ptr(pred), _ptr(x0), _ptr(noise), _ptr(latent_mask), _ptr(loss), _ptr(nsel), _ptr(target),
+                                           _ptr(ws), ws.numel() * ws.element_size(), _stream()))
+    return loss, nsel, target
+
+
+def masked_mse_bwd(pred, x0, noise, t, abar, latent_mask, prediction_type, n_selected, grad_out, out=None):
+    """dpred = grad_out * 2 * (pred - target) / n_selected on the selected elements, 0 elsewhere — NHWC [R,h,w,c] in pred's dtype; n_selected (int64 [1], from
+    the forward) and grad_out (fp32 [1]) are read on the device.  One launch."""
+    _check_cuda(pred, x0, noise, t, abar, latent_mask, n_selected, grad_out, out)
+    d = _diffusion_args(x0, noise, t, abar, pred, latent_mask, prediction_type)
+    assert n_selected.dtype == torch.int64 and grad_out.dtype == torch.float32 and grad_out.numel() == 1
+    if out is None:
+        out = torch.empty(tuple(pred.shape), dtype=pred.dtype, device=pred.device)
+    assert out.shape == pred.shape and out.dtype == pred.dtype
+    check(_lib.load().e2eft_masked_mse_bwd(C.byref(d), _ptr(t), _ptr(abar), _ptr(pred), _ptr(x0), _ptr(noise), _ptr(latent_mask), _ptr(n_selected), _ptr(grad_out),
+                                           _ptr(out), _nhwc_ld(out), _stream()))
+    return out
+
+
 def add(a, b, out=None):
     _check_cuda(a, b, out)
     assert a.shape == b.shape and a.dtype == b.dtype

@@ -135,7 +135,43 @@ class DDPMScheduler(DDIMScheduler):
     .save_pretrained(out)` which writes scheduler/scheduler_config.json.  The E2E-FT step never calls the scheduler's stochastic `step()`: it only
     needs the noise schedule (identical to DDIM's: scaled_linear betas, diffusers scheduling_ddpm.py) and the config, so this is the same object
     under the reference's class name; `save_pretrained` records `_class_name: DDPMScheduler` as diffusers would.  SD-v2 ships `clip_sample: false`;
-    a checkpoint that sets it (DDPM's diffusers default is true) is refused by the fused single-step path exactly like DDIM's (zero_latent_x0_scale)."""
+    a checkpoint that sets it (DDPM's diffusers default is true) is refused by the fused single-step path exactly like DDIM's (zero_latent_x0_scale).
+
+    The diffusion objective of the GeoWizard trainer (GeoWizard/geowizard/training/train_depth_normal.py:671,680) also calls `add_noise` and `get_velocity`:
+    both take diffusers' argument order and run on device tensors through e2eft_diffusion_mix (one launch, per-row timesteps read on the device)."""
+
+    def alphas_cumprod_on(self, device):
+        """the fp32 alphas_cumprod table on `device`: uploaded once per (scheduler, device) and kept"""
+        cache = self.__dict__.setdefault("_abar_dev", {})
+        key = str(torch.device(device))
+        tab = cache.get(key)
+        if tab is None:
+            tab = cache[key] = self.alphas_cumprod.to(device=device, dtype=torch.float32).contiguous()
+        return tab
+
+    def _mix(self, x0, noise, timesteps, kind):
+        from . import ops
+        ops._check_cuda(x0, noise, timesteps)
+        if x0.dim() != 4 or x0.shape != noise.shape or x0.dtype != noise.dtype:
+            raise ValueError("expected two [R,C,h,w] tensors of one dtype, got %s %s and %s %s" % (tuple(x0.shape), x0.dtype, tuple(noise.shape), noise.dtype))
+        t = timesteps.to(torch.int64).reshape(-1).contiguous()
+        if t.numel() != x0.shape[0]:
+            raise ValueError("expected one timestep per row: %d timesteps for %d rows" % (t.numel(), x0.shape[0]))
+        from .autograd import _nhwc_view
+        R, Cc, h, w = x0.shape
+        out = torch.empty((R, h, w, Cc), dtype=x0.dtype, device=x0.device)
+        ops.diffusion_mix_(_nhwc_view(x0), _nhwc_view(noise), t, self.alphas_cumprod_on(x0.device), out, kind)
+        return out.permute(0, 3, 1, 2)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers `DDPMScheduler.add_noise`: sqrt(abar_t) * original_samples + sqrt(1 - abar_t) * noise per row (logical NCHW in, logical NCHW out)"""
+        from ._lib import DIFFUSION_ADD_NOISE
+        return self._mix(original_samples, noise, timesteps, DIFFUSION_ADD_NOISE)
+
+    def get_velocity(self, sample, noise, timesteps):
+        """diffusers `DDPMScheduler.get_velocity`: sqrt(abar_t) * noise - sqrt(1 - abar_t) * sample per row"""
+        from ._lib import DIFFUSION_VELOCITY
+        return self._mix(sample, noise, timesteps, DIFFUSION_VELOCITY)
 
     def step(self, *a, **kw):
         raise NotImplementedError("ancestral DDPM sampling is not on the E2E-FT path (training/train.py reads the schedule only; inference uses DDIMScheduler)")

@@ -153,31 +153,76 @@ def geowizard_class_embedding(batch, domain, dtype, device):
     return torch.cat([torch.sin(geo), torch.cos(geo), torch.sin(dom), torch.cos(dom)], dim=-1).to(dtype)
 
 
-def geowizard_e2e_ft_loss(unet, vae, batch, imgs_embed, domain="indoor", depth_scale=0.5, normal_scale=1.0, return_parts=False):
+GEOWIZARD_PYRAMID_MESSAGE = ("noise_type='pyramid' is not built for the GeoWizard trainer: its multi-resolution noise weights every level per sample by t / 1000 "
+                             "(GeoWizard/geowizard/training/train_depth_normal.py:286-296), which is a different function from e2eft_pyramid_noise "
+                             "(training/util/noise.py:8-18, no timestep weight)")
+
+
+def _geowizard_noise(noise_type, generator, noise, rows, C, h, w, dt, dev):
+    """the geometry noise [2b,4,h,w] of the GeoWizard trainer (train_depth_normal.py:656-663) as an NHWC tensor [2b,h,w,4]: an explicit `noise`, zeros, or
+    standard normals drawn on the device by a noise.DeviceNoise"""
+    if noise_type == "pyramid":
+        raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
+    if noise is not None:
+        if tuple(noise.shape) != (rows, C, h, w):
+            raise ValueError("noise must be [%d,%d,%d,%d], got %s" % (rows, C, h, w, tuple(noise.shape)))
+        return F._nhwc_view(noise.to(device=dev, dtype=dt))
+    if noise_type == "zeros":
+        return torch.zeros((rows, h, w, C), dtype=dt, device=dev)
+    if noise_type == "gaussian":
+        from . import noise as N
+        if not isinstance(generator, N.DeviceNoise):
+            raise TypeError("noise_type='gaussian' draws on the device: pass generator=noise.DeviceNoise(seed)")
+        return N.randn_into(torch.empty((rows, h, w, C), dtype=dt, device=dev), generator)
+    raise ValueError("Unknown noise type %s" % noise_type)
+
+
+def geowizard_e2e_ft_loss(unet, vae, batch, imgs_embed, domain="indoor", depth_scale=0.5, normal_scale=1.0, return_parts=False, noise_type="zeros", generator=None,
+                          noise=None):
     """Forward half of the GeoWizard E2E-FT micro-step (GeoWizard/geowizard/training/train_depth_normal.py:597-768, --e2e_ft, zeros
     noise): the UNet runs the doubled batch [depth rows; normal rows] with cross-domain joint self-attention and the class
     embedding, the frozen decoder decodes both halves, loss = 0.5 * SSI(depth) + 1.0 * angular(normals vs -GT).
-    imgs_embed: CLIP image embeddings [b,1,768] (an input here)."""
+    imgs_embed: CLIP image embeddings [b,1,768] (an input here).
+    noise_type (:656-668): "zeros" (default), "gaussian" (drawn on the device by `generator`, a noise.DeviceNoise) or an explicit `noise` [2b,4,h,w]: x_t = noise
+    (:668) goes into channels 4:8 of the UNet input and x0 comes from that x_t; "pyramid" is refused (the trainer's variant is weighted by t / 1000)."""
     core = getattr(unet, "module", unet)
     with ops.on_device_of(next(core.parameters())):
-        return _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts)
+        return _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts, noise_type, generator, noise)
 
 
-def _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts):
+def _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts, noise_type="zeros", generator=None, noise=None):
     dev = core.device
     dt = getattr(core, "compute_dtype", core.dtype)
+    if noise_type not in ("zeros", "gaussian", "pyramid"):
+        raise ValueError("Unknown noise type %s" % noise_type)
+    if noise_type == "pyramid":
+        raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
     with torch.no_grad():
         rgb_latents = encode_image(vae, batch["rgb"].to(device=dev, dtype=dt)) * vae.config.scaling_factor
     val_mask = batch["val_mask"].bool().to(dev)
     b = rgb_latents.shape[0]
     timesteps = torch.full((2 * b,), 999, device=dev, dtype=torch.long)
-    noisy = torch.zeros_like(rgb_latents).repeat(2, 1, 1, 1)
     ctx = imgs_embed.to(device=dev, dtype=dt).repeat(2, 1, 1)
     cls = geowizard_class_embedding(b, domain, dt, dev)
-    unet_input = torch.cat((rgb_latents.repeat(2, 1, 1, 1), noisy), dim=1).contiguous(memory_format=torch.channels_last)
-    noise_pred = unet(unet_input, timesteps, ctx, class_labels=cls, return_dict=False)[0]
     from .scheduler import DDIMScheduler
-    x0 = noise_pred * (DDIMScheduler().zero_latent_x0_scale(999) / vae.config.scaling_factor)
+    sf = vae.config.scaling_factor
+    if noise is None and noise_type == "zeros":
+        noisy = torch.zeros_like(rgb_latents).repeat(2, 1, 1, 1)
+        unet_input = torch.cat((rgb_latents.repeat(2, 1, 1, 1), noisy), dim=1).contiguous(memory_format=torch.channels_last)
+        noise_pred = unet(unet_input, timesteps, ctx, class_labels=cls, return_dict=False)[0]
+        x0 = noise_pred * (DDIMScheduler().zero_latent_x0_scale(999) / sf)
+    else:
+        # x_t = noise (:668) in channels 4:8 of the [2b,h,w,8] UNet input, x0 from that x_t by the scheduler's prediction type
+        _, C, h, w = rgb_latents.shape
+        xin = torch.empty((2 * b, h, w, 2 * C), dtype=dt, device=dev)
+        lat = F._nhwc_view(rgb_latents)
+        ops.copy_scale(lat, xin[:b, ..., :C])
+        ops.copy_scale(lat, xin[b:, ..., :C])
+        x_t = xin[..., C:]
+        ops.copy_scale(_geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev), x_t)
+        noise_pred = unet(xin.permute(0, 3, 1, 2), timesteps, ctx, class_labels=cls, return_dict=False)[0]
+        c_x, c_v = DDIMScheduler().x0_coefficients_for(999)
+        x0 = F.latent_x0(noise_pred, x_t, c_x / sf, c_v / sf)
     est = vae.decoder(vae.post_quant_conv(x0)).permute(0, 2, 3, 1)          # NHWC view [2b,H,W,3]
     depth = F.depth_head(est[:b], to_unit=False)
     normal = F.normal_head(est[b:], clamp=True)
@@ -185,6 +230,69 @@ def _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_sca
     ang = F.angular_loss(normal, batch["normals"].to(device=dev) * -1, val_mask)     # GeoWizard trains on inverted normals (:611,751)
     loss = ssi * depth_scale + ang * normal_scale
     return (loss, ssi, ang) if return_parts else loss
+
+
+def geowizard_diffusion_loss(unet, vae, batch, imgs_embed, domain="indoor", noise_scheduler=None, noise_type="gaussian", generator=None, noise=None,
+                             timesteps=None, prediction_type=None, return_parts=False):
+    """Forward half of the GeoWizard DIFFUSION-objective micro-step (GeoWizard/geowizard/training/train_depth_normal.py:598-717 WITHOUT --e2e_ft): one frozen VAE
+    encode of [rgb; depth; -normals] (:611,634-638), per-sample timesteps `randint(0, T, (b,)).repeat(2)` (:651), geometry noise (:656-663), `add_noise` written
+    straight into channels 4:8 of the UNet input (:671,704), the UNet over the doubled batch [depth rows; normal rows] with the class embedding (:684-709), and the
+    mean squared error against the target of the prediction type over the latent cells whose 8 x 8 pixels are all valid (:606-609,677-682,713-717).  The objective's
+    own arithmetic is five launches of csrc/diffusion.hip and synchronises nothing with the host.
+    batch: rgb [b,3,H,W], depth [b,3,H,W] (the normalised depth on three channels), normals [b,3,H,W], val_mask [b,1,H,W]; H and W multiples of 8.
+    noise_scheduler: a scheduler.DDPMScheduler (default: a fresh one); prediction_type overrides its config's (:674-676), "epsilon" or "v_prediction".
+    noise_type: "gaussian" (drawn on the device by `generator`, a noise.DeviceNoise), "zeros", or an explicit `noise` [2b,4,h,w]; "pyramid" is refused.
+    timesteps: int64 [b] instead of drawn ones (drawn on the device from torch's generator, no read-back).
+    No selected cell: the loss is 0 and its gradient is zero everywhere, as e2e_ft_loss does for an all-invalid batch (the reference skips the term, :714).
+    Returns the loss; return_parts: (loss, n_selected int64 [1], target fp32 [2b,4,h,w], x_t [2b,4,h,w])."""
+    core = getattr(unet, "module", unet)
+    with ops.on_device_of(next(core.parameters())):
+        return _geowizard_diffusion_loss(unet, core, vae, batch, imgs_embed, domain, noise_scheduler, noise_type, generator, noise, timesteps, prediction_type,
+                                         return_parts)
+
+
+def _geowizard_diffusion_loss(unet, core, vae, batch, imgs_embed, domain, noise_scheduler, noise_type, generator, noise, timesteps, prediction_type, return_parts):
+    dev = core.device
+    dt = getattr(core, "compute_dtype", core.dtype)
+    if noise_type not in ("zeros", "gaussian", "pyramid"):
+        raise ValueError("Unknown noise type %s" % noise_type)
+    if noise_type == "pyramid":
+        raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
+    if noise_scheduler is None:
+        from .scheduler import DDPMScheduler
+        noise_scheduler = DDPMScheduler()
+    pt = prediction_type if prediction_type is not None else noise_scheduler.config.prediction_type
+    if pt not in ("epsilon", "v_prediction"):
+        raise ValueError("Unknown prediction type %s" % pt)
+    rgb = batch["rgb"].to(device=dev, dtype=dt)
+    b = rgb.shape[0]
+    with torch.no_grad():
+        images = torch.cat((rgb, batch["depth"].to(device=dev, dtype=dt), batch["normals"].to(device=dev, dtype=dt) * -1), dim=0)
+        latents = F._nhwc_view(encode_image(vae, images) * vae.config.scaling_factor)       # [3b,h,w,4]: rgb | depth | normal rows
+    _, h, w, C = latents.shape
+    rgb_latents, geo_latents = latents[:b], latents[b:]                                     # geo rows [depth (b); normal (b)] (:639)
+    latent_mask = ops.latent_valid_mask(batch["val_mask"].to(dev))                          # [b,h,w]; row r reads image r % b (:609)
+    if tuple(latent_mask.shape[1:]) != (h, w):
+        raise ValueError("val_mask gives %s latent cells, the latents are %s" % (tuple(latent_mask.shape[1:]), (h, w)))
+    T = noise_scheduler.config.num_train_timesteps
+    if timesteps is None:
+        timesteps = torch.randint(0, T, (b,), device=dev)
+    elif timesteps.numel() != b:
+        raise ValueError("timesteps must hold one entry per image (%d), got %d" % (b, timesteps.numel()))
+    timesteps = timesteps.to(device=dev, dtype=torch.long).reshape(b).repeat(2)
+    nz = _geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev)
+    abar = noise_scheduler.alphas_cumprod_on(dev)
+    xin = torch.empty((2 * b, h, w, 2 * C), dtype=dt, device=dev)
+    ops.copy_scale(rgb_latents, xin[:b, ..., :C])
+    ops.copy_scale(rgb_latents, xin[b:, ..., :C])
+    x_t = ops.diffusion_mix_(geo_latents, nz, timesteps, abar, xin[..., C:])
+    ctx = imgs_embed.to(device=dev, dtype=dt).repeat(2, 1, 1)
+    cls = geowizard_class_embedding(b, domain, dt, dev)
+    noise_pred = unet(xin.permute(0, 3, 1, 2), timesteps, ctx, class_labels=cls, return_dict=False)[0]
+    out = F.masked_mse(noise_pred, geo_latents, nz, timesteps, abar, latent_mask, pt, want_target=return_parts)
+    if not return_parts:
+        return out[0]
+    return out[0], out[1], out[2].permute(0, 3, 1, 2), x_t.permute(0, 3, 1, 2)
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -759,6 +759,58 @@ int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, i
 int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,
                     const void* v, void* x0, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Diffusion-objective training step of the GeoWizard trainer (csrc/diffusion.hip): GeoWizard/geowizard/training/train_depth_normal.py:606-609
+ * (latent validity mask), :671 (`noise_scheduler.add_noise`), :677-682 (target by prediction type, `get_velocity` at :680) and :713-717 (the
+ * masked mean squared error, `F.mse_loss(noise_pred[latent_mask].float(), target[latent_mask].float())`) with its gradient.
+ *
+ * Latents are NHWC with one pixel stride per operand (the conventions of the latent-noise section): [rows, hw, (ld)], channels c..ld of a pixel are
+ * never touched.  Row r of `rows` has the timestep t[r] (int64 DEVICE array) and the coefficients
+ *     sa_r = sqrt(abar[t_r]),  sb_r = sqrt(1 - abar[t_r])
+ * from `abar`, the scheduler's fp32 alphas_cumprod table of n_timesteps entries on the DEVICE.  A VALID t (0 <= t < n_timesteps) IS THE CALLER'S
+ * CONTRACT: the kernels clamp t into the table so that they never read outside it, they do not report it.  All arithmetic is fp32 whatever the
+ * storage dtype; every product, sum, difference and square root of the mixing formulas is ONE correctly rounded IEEE operation (no fused
+ * multiply-add), so that fp32 results equal torch's eager `sa * x0 + sb * noise` / `sa * noise - sb * x0` bit for bit; 16-bit destinations are
+ * rounded once, at the store.  Sums are fp64 in a fixed order (wave butterfly, waves of a block left to right, the blocks' partials in index
+ * order), no floating-point atomics: the same input gives the same bits on every run, rank and graph replay.  Nothing is allocated and nothing
+ * is read back on the host: every call is capture-safe.  One launch per call, two for e2eft_masked_mse_fwd (partials, combine).
+ * ---------------------------------------------------------------------------------------------------- */
+#define E2EFT_DIFFUSION_ADD_NOISE 0 /* e2eft_diffusion_mix kind: y = sa * x0 + sb * noise      (add_noise,    :671) */
+#define E2EFT_DIFFUSION_VELOCITY 1  /*                           y = sa * noise - sb * x0      (get_velocity, :680) */
+#define E2EFT_PREDICTION_EPSILON 0  /* e2eft_diffusion_desc.prediction: target = noise                               (:677-678) */
+#define E2EFT_PREDICTION_V 1        /*                                  target = sa * noise - sb * x0                (:679-680); anything else is refused (:682) */
+typedef struct {
+    int32_t dtype;       /* of x0 and noise */
+    int32_t dtype_out;   /* of y (e2eft_diffusion_mix), of pred and dpred (e2eft_masked_mse_*) */
+    int32_t prediction;  /* E2EFT_PREDICTION_* (e2eft_masked_mse_* only) */
+    int32_t rows, hw, c; /* rows * hw * c < 2^31 */
+    int32_t batch;       /* images behind the latent mask: row r reads the mask of image r % batch (`latent_mask.repeat((2, 4, 1, 1))`, :609); e2eft_masked_mse_* only */
+    int32_t ldx0, ldn;   /* pixel strides of x0 and noise, >= c */
+    int32_t ldy;         /* pixel stride of y / pred / dpred, >= c */
+    int32_t n_timesteps; /* entries of abar, >= 1 */
+} e2eft_diffusion_desc;
+/* latent_mask[b, i, j] = 1 exactly when all 64 pixels of the 8 x 8 cell (i, j) of val_mask[b] (uint8 [batch, height, width], nonzero = valid) are
+ * valid, else 0 — `~torch.max_pool2d((~val_mask).float(), 8, 8).bool()` (:607-608).  latent_mask: uint8 [batch, height/8, width/8].  height and width
+ * must be multiples of 8 (the reference's mask and latent would not have one shape otherwise). */
+int e2eft_latent_valid_mask(int32_t batch, int32_t height, int32_t width, const uint8_t* val_mask, uint8_t* latent_mask, void* stream);
+/* y[r, p, 0:c] = the mix `kind` of x0 and noise with row r's coefficients, rounded once to dtype_out.  y is typically channels 4:8 of the
+ * [rows, h, w, 8] UNet input (ldy = 8): channels 0:4 stay untouched. */
+int e2eft_diffusion_mix(const e2eft_diffusion_desc* d, int32_t kind, const int64_t* t, const float* abar, const void* x0, const void* noise, void* y,
+                        void* stream);
+/* loss[0] = sum over the selected elements of (float(pred) - target)^2 / n_selected (fp32), n_selected[0] = their count (int64): element (r, p, ch) is
+ * selected when latent_mask[r % batch, p] != 0.  The target is recomputed from x0, noise and t (desc.prediction) and is stored only when out_target
+ * (fp32, dense [rows, hw, c]) is not NULL.  No selected element: loss = 0.0 exactly (the reference skips the term, `if latent_mask.any()`, :714).
+ * workspace: e2eft_masked_mse_workspace_bytes, 8-byte aligned, needs no clearing (every word read is written by the same call); its layout is
+ * private and the backward does not need it. */
+size_t e2eft_masked_mse_workspace_bytes(int32_t rows, int32_t hw, int32_t c);
+int e2eft_masked_mse_fwd(const e2eft_diffusion_desc* d, const int64_t* t, const float* abar, const void* pred, const void* x0, const void* noise,
+                         const uint8_t* latent_mask, float* loss, int64_t* n_selected, float* out_target, void* workspace, size_t ws_bytes,
+                         void* stream);
+/* dpred[r, p, 0:c] (dtype_out, pixel stride lddp) = grad_out[0] * 2 * (float(pred) - target) / n_selected[0] on the selected elements, exactly 0 on
+ * the others and everywhere when n_selected[0] == 0.  grad_out (fp32) and n_selected (int64, what the forward wrote) are read on the DEVICE. */
+int e2eft_masked_mse_bwd(const e2eft_diffusion_desc* d, const int64_t* t, const float* abar, const void* pred, const void* x0, const void* noise,
+                         const uint8_t* latent_mask, const int64_t* n_selected, const float* grad_out, void* dpred, int32_t lddp, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
