@@ -51,7 +51,8 @@ __global__ __launch_bounds__(256) void minmax_partial_kernel(long n, const float
     }
     block_minmax(mn, mx, part + blockIdx.x * 2);
 }
-__global__ __launch_bounds__(256) void minmax_final_kernel(int nparts, const float* __restrict__ part, float* __restrict__ mm /* [2] */) {
+// second stage, by one block: the partials in thread order, then block_minmax -> mm[0], mm[1] (global or LDS) by thread 0
+__device__ __forceinline__ void minmax_of_parts(int nparts, const float* __restrict__ part, float* mm) {
     float mn = INFINITY, mx = -INFINITY;
     for (int i = threadIdx.x; i < nparts; i += 256) {
         mn = fminf(mn, part[i * 2]);
@@ -59,10 +60,46 @@ __global__ __launch_bounds__(256) void minmax_final_kernel(int nparts, const flo
     }
     block_minmax(mn, mx, mm);
 }
+// the normalising arithmetic, stated once for the single-image and the batched kernel
+__device__ __forceinline__ float minmax_unit_value(float v, float mn, float d) { return d == 0.f ? 0.f : (v - mn) / d; }
+
+__global__ __launch_bounds__(256) void minmax_final_kernel(int nparts, const float* __restrict__ part, float* __restrict__ mm /* [2] */) {
+    minmax_of_parts(nparts, part, mm);
+}
 __global__ __launch_bounds__(256) void minmax_apply_kernel(long n, const float* __restrict__ x, const float* __restrict__ mm, float* __restrict__ out) {
     const float mn = mm[0], mx = mm[1];
     const float d = mx - mn;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = d == 0.f ? 0.f : (x[i] - mn) / d;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = minmax_unit_value(x[i], mn, d);
+}
+
+// The batched form: image b = blockIdx.y is x[b * n, (b + 1) * n).  Per image the first stage is minmax_partial_kernel's (the same blocks over the same
+// elements); the second stage is repeated by every block of the apply pass from the image's <= 256 partials (2 KB out of L2, in minmax_final_kernel's
+// order), which saves the one-block launch in between.  Loads and stores are scalar and coalesced: an image may start at any 4-byte address.
+__global__ __launch_bounds__(256) void minmax_partial_batched_kernel(long n, const float* __restrict__ x, float* __restrict__ part /* [B][256][2] */) {
+    const float* xb = x + (long)blockIdx.y * n;
+    float mn = INFINITY, mx = -INFINITY;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float v = xb[i];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    block_minmax(mn, mx, part + ((long)blockIdx.y * 256 + blockIdx.x) * 2);
+}
+__global__ __launch_bounds__(256) void minmax_apply_batched_kernel(long n, int nparts, const float* __restrict__ x, const float* __restrict__ part,
+                                                                   float* __restrict__ minmax /* [B][2] or null */, float* __restrict__ out) {
+    __shared__ float mm[2];
+    const long b = blockIdx.y;
+    minmax_of_parts(nparts, part + b * 512, mm);
+    __syncthreads();
+    const float mn = mm[0], mx = mm[1];
+    if (minmax && blockIdx.x == 0 && threadIdx.x == 0) {
+        minmax[b * 2] = mn;
+        minmax[b * 2 + 1] = mx;
+    }
+    const float d = mx - mn;
+    const float* xb = x + b * n;
+    float* ob = out + b * n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) ob[i] = minmax_unit_value(xb[i], mn, d);
 }
 
 static unsigned pp_gx(int w) { return (unsigned)((w + 255) / 256); }
@@ -98,4 +135,23 @@ extern "C" int e2eft_minmax_unit(int64_t n, const float* x, float* out, float* m
     if (nb > 16384) nb = 16384;
     hipLaunchKernelGGL(minmax_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, (long)n, x, (const float*)mm, out);
     return check_launch("minmax_unit");
+}
+
+extern "C" size_t e2eft_minmax_unit_batched_workspace_bytes(int32_t batch) { return batch > 0 ? (size_t)batch * 256 * 2 * sizeof(float) : 0; }
+
+extern "C" int e2eft_minmax_unit_batched(int32_t batch, int64_t n_per_image, const float* x, float* out, float* minmax, void* workspace, size_t ws_bytes,
+                                         void* stream) {
+    if (batch <= 0 || n_per_image <= 0) return E2EFT_OK;
+    E2EFT_REQUIRE(x && out && workspace, "minmax_unit_batched: null pointer");
+    E2EFT_REQUIRE(batch <= 65535, "minmax_unit_batched: batch %d > 65535", batch);
+    const size_t need = e2eft_minmax_unit_batched_workspace_bytes(batch);
+    if (ws_bytes < need) return fail(E2EFT_ERR_WORKSPACE, "minmax_unit_batched: workspace %zu < %zu", ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    long nb = ((long)n_per_image + 255) / 256;
+    const int nparts = (int)(nb > 256 ? 256 : nb);          // e2eft_minmax_unit's grids, per image
+    hipLaunchKernelGGL(minmax_partial_batched_kernel, dim3(nparts, batch), dim3(256), 0, s, (long)n_per_image, x, part);
+    if (nb > 16384) nb = 16384;
+    hipLaunchKernelGGL(minmax_apply_batched_kernel, dim3((unsigned)nb, batch), dim3(256), 0, s, (long)n_per_image, nparts, x, (const float*)part, minmax, out);
+    return check_launch("minmax_unit_batched");
 }

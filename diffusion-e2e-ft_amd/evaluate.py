@@ -6,6 +6,7 @@ for whole batches in one launch sequence (csrc/evalmetrics.hip), instead of nump
   depth_metrics              per-image metric table (dict name -> tensor [B]) and its mean, named as eval.py's metric functions
   MetricTracker              running averages keyed by metric name (the reference's pandas-backed tracker, metric.py:9-31)
   evaluate_depth_benchmark   the reference's infer.py + eval.py pair over one benchmark dataset (eval_data.py) without the .npy round trip
+  group_by_shape             the batches of both runners' predict_batch_size mode (pipe.predict_batch on device tensors): consecutive frames of one shape
 
 Surface normals (DSINE's benchmark mode, csrc/normaleval.hip), named as DSINE/utils/utils.py names them:
   normal_error               compute_normal_error (utils.py:150-158): per-pixel angular error in degrees, [B,1,H,W] fp32
@@ -104,12 +105,51 @@ def _metric_table(rows):
     return tabulate(rows)
 
 
-def evaluate_depth_benchmark(pipe, dataset, alignment="least_square", alignment_max_res=None, output_dir=None, save_predictions=False, **pipe_kwargs):
+def _batches(pairs, batch_size):
+    """(shape, payload) pairs in dataset order -> lists of payloads: consecutive pairs of one shape, at most batch_size per list; another shape starts a new list"""
+    group, shape = [], None
+    for s, payload in pairs:
+        if group and (s != shape or len(group) == batch_size):
+            yield group
+            group = []
+        shape = s
+        group.append(payload)
+    if group:
+        yield group
+
+
+def group_by_shape(shapes, batch_size):
+    """the batches of the runners' predict_batch_size mode as index lists: [shape of frame i] -> [[i, ...], ...] — consecutive frames of one shape, at most batch_size
+    per group, dataset order kept (a pure function: no tensors, no device)"""
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError("batch_size must be an integer >= 1, got %r" % (batch_size,))
+    return list(_batches(((tuple(s), i) for i, s in enumerate(shapes)), batch_size))
+
+
+def _batched_pipe(pipe, predict_batch_size, who):
+    """predict_batch_size of a runner: None stays None (the per-frame loop); anything else must be an integer >= 1 and the pipe must have predict_batch"""
+    if predict_batch_size is None:
+        return None
+    try:
+        group_by_shape((), predict_batch_size)
+    except ValueError:
+        raise ValueError("%s: predict_batch_size must be None or an integer >= 1, got %r" % (who, predict_batch_size)) from None
+    if not callable(getattr(pipe, "predict_batch", None)):
+        raise TypeError("%s: predict_batch_size=%d needs a pipeline with a predict_batch method; %s has none" % (who, predict_batch_size, type(pipe).__name__))
+    return predict_batch_size
+
+
+def evaluate_depth_benchmark(pipe, dataset, alignment="least_square", alignment_max_res=None, output_dir=None, save_predictions=False, predict_batch_size=None,
+                             **pipe_kwargs):
     """Marigold/infer.py:278-333 and Marigold/eval.py:146-249 in one loop over an eval_data dataset in EVAL mode: per sample, `pipe(PIL image,
     **pipe_kwargs).depth_np` is aligned to depth_raw_linear over valid_mask_raw, clipped to the dataset's range and measured (depth_metrics, on the
     device); the ten metrics are averaged over the samples (MetricTracker) and returned as a dict.  A sample without a valid pixel is named in a
     warning and left out of the average.  output_dir: per_sample_metrics.csv and eval_metrics[-<alignment>].txt as eval.py writes them;
-    save_predictions: also the .npy predictions where infer.py puts them (<output_dir>/<scene dir>/<get_pred_name(...)>)."""
+    save_predictions: also the .npy predictions where infer.py puts them (<output_dir>/<scene dir>/<get_pred_name(...)>).
+    predict_batch_size: None — the loop above; an integer >= 1 — consecutive frames of one shape go, up to predict_batch_size at a time, through
+    `pipe.predict_batch(uint8 [B,3,H,W] device tensor, **pipe_kwargs)` (its keywords, not `__call__`'s) and its fp32 [B,H,W] device tensor is measured as
+    it is, no PIL image and no numpy in between; rows, files and their text are those of the loop, in dataset order.  (A `batch_size` among the
+    keywords is, as before, the pipeline's own: the ensemble members per pass of `__call__`.)"""
     import os
     import warnings
 
@@ -130,30 +170,61 @@ def evaluate_depth_benchmark(pipe, dataset, alignment="least_square", alignment_
         per_sample = os.path.join(output_dir, "per_sample_metrics.csv")
         with open(per_sample, "w") as f:
             f.write("filename," + ",".join(METRIC_NAMES) + "\n")
-    for i in range(len(dataset)):
-        item = dataset[i]
-        rgb_name = item["rgb_relative_path"]
-        pred_name = os.path.join(os.path.dirname(rgb_name), get_pred_name(os.path.basename(rgb_name), dataset.name_mode, suffix=".npy"))
-        image = Image.fromarray(item["rgb_int"].permute(1, 2, 0).to(torch.uint8).cpu().numpy())
-        pred = np.asarray(pipe(image, **pipe_kwargs).depth_np)
-        if save_predictions:
-            os.makedirs(os.path.dirname(os.path.join(output_dir, pred_name)), exist_ok=True)
-            np.save(os.path.join(output_dir, pred_name), pred)
-        gt, mask = item["depth_raw_linear"][0], item["valid_mask_raw"][0]
-        if tuple(pred.shape) != tuple(gt.shape):
-            raise ValueError("%s: prediction %s and ground truth %s differ in shape" % (rgb_name, tuple(pred.shape), tuple(gt.shape)))
+    predict_batch_size = _batched_pipe(pipe, predict_batch_size, "evaluate_depth_benchmark")
+
+    def pred_name_of(rgb_name):
+        return os.path.join(os.path.dirname(rgb_name), get_pred_name(os.path.basename(rgb_name), dataset.name_mode, suffix=".npy"))
+
+    def save(pred_name, pred):
+        os.makedirs(os.path.dirname(os.path.join(output_dir, pred_name)), exist_ok=True)
+        np.save(os.path.join(output_dir, pred_name), pred)
+
+    def has_valid_pixels(item, pred_shape):
+        rgb_name, gt = item["rgb_relative_path"], item["depth_raw_linear"][0]
+        if tuple(pred_shape) != tuple(gt.shape):
+            raise ValueError("%s: prediction %s and ground truth %s differ in shape" % (rgb_name, tuple(pred_shape), tuple(gt.shape)))
         if int(item["n_valid_raw"]) == 0:
             warnings.warn("evaluate_depth_benchmark: %s has no valid ground-truth pixel; skipped" % rgb_name)
-            continue
+            return False
+        return True
+
+    def measure(items, pred):
+        """the frames of `items` (one shape) against pred [len(items),H,W] on the device -> one row of the ten metrics per frame, recorded in order"""
+        gt = torch.stack([item["depth_raw_linear"][0] for item in items])
+        mask = torch.stack([item["valid_mask_raw"][0] for item in items])
         with ops.on_device_of(gt):
-            m = depth_metrics(torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(gt.device), gt, mask, alignment=alignment,
-                              min_depth=dataset.min_depth, max_depth=dataset.max_depth, alignment_max_res=alignment_max_res)
-            values = torch.stack([m[k][0] for k in METRIC_NAMES]).cpu().tolist()
-        for k, v in zip(METRIC_NAMES, values):
-            tracker.update(k, v)
-        if per_sample is not None:
-            with open(per_sample, "a") as f:
-                f.write(pred_name + "," + ",".join(str(v) for v in values) + "\n")
+            m = depth_metrics(pred.to(gt.device), gt, mask, alignment=alignment, min_depth=dataset.min_depth, max_depth=dataset.max_depth,
+                              alignment_max_res=alignment_max_res)
+            table = torch.stack([m[k] for k in METRIC_NAMES], dim=1).cpu().tolist()
+        for item, values in zip(items, table):
+            for k, v in zip(METRIC_NAMES, values):
+                tracker.update(k, v)
+            if per_sample is not None:
+                with open(per_sample, "a") as f:
+                    f.write(pred_name_of(item["rgb_relative_path"]) + "," + ",".join(str(v) for v in values) + "\n")
+
+    items = (dataset[i] for i in range(len(dataset)))
+    if predict_batch_size is None:
+        for item in items:
+            image = Image.fromarray(item["rgb_int"].permute(1, 2, 0).to(torch.uint8).cpu().numpy())
+            pred = np.asarray(pipe(image, **pipe_kwargs).depth_np)
+            if save_predictions:
+                save(pred_name_of(item["rgb_relative_path"]), pred)
+            if has_valid_pixels(item, pred.shape):
+                measure([item], torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))[None])
+    else:
+        for group in _batches(((tuple(item["rgb_int"].shape), item) for item in items), predict_batch_size):
+            preds = pipe.predict_batch(torch.stack([item["rgb_int"] for item in group]).to(torch.uint8), **pipe_kwargs)
+            if not isinstance(preds, torch.Tensor) or preds.dim() != 3 or preds.shape[0] != len(group):
+                raise ValueError("%s: predict_batch must return a depth tensor [%d,H,W], got %s"
+                                 % (group[0]["rgb_relative_path"], len(group), tuple(preds.shape) if isinstance(preds, torch.Tensor) else type(preds).__name__))
+            preds = preds.float()
+            if save_predictions:
+                for item, pred in zip(group, preds.cpu().numpy()):
+                    save(pred_name_of(item["rgb_relative_path"]), pred)
+            valid = [j for j, item in enumerate(group) if has_valid_pixels(item, preds.shape[1:])]
+            if valid:                          # the group's frames in one call: depth_eval measures every image of a batch on its own
+                measure([group[j] for j in valid], preds if len(valid) == len(group) else preds[valid])
     result = tracker.result()
     if output_dir is not None:
         text = ("Evaluation metrics:\n    of predictions: %s\n    on dataset: %s\n    with samples in: %s\n"
@@ -312,13 +383,16 @@ def normal_metrics_text(m, iterations):
     return "Normal Estimation Metrics:\nMetrics at iteration %d\n%s\n" % (iterations, format_normal_metrics(m))
 
 
-def evaluate_normal_benchmark(pipe, dataset, output_dir=None, domain=None, **pipe_kwargs):
+def evaluate_normal_benchmark(pipe, dataset, output_dir=None, domain=None, predict_batch_size=None, **pipe_kwargs):
     """DSINE/projects/dsine/test.py:40-133 over one normal_eval_data.NormalBenchmarkDataset: per sample, `pipe(PIL image, **pipe_kwargs).normal_np` —
     the image is the RE-QUANTISED one of test.py:59-68 (the dataset's img_u8), so any callable with the reference's signature works — is measured
     against the ground truth over its valid pixels on the device (NormalMetricAccumulator: the errors of all images are pooled, then the metrics
     are taken, as the reference does).  normal_np may be [3,H,W] (Marigold) or [H,W,3] (GeoWizard).  A DepthNormalEstimationPipeline is also given
     `domain` (None: the dataset's, test.py:47-53).  Returns the metrics dict (evaluate.NORMAL_METRIC_NAMES and "n"), or None with a warning when no
-    pixel is valid anywhere.  output_dir: <output_dir>/test/<dataset_name>/metrics.txt as test.py:123-132 writes it."""
+    pixel is valid anywhere.  output_dir: <output_dir>/test/<dataset_name>/metrics.txt as test.py:123-132 writes it.
+    predict_batch_size: None — the loop above; an integer >= 1 — consecutive frames of one shape go, up to predict_batch_size at a time, through
+    `pipe.predict_batch(uint8 [B,3,H,W] device tensor of the re-quantised images, **pipe_kwargs)` (its keywords, not `__call__`'s; a MarigoldPipeline needs
+    normals=True among them) and the planar fp32 [B,3,H,W] device tensor it returns — the second of a (depth, normals) pair — is pooled as it is.  (A `batch_size` among the keywords is, as before, the pipeline's own.)"""
     import os
     import warnings
 
@@ -328,24 +402,41 @@ def evaluate_normal_benchmark(pipe, dataset, output_dir=None, domain=None, **pip
     from .pipeline import DepthNormalEstimationPipeline
     if isinstance(pipe, DepthNormalEstimationPipeline):
         pipe_kwargs = dict(pipe_kwargs, domain=domain if domain is not None else dataset.domain)
+    predict_batch_size = _batched_pipe(pipe, predict_batch_size, "evaluate_normal_benchmark")
     acc = NormalMetricAccumulator()
     iterations = 0
-    for i in range(len(dataset)):
-        item = dataset[i]
-        name = "%s/%s/%s" % (item["dataset_name"], item["scene_name"], item["img_name"])
-        gt, mask = item["normal"], item["normal_mask"]
-        image = Image.fromarray(item["img_u8"].permute(1, 2, 0).contiguous().cpu().numpy())
-        pred = np.asarray(pipe(image, **pipe_kwargs).normal_np)
-        H, W = gt.shape[-2:]
-        if pred.shape == (3, H, W):
-            p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))
-        elif pred.shape == (H, W, 3):
-            p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).permute(2, 0, 1)          # test.py:84: a view, read in place
-        else:
-            raise ValueError("%s: prediction %s matches neither [3,%d,%d] nor [%d,%d,3], the ground truth's shape" % (name, tuple(pred.shape), H, W, H, W))
+    items = (dataset[i] for i in range(len(dataset)))
+
+    def frame_by_frame():
+        for item in items:
+            name = "%s/%s/%s" % (item["dataset_name"], item["scene_name"], item["img_name"])
+            gt, mask = item["normal"], item["normal_mask"]
+            image = Image.fromarray(item["img_u8"].permute(1, 2, 0).contiguous().cpu().numpy())
+            pred = np.asarray(pipe(image, **pipe_kwargs).normal_np)
+            H, W = gt.shape[-2:]
+            if pred.shape == (3, H, W):
+                p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))
+            elif pred.shape == (H, W, 3):
+                p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).permute(2, 0, 1)          # test.py:84: a view, read in place
+            else:
+                raise ValueError("%s: prediction %s matches neither [3,%d,%d] nor [%d,%d,3], the ground truth's shape" % (name, tuple(pred.shape), H, W, H, W))
+            yield p, gt, mask, 1
+
+    def in_batches():
+        for group in _batches(((tuple(item["img_u8"].shape), item) for item in items), predict_batch_size):
+            preds = pipe.predict_batch(torch.stack([item["img_u8"] for item in group]), **pipe_kwargs)
+            preds = preds[1] if isinstance(preds, tuple) else preds
+            gt, mask = torch.stack([item["normal"] for item in group]), torch.stack([item["normal_mask"] for item in group])
+            if not isinstance(preds, torch.Tensor) or tuple(preds.shape) != tuple(gt.shape):
+                raise ValueError("%s/%s/%s: predict_batch returned %s, the ground truth of its %d frames is %s"
+                                 % (group[0]["dataset_name"], group[0]["scene_name"], group[0]["img_name"],
+                                    tuple(preds.shape) if isinstance(preds, torch.Tensor) else type(preds).__name__, len(group), tuple(gt.shape)))
+            yield preds, gt, mask, len(group)          # the errors of a batch are pooled image after image: the order of the loop
+
+    for p, gt, mask, frames in (frame_by_frame() if predict_batch_size is None else in_batches()):
         with ops.on_device_of(gt):
             acc.update(p.to(gt.device), gt, mask)
-        iterations += 1
+        iterations += frames
     result = acc.result() if iterations else None
     if result is None:
         warnings.warn("evaluate_normal_benchmark: no valid ground-truth pixel in %s (%d samples); no metrics" % (dataset.dataset_name, iterations))

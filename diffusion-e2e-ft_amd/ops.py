@@ -1617,6 +1617,21 @@ def minmax_unit(x):
     return out
 
 
+def minmax_unit_batched(x, return_minmax=False):
+    """minmax_unit per image of a contiguous fp32 [B, ...] batch in one launch sequence: out[b] holds the bits minmax_unit(x[b]) gives (zeros where an
+    image is constant); return_minmax: also the fp32 [B, 2] (min, max) table.  No host synchronisation."""
+    _check_cuda(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 1, "minmax_unit_batched: need a contiguous fp32 [B, ...] batch"
+    B = x.shape[0]
+    lib = _lib.load()
+    nbytes = lib.e2eft_minmax_unit_batched_workspace_bytes(B)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    mm = torch.empty((B, 2), dtype=torch.float32, device=x.device) if return_minmax else None
+    check(lib.e2eft_minmax_unit_batched(B, x.numel() // B if B else 0, _ptr(x), _ptr(out), _ptr(mm), _ptr(ws), nbytes, _stream()))
+    return (out, mm) if return_minmax else out
+
+
 # ---------------------------------------------------------------------------------------------------------
 # test-time ensembling (csrc/ensemble.hip): x is the fp32 [N, ...] stack of the N predictions of one image
 def _ens_stack(x):

@@ -359,6 +359,62 @@ class MarigoldPipeline:
         colored = _to_pil(np.moveaxis((((pred + 1) / 2) * 255).astype(np.uint8), 0, -1))                     # :338-341
         return MarigoldDepthOutput(depth_np=None, depth_colored=None, uncertainty=pred_uncert, normal_np=pred, normal_colored=colored)
 
+    @ops.device_scoped
+    @torch.no_grad()
+    def predict_batch(self, images, processing_res=768, match_input_res=True, resample_method="bilinear", normals=False, denoising_steps=1,
+                      noise="zeros", generator=None):
+        """`__call__` with ensemble_size = 1 for a whole batch, device tensors in and out (an addition to the reference's surface).
+        images: uint8 [B,3,H,W] (host or device; moved to the pipeline's device once) or a list of PIL images of ONE size.  Returns fp32 depth [B,H',W'] in
+        [0,1], or with normals=True fp32 normals [B,3,H',W'] in [-1,1]; H',W' is the input size when match_input_res, else the processing size (as single_infer
+        returns it: the VAE keeps whole 8-pixel latents).
+        The steps are `__call__`'s on the batch: resize_max_res when processing_res > 0, / 255 * 2 - 1, ONE single_infer on [B,...], then per image min-max to
+        [0,1] (ops.minmax_unit_batched) — normals: pred / (|pred| + 1e-5) over the channels —, resize back, clip.  Every resample_method ("bilinear", "bicubic",
+        "nearest") runs through resize_device(kind=...) on the device, before and after the model.  No host synchronisation with a device input and the
+        default one-step zero-noise setting: no host read of a tensor value (uint8 input cannot leave [-1,1], so `__call__`'s range assert has nothing to
+        check), no .cpu().  There is no ensemble_size: ensembling stays with `__call__`."""
+        if processing_res < 0:
+            raise ValueError("processing_res must be >= 0, got %s" % (processing_res,))
+        if resample_method not in ("bilinear", "bicubic", "nearest"):
+            raise ValueError("Unknown resampling method: %s" % resample_method)
+        rgb = _uint8_batch(images, self.device)
+        B, _, H0, W0 = rgb.shape
+        if processing_res > 0:
+            rgb = _resize_max_res_batch(rgb, processing_res, resample_method)
+        rgb_norm = (rgb / 255.0 * 2.0 - 1.0).to(self.dtype)
+        pred = self.single_infer(rgb_norm, denoising_steps, False, noise=noise, normals=normals, generator=generator).float()
+        h, w = pred.shape[-2:]
+        if normals:
+            pred = pred / (torch.norm(pred, p=2, dim=1, keepdim=True) + 1e-5)
+        else:
+            pred = ops.minmax_unit_batched(pred.reshape(B, h, w).contiguous())
+        if match_input_res and (h, w) != (H0, W0):
+            pred = resize_device(pred.reshape(-1, h, w), (H0, W0), kind=resample_method).reshape(pred.shape[:-2] + (H0, W0))
+        return pred.clamp(-1.0, 1.0).contiguous() if normals else pred.clamp(0.0, 1.0)
+
+
+def _uint8_batch(images, device):
+    """predict_batch's input -> uint8 [B,3,H,W] on `device`: a uint8 [B,3,H,W] tensor (one .to), or a list of PIL images of one size (stacked on the host, one copy)"""
+    if isinstance(images, torch.Tensor):
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] == 0:
+            raise ValueError("predict_batch: expected a uint8 [B,3,H,W] tensor, got %s %s" % (images.dtype, tuple(images.shape)))
+        return images.to(device).contiguous()
+    arrays = [np.asarray(im.convert("RGB")) for im in images]
+    if not arrays:
+        raise ValueError("predict_batch: no images")
+    sizes = [a.shape[:2] for a in arrays]
+    if len(set(sizes)) != 1:
+        raise ValueError("predict_batch: the images of a batch must have one size, got (H, W) = %s" % ", ".join(str(s) for s in sorted(set(sizes))))
+    return torch.from_numpy(np.ascontiguousarray(np.stack(arrays).transpose(0, 3, 1, 2))).to(device)
+
+
+def _resize_max_res_batch(rgb, max_edge_resolution, resample_method="bilinear"):
+    """resize_max_res for a uint8 [B,3,H,W] device batch: the B * 3 planes in one call of the table-driven resampler, rounded back to uint8 as
+    torchvision does for an integer image"""
+    B, C, H, W = rgb.shape
+    f = min(max_edge_resolution / W, max_edge_resolution / H)
+    nw, nh = int(W * f), int(H * f)
+    return resize_device(rgb.reshape(B * C, H, W), (nh, nw), round_u8=True, kind=resample_method).to(rgb.dtype).reshape(B, C, nh, nw)
+
 
 def _device_noise(noise, generator):
     """noise="gaussian" / "pyramid" with a noise.DeviceNoise generator: drawn on the device.  Any other generator (None, a torch.Generator) keeps torch's path."""
@@ -755,3 +811,30 @@ class DepthNormalEstimationPipeline:
         return DepthNormalPipelineOutput(depth_np=depth_pred.clamp(0, 1).cpu().numpy().astype(np.float32), depth_colored=None,
                                          normal_np=normal_pred.clamp(-1, 1).contiguous().cpu().numpy().astype(np.float32), normal_colored=None,
                                          uncertainty=uncert)
+
+    @ops.device_scoped
+    @torch.no_grad()
+    def predict_batch(self, images, processing_res=768, match_input_res=True, domain="indoor", denoising_steps=1, noise="zeros"):
+        """`__call__` with ensemble_size = 1 for a whole batch, device tensors in and out (an addition to the reference's surface).
+        images: uint8 [B,3,H,W] (host or device; moved to the pipeline's device once) or a list of PIL images of ONE size.  Returns (depth fp32 [B,H',W'] in
+        [0,1], normals fp32 [B,3,H',W'] in [-1,1]); H',W' is the input size when match_input_res, else the processing size.  The normals are PLANAR here,
+        as MarigoldPipeline.predict_batch returns them — `__call__` returns them HWC when match_input_res is set, as the reference does.
+        The steps are `__call__`'s on the batch: resize_max_res when processing_res > 0, / 255 * 2 - 1, ONE single_infer on [B,...] (2 * B UNet rows), per image
+        min-max of the depth (ops.minmax_unit_batched), bicubic resize back for the depth and nearest for the normals, clamps.  The CLIP embedding is
+        `self.img_embed` ([B,1,X]) when set, else the image encoder's for the batch.  No host synchronisation with a device input and the default one-step
+        zero-noise setting.  There is no ensemble_size: ensembling stays with `__call__`."""
+        if processing_res < 0 or denoising_steps < 1:
+            raise ValueError("processing_res must be >= 0 and denoising_steps >= 1, got %s, %s" % (processing_res, denoising_steps))
+        rgb = _uint8_batch(images, self.device)
+        B, _, H0, W0 = rgb.shape
+        if processing_res > 0:
+            rgb = _resize_max_res_batch(rgb, processing_res)
+        rgb_norm = (rgb.float() / 255.0 * 2.0 - 1.0).clamp(-1.0, 1.0).to(self.dtype)
+        d, n = self.single_infer(rgb_norm, domain=domain, num_inference_steps=denoising_steps, noise=noise)
+        h, w = d.shape[-2:]
+        depth = ops.minmax_unit_batched(d.float().reshape(B, h, w).contiguous())
+        normal = n.float()
+        if match_input_res and (h, w) != (H0, W0):
+            depth = resize_device(depth, (H0, W0), kind="bicubic")
+            normal = resize_device(normal.reshape(B * 3, h, w), (H0, W0), kind="nearest").reshape(B, 3, H0, W0)
+        return depth.clamp(0.0, 1.0), normal.clamp(-1.0, 1.0).contiguous()

@@ -505,12 +505,19 @@ int e2eft_align_normals_u8(int32_t batch, int32_t h, int32_t w, const uint8_t* n
  * bounds [out][2] = (first tap, tap count), weights [out][ksize]; mid: [planes][h0][w] fp32 scratch; round_u8: round half-to-even and clamp to
  * [0, 255] first (torchvision's treatment of an integer image); then y = v * mul + add.
  * e2eft_minmax_unit: out = (x - min x) / (max x - min x), zeros when max == min (marigold_pipeline.py:301-306); two-stage fixed-order reduction;
- * minmax (optional): the two values for the caller; workspace: e2eft_minmax_unit_workspace_bytes(). */
+ * minmax (optional): the two values for the caller; workspace: e2eft_minmax_unit_workspace_bytes().
+ * e2eft_minmax_unit_batched: the same per image of a batch in one launch sequence — image b is x[b * n_per_image, (b + 1) * n_per_image), and its output
+ * is, bit for bit, what e2eft_minmax_unit writes for that image alone (n_per_image need not be a multiple of anything: an image may start at any 4-byte
+ * address); minmax (optional): [batch][2]; workspace: e2eft_minmax_unit_batched_workspace_bytes(batch) (0 for batch <= 0), no clearing needed;
+ * batch <= 0 or n_per_image <= 0: nothing to do, success; batch <= 65535. */
 int e2eft_resample_bilinear_aa(int32_t planes, int32_t h0, int32_t w0, int32_t h, int32_t w, int32_t in_is_u8, const void* in,
                                const int32_t* xbounds, const float* xweights, int32_t xksize, const int32_t* ybounds, const float* yweights,
                                int32_t yksize, int32_t round_u8, float mul, float add, float* mid, float* out, void* stream);
 size_t e2eft_minmax_unit_workspace_bytes(void);
 int e2eft_minmax_unit(int64_t n, const float* x, float* out, float* minmax, void* workspace, size_t ws_bytes, void* stream);
+size_t e2eft_minmax_unit_batched_workspace_bytes(int32_t batch);
+int e2eft_minmax_unit_batched(int32_t batch, int64_t n_per_image, const float* x, float* out, float* minmax, void* workspace, size_t ws_bytes,
+                              void* stream);
 int e2eft_aug_resample_bilinear_u8(int32_t batch, int32_t h0, int32_t w0, int32_t h, int32_t w, const uint8_t* in, const uint8_t* flip,
                                    int32_t invert_x_on_flip, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                                    const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, uint8_t* mid, float* out, void* stream);

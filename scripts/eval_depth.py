@@ -5,7 +5,8 @@ Defaults follow the reference's protocol for the E2E-FT models: native resolutio
 
 usage: python scripts/eval_depth.py --checkpoint <diffusers-format dir> --dataset data_nyu_test --base_data_dir data/eval
                                     --filenames data_split/nyu/labeled/filename_list_test.txt --output_dir output/nyu_test
-       (--dataset_config <yaml> instead of --dataset for a configuration file in the reference's format)"""
+       (--dataset_config <yaml> instead of --dataset for a configuration file in the reference's format)
+       --batch_size N: up to N consecutive frames of one shape per pipe.predict_batch call, device tensors from the dataset to the metrics; the same files"""
 import argparse
 import os
 import sys
@@ -34,9 +35,15 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--half_precision", "--fp16", action="store_true")
     ap.add_argument("--save_predictions", action="store_true", help="also write the .npy predictions under --output_dir")
+    ap.add_argument("--batch_size", type=int, default=None, help="predict up to N consecutive frames of one shape per call (pipe.predict_batch, device tensors "
+                                                                 "end to end); default: one pipe.__call__ per frame")
     args = ap.parse_args(argv)
     if args.dataset and not args.filenames:
         ap.error("--dataset needs --filenames (the benchmark's filename list)")
+    if args.batch_size is not None and args.batch_size < 1:
+        ap.error("--batch_size needs an integer >= 1")
+    if args.batch_size is not None and args.ensemble_size != 1:
+        ap.error("--batch_size predicts without ensembling: leave --ensemble_size at 1")
     return args
 
 
@@ -60,10 +67,11 @@ def main(argv=None):
     dtype = torch.float16 if args.half_precision else torch.float32
     pipe = MarigoldPipeline.from_pretrained(args.checkpoint, variant="fp16" if args.half_precision else None, torch_dtype=dtype).to("cuda", dtype)
     pipe.unet.eval()
+    kw = dict(denoising_steps=args.denoise_steps, processing_res=args.processing_res, match_input_res=True, resample_method="bilinear", noise=args.noise)
+    if args.batch_size is None:      # __call__'s further keywords (batch_size here is its own: the ensemble members per pass)
+        kw.update(ensemble_size=args.ensemble_size, batch_size=0, color_map=None, show_progress_bar=False)
     result = evaluate.evaluate_depth_benchmark(pipe, dataset, alignment=args.alignment, alignment_max_res=args.alignment_max_res, output_dir=args.output_dir,
-                                               save_predictions=args.save_predictions, denoising_steps=args.denoise_steps, ensemble_size=args.ensemble_size,
-                                               processing_res=args.processing_res, match_input_res=True, batch_size=0, color_map=None, show_progress_bar=False,
-                                               resample_method="bilinear", noise=args.noise)
+                                               save_predictions=args.save_predictions, predict_batch_size=args.batch_size, **kw)
     print("%s (%d samples, alignment %s)" % (dataset.disp_name, len(dataset), args.alignment))
     for k, v in result.items():
         print("  %-28s %.6f" % (k, v))

@@ -9,7 +9,8 @@ ensemble_size, noise, domain.  Other keys are ignored, with a note.  ckpt_path i
 usage: python scripts/eval_normals.py experiments/normals/eval_args/marigold_e2e_ft.txt --base_data_dir data --split_dir DSINE/data/datasets
                                       --output_dir output/normals [--ckpt_path <dir>]
        --base_data_dir   the folder that holds dsine_eval/
-       --split_dir       a folder laid out as <dataset>/split/<split>.txt (DSINE/data/datasets of a reference checkout)"""
+       --split_dir       a folder laid out as <dataset>/split/<split>.txt (DSINE/data/datasets of a reference checkout)
+       --batch_size N    up to N consecutive frames of one shape per pipe.predict_batch call (needs ensemble_size 1); the same metrics.txt"""
 import argparse
 import os
 import sys
@@ -65,7 +66,12 @@ def parse(argv=None):
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--ckpt_path", default=None, help="overrides the args file's ckpt_path (a local diffusers-format directory)")
     ap.add_argument("--half_precision", "--fp16", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--batch_size", type=int, default=None, help="predict up to N consecutive frames of one shape per call (pipe.predict_batch, device tensors "
+                                                                 "end to end); default: one pipe.__call__ per frame")
+    args = ap.parse_args(argv)
+    if args.batch_size is not None and args.batch_size < 1:
+        ap.error("--batch_size needs an integer >= 1")
+    return args
 
 
 def load_pipeline(cfg, dtype, device="cuda"):
@@ -94,6 +100,16 @@ def pipe_kwargs_of(cfg):
         kw.update(color_map="Spectral")
     else:
         kw.update(color_map=None, resample_method="bilinear", batch_size=0, normals=True)
+    return kw
+
+
+def batch_kwargs_of(cfg):
+    """the same settings as predict_batch takes them (--batch_size): no ensembling, no colouring, no progress bar"""
+    if cfg["ensemble_size"] != 1:
+        raise ValueError("--batch_size predicts without ensembling: the args file sets ensemble_size %d" % cfg["ensemble_size"])
+    kw = dict(denoising_steps=cfg["denoise_steps"], processing_res=cfg["processing_res"], match_input_res=True, noise=cfg["noise"])
+    if cfg["model_type"] != "geowizard":
+        kw.update(resample_method="bilinear", normals=True)
     return kw
 
 
@@ -129,7 +145,8 @@ def main(argv=None, pipe=None):
     for name in benchmarks_of(cfg["eval_data"]):
         split = os.path.join(args.split_dir, name, "split", normal_eval_data.NORMAL_BENCHMARKS[name]["split"] + ".txt")
         dataset = normal_eval_data.NormalBenchmarkDataset(name, os.path.join(args.base_data_dir, "dsine_eval", name), split)
-        res = evaluate.evaluate_normal_benchmark(pipe, dataset, output_dir=args.output_dir, domain=cfg["domain"], **pipe_kwargs_of(cfg))
+        kw = pipe_kwargs_of(cfg) if args.batch_size is None else batch_kwargs_of(cfg)
+        res = evaluate.evaluate_normal_benchmark(pipe, dataset, output_dir=args.output_dir, domain=cfg["domain"], predict_batch_size=args.batch_size, **kw)
         results[name] = res
         print("%s (%d samples)" % (name, len(dataset)))
         print(evaluate.format_normal_metrics(res) if res is not None else "No normal errors to compute metrics.")
