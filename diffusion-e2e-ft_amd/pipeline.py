@@ -33,16 +33,16 @@ class DepthNormalPipelineOutput:          # geowizard_pipeline.py:37-57
     uncertainty: Optional[np.ndarray]
 
 
-class MarigoldPipeline:
+class _LatentPipeline:
+    """What both pipelines own: the unet / vae / scheduler slots, `dtype` / `device`, the VAE round trip with the latent scale factors, the one-step
+    schedule, the DDIM update and the hipGraph cache."""
     rgb_latent_scale_factor = 0.18215    # marigold_pipeline.py:134
     depth_latent_scale_factor = 0.18215  # marigold_pipeline.py:135
 
     _graphs = None
 
-    def __init__(self, unet, vae, scheduler, text_encoder=None, tokenizer=None):
+    def __init__(self, unet, vae, scheduler):
         self.unet, self.vae, self.scheduler = unet, vae, scheduler
-        self.text_encoder, self.tokenizer = text_encoder, tokenizer
-        self.empty_text_embed = None
 
     # ---- DiffusionPipeline-like surface (Marigold/run.py:274-290) ----
     @property
@@ -52,6 +52,73 @@ class MarigoldPipeline:
     @property
     def device(self):
         return self.unet.device
+
+    # ---- marigold_pipeline.py:481-498 ----
+    @ops.device_scoped
+    @torch.no_grad()
+    def encode_rgb(self, rgb_in):
+        h = self.vae.encoder(rgb_in)
+        moments = self.vae.quant_conv(h)
+        mean = moments[:, : moments.shape[1] // 2]  # torch.chunk(moments, 2, dim=1)[0]
+        return _scaled(mean, self.rgb_latent_scale_factor)
+
+    def _decode(self, latent):
+        z = self.vae.post_quant_conv(_scaled(latent, 1.0 / self.depth_latent_scale_factor))
+        return self.vae.decoder(z)
+
+    def _one_step_schedule(self):
+        """(t_dev [1], sb) of the one-step setting: x0 = -sb * model_output (by prediction_type); sb comes from the host copy of the timestep, no device read-back"""
+        self.scheduler.set_timesteps(1, device=self.device)
+        return self.scheduler.timesteps[:1], -self.scheduler.zero_latent_x0_scale(self.scheduler.timesteps_host[0])
+
+    def _ddim_step(self, v, t_host, latent, last):
+        """one scheduler step from the host copy of the timestep (no device synchronisation per step); the last step hands back the predicted x0
+        (marigold_pipeline.py:466-468, geowizard_pipeline.py:332-336)"""
+        step = self.scheduler.step(v, t_host, latent)
+        return step.pred_original_sample if last else step.prev_sample
+
+    def enable_hip_graphs(self, enabled=True):
+        """Replay the one-step zero-latent `single_infer` from a hipGraph captured per key (Marigold: input shape, dtype, modality, context; GeoWizard: batch
+        shape, dtype, domain, embedding source): ~1.4k launches per batch become one graph launch, which removes the host-side gaps on the small UNet levels
+        (at 2 GeoWizard images per step the CLIP tower is launch-bound as well).  Weights are baked in by address: call this again after changing them
+        (load_state_dict, .to(), an optimizer step)."""
+        self._graphs = {} if enabled else None
+        return self
+
+    def _replay(self, key, static, keep, fn):
+        """`fn(*static)` replayed from the graph cached under key + the weight state.  static: the tensors copied into the graph's own input buffers before
+        every replay (a None passes through); keep: tensors the graph reads in place — the entry keeps them alive, an address in `key` or baked into the graph
+        must not be handed to another tensor while the entry lives; fn: only device work on the current stream, returns a tensor or a tuple of tensors."""
+        from . import autograd as F
+        w0 = self.unet.conv_in.weight
+        weights = (F.PARAM_EPOCH, w0.data_ptr(), w0._version)
+        key = key + (weights,)
+        ent = self._graphs.get(key)
+        if ent is None:
+            # a new weight state makes every graph captured for an older one unreachable — drop them (validation during training would otherwise grow the
+            # cache by one graph + its static buffers per step)
+            for k in [k for k in self._graphs if k[-1] != weights]:
+                del self._graphs[k]
+            fn(*static)                      # eager pass: fills the packed-weight caches (and the folded cross-attention of a kept context)
+            torch.cuda.synchronize()
+            s_in = tuple(None if t is None else t.clone() for t in static)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                s_out = fn(*s_in)
+            ent = self._graphs[key] = (g, s_in, s_out, (w0, keep))
+        g, s_in, s_out, _ = ent
+        for s, t in zip(s_in, static):
+            if s is not None:
+                s.copy_(t)
+        g.replay()
+        return s_out.clone() if isinstance(s_out, torch.Tensor) else tuple(o.clone() for o in s_out)
+
+
+class MarigoldPipeline(_LatentPipeline):
+    def __init__(self, unet, vae, scheduler, text_encoder=None, tokenizer=None):
+        super().__init__(unet, vae, scheduler)
+        self.text_encoder, self.tokenizer = text_encoder, tokenizer
+        self.empty_text_embed = None
 
     def to(self, *args, **kwargs):
         self.unet.to(*args, **kwargs)
@@ -113,19 +180,6 @@ class MarigoldPipeline:
             ids = empty_prompt_ids("do_not_pad").to(self.device)
         self.empty_text_embed = self.text_encoder(ids)[0].to(self.dtype)
 
-    # ---- marigold_pipeline.py:481-498 ----
-    @ops.device_scoped
-    @torch.no_grad()
-    def encode_rgb(self, rgb_in):
-        h = self.vae.encoder(rgb_in)
-        moments = self.vae.quant_conv(h)
-        mean = moments[:, : moments.shape[1] // 2]  # torch.chunk(moments, 2, dim=1)[0]
-        return _scaled(mean, self.rgb_latent_scale_factor)
-
-    def _decode(self, latent):
-        z = self.vae.post_quant_conv(_scaled(latent, 1.0 / self.depth_latent_scale_factor))
-        return self.vae.decoder(z)
-
     # ---- marigold_pipeline.py:501-519 ----
     @ops.device_scoped
     @torch.no_grad()
@@ -146,81 +200,61 @@ class MarigoldPipeline:
     def single_infer(self, rgb_in, num_inference_steps, show_pbar=False, noise="gaussian", normals=False, generator=None):
         device, dt = self.device, self.dtype
         rgb_in = rgb_in.to(device=device, dtype=dt)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        timesteps = self.scheduler.timesteps
         if isinstance(noise, str) and noise == "zeros" and num_inference_steps == 1:
             # E2E-FT path (x_t = 0, one step): no host synchronisation anywhere, optionally replayed from a captured hipGraph
-            if self.empty_text_embed is None:
-                self.encode_empty_text()
-            ctx = self._empty_ctx(device, dt)
-            sb = -self.scheduler.zero_latent_x0_scale(self.scheduler.timesteps_host[0])   # x0 = -sb * model_output (by prediction_type)
-            if self._graphs is not None:
-                return self._replay(rgb_in, timesteps[:1], sb, ctx, normals)
-            return self._e2e_ft_zero_latent(rgb_in, timesteps[:1], sb, ctx, normals)
+            t_dev, sb, ctx = self._one_step()
+            if self._graphs is None:
+                return self._e2e_ft_zero_latent(rgb_in, t_dev, sb, ctx, normals)
+            # the context is part of the key by IDENTITY (address + version; the entry keeps the tensor alive): the graph reads it in place and bakes what the
+            # cross-attention layers derived from it (modules.Attention._fold) — a changed embedding is another graph, not a copy into a static buffer
+            key = (tuple(rgb_in.shape), rgb_in.dtype, bool(normals), tuple(ctx.shape), float(sb), ctx.data_ptr(), ctx._version)
+            return self._replay(key, (rgb_in, t_dev), ctx, lambda r, t: self._e2e_ft_zero_latent(r, t, sb, ctx, normals))
+        self.scheduler.set_timesteps(num_inference_steps, device=device)
         rgb_latent = self.encode_rgb(rgb_in)  # [B,4,h,w] logical NCHW
-        B, C, h, w = rgb_latent.shape
-        # UNet input buffer [B,h,w,8] NHWC: channels 0:4 rgb latent, 4:8 current latent ("this order is important" :447-449)
-        xin = torch.zeros((B, h, w, 2 * C), dtype=dt, device=device)
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[..., :C])
-        on_device = None
-        if isinstance(noise, torch.Tensor):      # an explicit initial latent [B,4,h,w]
-            latent = noise.to(device=device, dtype=dt)
-        elif _device_noise(noise, generator):    # drawn by the device generator straight into channels 4:8 of the input buffer (noise.py): no host tensor, no copy
-            from . import noise as N
-            N.noise_into(noise, xin[..., C:], generator)
-            latent, on_device = to_nchw_view(xin[..., C:]), True
-        elif noise == "gaussian":
-            latent = torch.randn((B, C, h, w), device=device, dtype=dt, generator=generator)
-        elif noise == "pyramid":
-            latent = pyramid_noise_like(rgb_latent).to(device)
-        elif noise == "zeros":
-            latent = None  # xin[..., C:] is already zero
-        else:
-            raise ValueError("Unknown noise type: %s" % noise)
-        if latent is not None and not on_device:
+        B, C = rgb_latent.shape[:2]
+        xin = _unet_input(rgb_latent)
+        # a DeviceNoise generator draws straight into channels 4:8 of the input buffer (noise.py): no host tensor, no copy; "zeros": they are zero already
+        latent = _initial_latent(noise, generator, rgb_latent, "Unknown noise type: %s", dst=xin[..., C:])
+        if latent is not None and not _device_noise(noise, generator):
             ops.copy_scale(latent.permute(0, 2, 3, 1).contiguous(), xin[..., C:])
         if self.empty_text_embed is None:
             self.encode_empty_text()
         ctx = self.empty_text_embed.to(device=device, dtype=dt).repeat(B, 1, 1)
-        x0 = None
-        for i, (t, t_host) in enumerate(zip(timesteps, self.scheduler.timesteps_host)):
+        for i, (t, t_host) in enumerate(zip(self.scheduler.timesteps, self.scheduler.timesteps_host)):
             v = self.unet(to_nchw_view(xin), t, encoder_hidden_states=ctx).sample
-            cur = latent if latent is not None else torch.zeros((B, C, h, w), dtype=dt, device=device)
-            step = self.scheduler.step(v, t_host, cur)     # host copy of the timestep: no device synchronisation per step
-            latent = step.prev_sample
-            x0 = step.pred_original_sample
-            if i == num_inference_steps - 1:
-                latent = x0
+            cur = latent if latent is not None else torch.zeros(tuple(rgb_latent.shape), dtype=dt, device=device)
+            latent = self._ddim_step(v, t_host, cur, i == num_inference_steps - 1)
             ops.copy_scale(latent.permute(0, 2, 3, 1).contiguous(), xin[..., C:])
+        return self._decode_head(latent, normals)
+
+    def _one_step(self):
+        """(t_dev, sb, ctx) of the E2E-FT path: the one-step schedule and the empty-prompt context (encoded on first use)"""
+        t_dev, sb = self._one_step_schedule()
+        if self.empty_text_embed is None:
+            self.encode_empty_text()
+        return t_dev, sb, self._empty_ctx(self.device, self.dtype)
+
+    def _decode_head(self, x0, normals):
         if normals:
-            dec = self.decode_normal(x0)
-            return ops.normal_head(dec.permute(0, 2, 3, 1), clamp=False)
-        stacked = self._decode(x0)
-        return ops.depth_head(stacked.permute(0, 2, 3, 1), to_unit=True)  # clip(mean_c, -1, 1) -> (x+1)/2  (:518,476-477)
+            return ops.normal_head(self._decode(x0).permute(0, 2, 3, 1), clamp=False)
+        return ops.depth_head(self._decode(x0).permute(0, 2, 3, 1), to_unit=True)   # clip(mean_c, -1, 1) -> (x+1)/2  (:518,476-477)
+
+    def _zero_latent_x0(self, rgb_in, t_dev, sb, ctx1, marks=None):
+        """encode -> UNet on [rgb latent | zeros] at t -> x0 = -sqrt(1 - abar_t) * v (marigold_pipeline.py:457-465, train.py:509-512).  Only device work on the
+        current stream: safe inside a hipGraph capture.  marks: optional list that receives three recorded events (start, after encode, after UNet)."""
+        _mark(marks)
+        xin = _unet_input(self.encode_rgb(rgb_in))
+        _mark(marks)
+        v = self.unet(to_nchw_view(xin), t_dev, encoder_hidden_states=ctx1.expand(xin.shape[0], -1, -1)).sample
+        x0 = _scaled(v, -sb)
+        _mark(marks)
+        return x0
 
     def _e2e_ft_zero_latent(self, rgb_in, t_dev, sb, ctx1, normals, marks=None):
-        """encode -> UNet on [rgb latent | zeros] at t -> x0 = -sqrt(1 - abar_t) * v (marigold_pipeline.py:457-465, train.py:509-512)
-        -> decode -> head.  Only device work on the current stream: safe inside a hipGraph capture.
-        marks: optional list that receives four recorded events (start, after encode, after UNet, end) for stage timing."""
-        def mark():
-            if marks is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                marks.append(e)
-        mark()
-        rgb_latent = self.encode_rgb(rgb_in)
-        B, C, h, w = rgb_latent.shape
-        xin = torch.zeros((B, h, w, 2 * C), dtype=rgb_in.dtype, device=rgb_in.device)   # channels 0:4 rgb latent, 4:8 the zero latent (:447-449)
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[..., :C])
-        mark()
-        v = self.unet(to_nchw_view(xin), t_dev, encoder_hidden_states=ctx1.expand(B, -1, -1)).sample
-        x0 = _scaled(v, -sb)
-        mark()
-        if normals:
-            out = ops.normal_head(self.decode_normal(x0).permute(0, 2, 3, 1), clamp=False)
-        else:
-            out = ops.depth_head(self._decode(x0).permute(0, 2, 3, 1), to_unit=True)   # clip(mean_c, -1, 1) -> (x+1)/2  (:518,476-477)
-        mark()
+        """_zero_latent_x0 -> decode -> head, capturable like it.  marks: optional list that receives four recorded events (start, after encode, after UNet,
+        end) for stage timing."""
+        out = self._decode_head(self._zero_latent_x0(rgb_in, t_dev, sb, ctx1, marks), normals)
+        _mark(marks)
         return out
 
     @ops.device_scoped
@@ -228,44 +262,23 @@ class MarigoldPipeline:
     def predict_latent(self, rgb_in):
         """the predicted x0 LATENT of the one-step zero-latent path ([B,4,h/8,w/8], logical NCHW): encode -> UNet at the scheduler's first timestep -> x0, i.e.
         `single_infer` without the decoder — the quantity BASELINE.json states parity on ("within 1e-3 relative fp32 on the depth/normal latent")"""
-        device, dt = self.device, self.dtype
-        rgb_in = rgb_in.to(device=device, dtype=dt)
-        self.scheduler.set_timesteps(1, device=device)
-        if self.empty_text_embed is None:
-            self.encode_empty_text()
-        sb = -self.scheduler.zero_latent_x0_scale(self.scheduler.timesteps_host[0])
-        rgb_latent = self.encode_rgb(rgb_in)
-        B, C, h, w = rgb_latent.shape
-        xin = torch.zeros((B, h, w, 2 * C), dtype=dt, device=device)
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[..., :C])
-        v = self.unet(to_nchw_view(xin), self.scheduler.timesteps[:1], encoder_hidden_states=self._empty_ctx(device, dt).expand(B, -1, -1)).sample
-        return _scaled(v, -sb)
+        return self._zero_latent_x0(rgb_in.to(device=self.device, dtype=self.dtype), *self._one_step())
 
     @ops.device_scoped
     @torch.no_grad()
     def stage_times_ms(self, rgb_in, normals=False, repeats=3):
         """{"vae_encode", "unet", "vae_decode"}: mean milliseconds per batch of the three stages of the E2E-FT path (HIP events on the
         launch stream; SURVEY.md §8(d) asks for the UNet-only rate next to the full path)."""
-        device, dt = self.device, self.dtype
-        rgb_in = rgb_in.to(device=device, dtype=dt)
-        self.scheduler.set_timesteps(1, device=device)
-        sb = -self.scheduler.zero_latent_x0_scale(self.scheduler.timesteps_host[0])   # x0 = -sb * model_output (by prediction_type)
-        ctx = self._empty_ctx(device, dt)
+        rgb_in = rgb_in.to(device=self.device, dtype=self.dtype)
+        t_dev, sb, ctx = self._one_step()
         tot = [0.0, 0.0, 0.0]
         for _ in range(repeats):
             marks = []
-            self._e2e_ft_zero_latent(rgb_in, self.scheduler.timesteps[:1], sb, ctx, normals, marks=marks)
+            self._e2e_ft_zero_latent(rgb_in, t_dev, sb, ctx, normals, marks=marks)
             torch.cuda.synchronize()
             for i in range(3):
                 tot[i] += marks[i].elapsed_time(marks[i + 1])
         return dict(zip(("vae_encode", "unet", "vae_decode"), (v / repeats for v in tot)))
-
-    def enable_hip_graphs(self, enabled=True):
-        """Replay the E2E-FT path from a hipGraph captured per (input shape, dtype, modality): ~1.4k launches per batch become one
-        graph launch, which removes the host-side gaps on the small UNet levels.  Weights are baked in by address: call this again
-        after changing them (load_state_dict, .to(), an optimizer step)."""
-        self._graphs = {} if enabled else None
-        return self
 
     def _empty_ctx(self, device, dt):
         """the empty-prompt embedding on `device` in `dt` as ONE stable tensor per (source tensor state, device, dtype): the UNet's cross-attention layers key their
@@ -279,27 +292,8 @@ class MarigoldPipeline:
             hit = self.__dict__["_ctx_dev"] = (key, src.to(device=device, dtype=dt), src)      # (src kept alive: its address is part of the key)
         return hit[1]
 
-    def _replay(self, rgb_in, t_dev, sb, ctx1, normals):
-        from . import autograd as F
-        w0 = self.unet.conv_in.weight
-        # the context is part of the key by IDENTITY (address + version; the entry keeps the tensor alive): the graph reads it in place and bakes what the
-        # cross-attention layers derived from it (modules.Attention._fold) — a changed embedding is another graph, not a copy into a static buffer
-        key = (tuple(rgb_in.shape), rgb_in.dtype, bool(normals), tuple(ctx1.shape), float(sb), ctx1.data_ptr(), ctx1._version, F.PARAM_EPOCH, w0.data_ptr(), w0._version)
-        ent = self._graphs.get(key)
-        if ent is None:
-            _evict_stale_graphs(self._graphs, key, n_weight_fields=3)
-            self._e2e_ft_zero_latent(rgb_in, t_dev, sb, ctx1, normals)       # eager pass: fills the packed-weight caches (and the folded cross-attention of ctx1)
-            torch.cuda.synchronize()
-            s_in, s_t = rgb_in.clone(), t_dev.clone()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                s_out = self._e2e_ft_zero_latent(s_in, s_t, sb, ctx1, normals)
-            ent = self._graphs[key] = (g, s_in, ctx1, s_t, s_out)
-        g, s_in, _, s_t, s_out = ent
-        s_in.copy_(rgb_in)
-        s_t.copy_(t_dev)
-        g.replay()
-        return s_out.clone()
+    def _unit_range(self, rgb):
+        return (rgb / 255.0 * 2.0 - 1.0).to(self.dtype)
 
     # ---- marigold_pipeline.py:158-353 ----
     @ops.device_scoped
@@ -310,18 +304,14 @@ class MarigoldPipeline:
         """generator: a `torch.Generator` (host / torch RNG, as before) or a `noise.DeviceNoise` — then noise="gaussian" / "pyramid" is drawn on the device,
         once per ensemble batch, directly in the UNet's input buffer"""
         assert processing_res >= 0 and ensemble_size >= 1
-        if isinstance(input_image, torch.Tensor):
-            rgb = input_image.squeeze()
-        else:  # PIL image
-            rgb = torch.from_numpy(np.asarray(input_image.convert("RGB"))).permute(2, 0, 1)
+        rgb = _image_chw(input_image)
         input_size = rgb.shape
-        assert rgb.dim() == 3 and input_size[0] == 3, "Wrong input shape %s, expected [rgb, H, W]" % (tuple(input_size),)
         on_dev = resample_method == "bilinear" and self.device.type == "cuda"      # pre / post-processing on the device (csrc/prepost.hip)
         if on_dev:
             rgb = rgb.to(self.device)
         if processing_res > 0:
             rgb = resize_max_res(rgb, processing_res, resample_method)
-        rgb_norm = (rgb / 255.0 * 2.0 - 1.0).to(self.dtype)
+        rgb_norm = self._unit_range(rgb)
         assert rgb_norm.min() >= -1.0 and rgb_norm.max() <= 1.0
         dup = torch.stack([rgb_norm] * ensemble_size)
         bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size, max(rgb_norm.shape[1:]), self.dtype)   # :254-261
@@ -334,22 +324,20 @@ class MarigoldPipeline:
             pred, pred_uncert = ensemble_normals(preds) if normals else ensemble_depths(preds, **(ensemble_kwargs or {}))
         else:
             pred, pred_uncert = preds, None
-        if normals:
-            pred = pred / (torch.norm(pred, p=2, dim=0, keepdim=True) + 1e-5)
-        elif on_dev and pred.is_cuda:
-            pred = ops.minmax_unit(pred.contiguous())
+        size = tuple(input_size[-2:]) if match_input_res else None
+        if on_dev:        # predict_batch's tails on the one image; the clip is numpy's below, on the host as in the torch branch: no launch for it
+            pred = (_post_normals(pred[None], size, "bilinear", renorm=True, clamp=False) if normals else _post_depth(pred, size, "bilinear", clamp=False))[0]
         else:
-            mn, mx = torch.min(pred), torch.max(pred)
-            pred = torch.zeros_like(pred) if mx == mn else (pred - mn) / (mx - mn)
-        if match_input_res and tuple(pred.shape[-2:]) != tuple(input_size[-2:]) and on_dev and pred.is_cuda:
-            pred = resize_device(pred if normals else pred[None], tuple(input_size[-2:]))
-            pred = pred if normals else pred[0]
-        elif match_input_res and tuple(pred.shape[-2:]) != tuple(input_size[-2:]):
-            p4 = pred[None] if normals else pred[None, None]
-            p4 = torch.nn.functional.interpolate(p4, size=tuple(input_size[-2:]), mode=resample_method,
-                                                 antialias=resample_method != "nearest",
-                                                 **({} if resample_method == "nearest" else {"align_corners": False}))
-            pred = p4[0] if normals else p4[0, 0]
+            if normals:
+                pred = pred / (torch.norm(pred, p=2, dim=0, keepdim=True) + 1e-5)
+            else:
+                mn, mx = torch.min(pred), torch.max(pred)
+                pred = torch.zeros_like(pred) if mx == mn else (pred - mn) / (mx - mn)
+            if size is not None and tuple(pred.shape[-2:]) != size:
+                p4 = pred[None] if normals else pred[None, None]
+                p4 = torch.nn.functional.interpolate(p4, size=size, mode=resample_method, antialias=resample_method != "nearest",
+                                                     **({} if resample_method == "nearest" else {"align_corners": False}))
+                pred = p4[0] if normals else p4[0, 0]
         pred = pred.cpu().numpy()
         if not normals:
             pred = pred.clip(0, 1)
@@ -377,19 +365,80 @@ class MarigoldPipeline:
         if resample_method not in ("bilinear", "bicubic", "nearest"):
             raise ValueError("Unknown resampling method: %s" % resample_method)
         rgb = _uint8_batch(images, self.device)
-        B, _, H0, W0 = rgb.shape
+        size = tuple(rgb.shape[-2:]) if match_input_res else None
         if processing_res > 0:
             rgb = _resize_max_res_batch(rgb, processing_res, resample_method)
-        rgb_norm = (rgb / 255.0 * 2.0 - 1.0).to(self.dtype)
-        pred = self.single_infer(rgb_norm, denoising_steps, False, noise=noise, normals=normals, generator=generator).float()
-        h, w = pred.shape[-2:]
-        if normals:
-            pred = pred / (torch.norm(pred, p=2, dim=1, keepdim=True) + 1e-5)
-        else:
-            pred = ops.minmax_unit_batched(pred.reshape(B, h, w).contiguous())
-        if match_input_res and (h, w) != (H0, W0):
-            pred = resize_device(pred.reshape(-1, h, w), (H0, W0), kind=resample_method).reshape(pred.shape[:-2] + (H0, W0))
-        return pred.clamp(-1.0, 1.0).contiguous() if normals else pred.clamp(0.0, 1.0)
+        pred = self.single_infer(self._unit_range(rgb), denoising_steps, False, noise=noise, normals=normals, generator=generator)
+        return _post_normals(pred, size, resample_method, renorm=True) if normals else _post_depth(pred, size, resample_method)
+
+
+def _image_chw(input_image):
+    """`__call__`'s input_image, a tensor ([3,H,W] once squeezed) or a PIL image -> [3,H,W] in 0..255 (uint8 from PIL)"""
+    if isinstance(input_image, torch.Tensor):
+        rgb = input_image.squeeze()
+    else:  # PIL image
+        rgb = torch.from_numpy(np.asarray(input_image.convert("RGB"))).permute(2, 0, 1)
+    assert rgb.dim() == 3 and rgb.shape[0] == 3, "Wrong input shape %s, expected [rgb, H, W]" % (tuple(rgb.shape),)
+    return rgb
+
+
+def _post_depth(depth, size, kind, clamp=True):
+    """predictions [.., h, w] of B images -> fp32 [B,H,W]: per image min-max to [0,1] (ops.minmax_unit_batched: zeros where an image is constant), resize back
+    to `size` (None: keep) through resize_device(kind=...), clamp (left out for a caller that clips on the host).  No host synchronisation."""
+    h, w = depth.shape[-2:]
+    depth = ops.minmax_unit_batched(depth.float().reshape(-1, h, w).contiguous())
+    if size is not None and (h, w) != tuple(size):
+        depth = resize_device(depth, size, kind=kind)
+    return depth.clamp(0.0, 1.0) if clamp else depth
+
+
+def _post_normals(normal, size, kind, renorm, clamp=True):
+    """normals [B,3,h,w] -> fp32 [B,3,H,W]: renorm: pred / (|pred| + 1e-5) over the channels; resize back to `size` (None: keep) through
+    resize_device(kind=...), clamp (left out for a caller that clips on the host).  No host synchronisation."""
+    normal = normal.float()
+    if renorm:
+        normal = normal / (torch.norm(normal, p=2, dim=1, keepdim=True) + 1e-5)
+    h, w = normal.shape[-2:]
+    if size is not None and (h, w) != tuple(size):
+        normal = resize_device(normal.reshape(-1, h, w), size, kind=kind).reshape(normal.shape[:-2] + tuple(size))
+    return normal.clamp(-1.0, 1.0).contiguous() if clamp else normal
+
+
+def _mark(marks):
+    if marks is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append(e)
+
+
+def _unet_input(rgb_latent, copies=1):
+    """UNet input buffer [copies * B,h,w,2C] NHWC from the rgb latent [B,C,h,w]: channels 0:C the rgb latent in each of the `copies` row blocks (GeoWizard: a
+    depth block and a normal block), C:2C the current latent, zero here ("this order is important", marigold_pipeline.py:447-449)"""
+    B, C, h, w = rgb_latent.shape
+    xin = torch.zeros((copies * B, h, w, 2 * C), dtype=rgb_latent.dtype, device=rgb_latent.device)
+    for r in range(copies):
+        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[r * B:(r + 1) * B, ..., :C])
+    return xin
+
+
+def _initial_latent(noise, generator, rgb_latent, unknown, dst=None):
+    """the initial latent [B,C,h,w] that `noise` names, None for "zeros".  A DeviceNoise generator (noise.py) draws into `dst`, an NHWC [B,h,w,C] view (a
+    fresh buffer when None), and the result is its NCHW view; every other draw is torch's.  unknown: the caller's error text for any other `noise`."""
+    if isinstance(noise, torch.Tensor):          # an explicit initial latent [B,4,h,w] (tests, reproducibility across devices)
+        return noise.to(device=rgb_latent.device, dtype=rgb_latent.dtype)
+    B, C, h, w = rgb_latent.shape
+    if _device_noise(noise, generator):
+        from . import noise as N
+        if dst is None:
+            dst = torch.empty((B, h, w, C), dtype=rgb_latent.dtype, device=rgb_latent.device)
+        return to_nchw_view(N.noise_into(noise, dst, generator))
+    if noise == "gaussian":
+        return torch.randn((B, C, h, w), device=rgb_latent.device, dtype=rgb_latent.dtype, generator=generator)
+    if noise == "pyramid":
+        return pyramid_noise_like(rgb_latent)
+    if noise == "zeros":
+        return None
+    raise ValueError(unknown % noise)
 
 
 def _uint8_batch(images, device):
@@ -420,14 +469,6 @@ def _device_noise(noise, generator):
     """noise="gaussian" / "pyramid" with a noise.DeviceNoise generator: drawn on the device.  Any other generator (None, a torch.Generator) keeps torch's path."""
     from .noise import DeviceNoise
     return isinstance(noise, str) and noise in ("gaussian", "pyramid") and isinstance(generator, DeviceNoise)
-
-
-def _evict_stale_graphs(graphs, new_key, n_weight_fields):
-    """graph keys end in (PARAM_EPOCH, conv_in data_ptr, conv_in version): a new weight state makes every graph captured for an older one
-    unreachable — drop them (validation during training would otherwise grow the cache by one graph + its static buffers per step)"""
-    tail = new_key[-n_weight_fields:]
-    for k in [k for k in graphs if k[-n_weight_fields:] != tail]:
-        del graphs[k]
 
 
 def find_batch_size(ensemble_size, input_res, dtype):
@@ -588,17 +629,16 @@ def pyramid_noise_like(x, discount=0.9):
     return total / total.std()
 
 
-class DepthNormalEstimationPipeline:
+class DepthNormalEstimationPipeline(_LatentPipeline):
     """GeoWizard joint depth + normal single-step inference, batched (rows [depth x B ; normal x B]) as in
     GeoWizard/geowizard/training/train_depth_normal.py:687-704; per-image semantics of geowizard_pipeline.py:252-344.
     `image_encoder` (clip.CLIPVisionModelWithProjection, geowizard_pipeline.py:76-86) is optional: without it pass `img_embed`
     [B,1,X] to single_infer directly."""
 
     def __init__(self, unet, vae, scheduler, image_encoder=None, feature_extractor=None):
-        self.unet, self.vae, self.scheduler = unet, vae, scheduler
+        super().__init__(unet, vae, scheduler)
         self.image_encoder, self.feature_extractor = image_encoder, feature_extractor
         self.img_embed = None                      # geowizard_pipeline.py:86
-        self._m = MarigoldPipeline(unet, vae, scheduler)
 
     def _clip_constants(self):
         """(size, mean [3,1,1], std [3,1,1]) of the CLIP preprocessor, resident on the device (no host->device copy per image)"""
@@ -625,14 +665,6 @@ class DepthNormalEstimationPipeline:
         x = preprocess_for_clip(rgb.to(device=self.device, dtype=self.dtype), size, mean, std)
         return self.image_encoder(x).image_embeds.unsqueeze(1).to(self.dtype)
 
-    @property
-    def dtype(self):
-        return self.unet.dtype
-
-    @property
-    def device(self):
-        return self.unet.device
-
     @staticmethod
     def class_embedding(batch, domain, dtype, device):
         geo = torch.tensor([[0.0, 1.0], [1.0, 0.0]], dtype=torch.float32).repeat_interleave(batch, 0)
@@ -641,69 +673,46 @@ class DepthNormalEstimationPipeline:
         emb = torch.cat([torch.sin(geo), torch.cos(geo), torch.sin(dom), torch.cos(dom)], dim=-1)  # 10 constants, host
         return emb.to(device=device, dtype=dtype)
 
-    _graphs = None
+    def _unit_range(self, rgb):
+        return (rgb.float() / 255.0 * 2.0 - 1.0).clamp(-1.0, 1.0).to(self.dtype)
 
-    def enable_hip_graphs(self, enabled=True):
-        """Replay single_infer from one captured hipGraph per (batch shape, dtype, domain, embedding source) — see
-        MarigoldPipeline.enable_hip_graphs; at 2 images per step the CLIP tower and the small UNet levels are launch-bound."""
-        self._graphs = {} if enabled else None
-        return self
+    def _decode_heads(self, geo, B):
+        """joint latent [depth x B ; normal x B] -> (depth [B,1,H,W] in [0,1], unit normals [B,3,H,W], sign flipped: geowizard_pipeline.py:341-342)"""
+        depth = ops.depth_head(self._decode(geo[:B]).permute(0, 2, 3, 1), to_unit=True)
+        normal = ops.normal_head(self._decode(geo[B:]).permute(0, 2, 3, 1), clamp=False, sign=-1.0)
+        return depth, normal
 
     def _device_path(self, rgb, img_embed, t_dev, sb, cls):
         """everything after the host-side setup; only device work on the current stream (capturable)"""
         if img_embed is None:
             img_embed = self.encode_img_embed(rgb)
         B = rgb.shape[0]
-        dt = rgb.dtype
-        rgb_latent = self._m.encode_rgb(rgb)
-        _, C, h, w = rgb_latent.shape
-        xin = torch.zeros((2 * B, h, w, 2 * C), dtype=dt, device=rgb.device)  # geo latent half stays zero
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[:B, ..., :C])
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[B:, ..., :C])
-        ctx = img_embed.to(dt).repeat(2, 1, 1)
+        xin = _unet_input(self.encode_rgb(rgb), copies=2)      # geo latent half stays zero
+        ctx = img_embed.to(rgb.dtype).repeat(2, 1, 1)
         v = self.unet(to_nchw_view(xin), t_dev.repeat(2 * B), encoder_hidden_states=ctx, class_labels=cls).sample
-        x0 = _scaled(v, -sb)
-        depth = ops.depth_head(self._m._decode(x0[:B]).permute(0, 2, 3, 1), to_unit=True)
-        normal = ops.normal_head(self._m._decode(x0[B:]).permute(0, 2, 3, 1), clamp=False, sign=-1.0)  # :341-342
-        return depth, normal
+        return self._decode_heads(_scaled(v, -sb), B)
 
     @torch.no_grad()
     def _multi_step(self, rgb, img_embed, cls, num_inference_steps, noise, generator):
         """geowizard_pipeline.py:266-343 for the pre-E2E-FT checkpoints: DDIM over the joint geometry latent (the SAME initial noise for
         the depth and the normal row of an image, :271), host launches only."""
-        device, dt = rgb.device, rgb.dtype
         B = rgb.shape[0]
         if img_embed is None:
             img_embed = self.encode_img_embed(rgb)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        rgb_latent = self._m.encode_rgb(rgb)
-        _, C, h, w = rgb_latent.shape
-        if isinstance(noise, torch.Tensor):          # an explicit initial latent [B,4,h,w] (tests, reproducibility across devices)
-            geo = noise.to(device=device, dtype=dt)
-        elif _device_noise(noise, generator):        # drawn on the device (noise.py); the depth and the normal row share it as below
-            from . import noise as N
-            geo = to_nchw_view(N.noise_into(noise, torch.empty((B, h, w, C), dtype=dt, device=device), generator))
-        elif noise == "gaussian":
-            geo = torch.randn((B, C, h, w), device=device, dtype=dt, generator=generator)
-        elif noise == "pyramid":
-            geo = pyramid_noise_like(rgb_latent).to(device=device, dtype=dt)
-        elif noise == "zeros":
-            geo = torch.zeros((B, C, h, w), device=device, dtype=dt)
-        else:
-            raise ValueError("Invalid noise type: %s" % noise)
+        self.scheduler.set_timesteps(num_inference_steps, device=rgb.device)
+        rgb_latent = self.encode_rgb(rgb)
+        C = rgb_latent.shape[1]
+        geo = _initial_latent(noise, generator, rgb_latent, "Invalid noise type: %s")
+        if geo is None:
+            geo = torch.zeros(tuple(rgb_latent.shape), device=rgb.device, dtype=rgb.dtype)
         geo = geo.repeat(2, 1, 1, 1)
-        xin = torch.zeros((2 * B, h, w, 2 * C), dtype=dt, device=device)
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[:B, ..., :C])
-        ops.copy_scale(rgb_latent.permute(0, 2, 3, 1), xin[B:, ..., :C])
-        ctx = img_embed.to(dt).repeat(2, 1, 1)
+        xin = _unet_input(rgb_latent, copies=2)
+        ctx = img_embed.to(rgb.dtype).repeat(2, 1, 1)
         for i, (t, t_host) in enumerate(zip(self.scheduler.timesteps, self.scheduler.timesteps_host)):
             ops.copy_scale(geo.permute(0, 2, 3, 1).contiguous(), xin[..., C:])
             v = self.unet(to_nchw_view(xin), t.repeat(2 * B), encoder_hidden_states=ctx, class_labels=cls).sample
-            step = self.scheduler.step(v, t_host, geo)
-            geo = step.pred_original_sample if i == num_inference_steps - 1 else step.prev_sample   # :332-336
-        depth = ops.depth_head(self._m._decode(geo[:B]).permute(0, 2, 3, 1), to_unit=True)
-        normal = ops.normal_head(self._m._decode(geo[B:]).permute(0, 2, 3, 1), clamp=False, sign=-1.0)
-        return depth, normal
+            geo = self._ddim_step(v, t_host, geo, i == num_inference_steps - 1)
+        return self._decode_heads(geo, B)
 
     @ops.device_scoped
     @torch.no_grad()
@@ -721,9 +730,7 @@ class DepthNormalEstimationPipeline:
         if num_inference_steps != 1 or isinstance(noise, torch.Tensor) or noise != "zeros":
             cls = self.class_embedding(B, domain, dt, device)
             return self._multi_step(rgb, None if img_embed is None else img_embed.to(device=device, dtype=dt), cls, num_inference_steps, noise, generator)
-        self.scheduler.set_timesteps(1, device=device)
-        t_dev = self.scheduler.timesteps[:1]
-        sb = -self.scheduler.zero_latent_x0_scale(self.scheduler.timesteps_host[0])   # x0 = -sb * model_output (by prediction_type); host copy, no device read-back
+        t_dev, sb = self._one_step_schedule()
         ck = (B, domain, dt, str(device))
         if getattr(self, "_cls_key", None) != ck:
             self._cls, self._cls_key = self.class_embedding(B, domain, dt, device), ck
@@ -732,26 +739,9 @@ class DepthNormalEstimationPipeline:
             img_embed = img_embed.to(device=device, dtype=dt)
         if self._graphs is None:
             return self._device_path(rgb, img_embed, t_dev, sb, cls)
-        from . import autograd as F
-        w0 = self.unet.conv_in.weight
-        key = (tuple(rgb.shape), dt, domain, None if img_embed is None else tuple(img_embed.shape), float(sb), F.PARAM_EPOCH, w0.data_ptr(), w0._version)
-        ent = self._graphs.get(key)
-        if ent is None:
-            _evict_stale_graphs(self._graphs, key, n_weight_fields=3)
-            self._device_path(rgb, img_embed, t_dev, sb, cls)        # eager pass: fills the packed-weight caches
-            torch.cuda.synchronize()
-            s_rgb, s_emb, s_t = rgb.clone(), None if img_embed is None else img_embed.clone(), t_dev.clone()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                s_out = self._device_path(s_rgb, s_emb, s_t, sb, cls)
-            ent = self._graphs[key] = (g, s_rgb, s_emb, s_t, s_out)
-        g, s_rgb, s_emb, s_t, s_out = ent
-        s_rgb.copy_(rgb)
-        if s_emb is not None:
-            s_emb.copy_(img_embed)
-        s_t.copy_(t_dev)
-        g.replay()
-        return s_out[0].clone(), s_out[1].clone()
+        # the class embedding is a function of key fields (batch, domain, dtype); the graph reads it in place, so the entry keeps it alive
+        key = (tuple(rgb.shape), dt, domain, None if img_embed is None else tuple(img_embed.shape), float(sb))
+        return self._replay(key, (rgb, img_embed, t_dev), cls, lambda r, e, t: self._device_path(r, e, t, sb, cls))
 
     # ---- geowizard_pipeline.py:88-230 ----
     @ops.device_scoped
@@ -763,16 +753,12 @@ class DepthNormalEstimationPipeline:
         is a no-op); the reference's own defaults for the original checkpoints are 10 steps, 10 members, gaussian noise.  Resampling runs in torch (the reference goes
         through PIL / cv2 on the host: bicubic for depth, nearest for normals) and the colourised images are left to the caller."""
         assert processing_res >= 0 and ensemble_size >= 1 and denoising_steps >= 1
-        if isinstance(input_image, torch.Tensor):
-            rgb = input_image.squeeze()
-        else:
-            rgb = torch.from_numpy(np.asarray(input_image.convert("RGB"))).permute(2, 0, 1)
-        assert rgb.dim() == 3 and rgb.shape[0] == 3
-        H0, W0 = rgb.shape[-2:]
+        rgb = _image_chw(input_image)
+        size = tuple(rgb.shape[-2:]) if match_input_res else None
         rgb = rgb.to(self.device)
         if processing_res > 0:
             rgb = resize_max_res(rgb, processing_res)
-        rgb_norm = (rgb.float() / 255.0 * 2.0 - 1.0).clamp(-1.0, 1.0).to(self.dtype)
+        rgb_norm = self._unit_range(rgb)
         bs = batch_size if batch_size > 0 else 1
         dup = torch.stack([rgb_norm] * ensemble_size)
         depths, normals = [], []
@@ -789,28 +775,15 @@ class DepthNormalEstimationPipeline:
             normal_pred = ensemble_normals(normal_preds)[0]
         else:
             depth_pred, normal_pred = depth_preds[0], normal_preds[0]
-        if depth_pred.is_cuda:
-            depth_pred = ops.minmax_unit(depth_pred.float().contiguous())       # csrc/prepost.hip (zeros when the prediction is constant)
-        else:
-            mn, mx = depth_pred.min(), depth_pred.max()
-            depth_pred = (depth_pred - mn) / (mx - mn)
-        hwc = False
-        if match_input_res and tuple(depth_pred.shape[-2:]) != (H0, W0):
-            # geowizard_pipeline.py:201-205: Pillow's resize of the float depth (default BICUBIC = the antialiased Keys cubic, a = -0.5) and cv2.INTER_NEAREST for
-            # the normals — on the device through the table-driven resampler of csrc/prepost.hip; host tensors (CPU plumbing runs) take torch's own kernels
-            if depth_pred.is_cuda:
-                depth_pred = resize_device(depth_pred[None], (H0, W0), kind="bicubic")[0]
-                normal_pred = resize_device(normal_pred, (H0, W0), kind="nearest")
-            else:
-                depth_pred = torch.nn.functional.interpolate(depth_pred[None, None], size=(H0, W0), mode="bicubic", antialias=True, align_corners=False)[0, 0]
-                iy = torch.from_numpy(cv2_nearest_indices(normal_pred.shape[-2], H0)).long()
-                ix = torch.from_numpy(cv2_nearest_indices(normal_pred.shape[-1], W0)).long()
-                normal_pred = normal_pred[:, iy][:, :, ix]
+        # geowizard_pipeline.py:201-205: Pillow's resize of the float depth (default BICUBIC = the antialiased Keys cubic, a = -0.5) and cv2.INTER_NEAREST for
+        # the normals — through the table-driven resampler of csrc/prepost.hip.  The predictions are device tensors: single_infer moves its input to the
+        # device and every libe2eft op refuses host tensors (ops._check_cuda), the ensembling ones included
+        depth_pred = _post_depth(depth_pred, size, "bicubic")[0]
+        normal_pred = _post_normals(normal_pred[None], size, "nearest", renorm=False)[0]
         if match_input_res:
-            normal_pred, hwc = normal_pred.permute(1, 2, 0), True      # the reference returns HWC normals after its cv2 resize (:205)
-        return DepthNormalPipelineOutput(depth_np=depth_pred.clamp(0, 1).cpu().numpy().astype(np.float32), depth_colored=None,
-                                         normal_np=normal_pred.clamp(-1, 1).contiguous().cpu().numpy().astype(np.float32), normal_colored=None,
-                                         uncertainty=uncert)
+            normal_pred = normal_pred.permute(1, 2, 0).contiguous()      # the reference returns HWC normals after its cv2 resize (:205)
+        return DepthNormalPipelineOutput(depth_np=depth_pred.cpu().numpy().astype(np.float32), depth_colored=None,
+                                         normal_np=normal_pred.cpu().numpy().astype(np.float32), normal_colored=None, uncertainty=uncert)
 
     @ops.device_scoped
     @torch.no_grad()
@@ -826,15 +799,8 @@ class DepthNormalEstimationPipeline:
         if processing_res < 0 or denoising_steps < 1:
             raise ValueError("processing_res must be >= 0 and denoising_steps >= 1, got %s, %s" % (processing_res, denoising_steps))
         rgb = _uint8_batch(images, self.device)
-        B, _, H0, W0 = rgb.shape
+        size = tuple(rgb.shape[-2:]) if match_input_res else None
         if processing_res > 0:
             rgb = _resize_max_res_batch(rgb, processing_res)
-        rgb_norm = (rgb.float() / 255.0 * 2.0 - 1.0).clamp(-1.0, 1.0).to(self.dtype)
-        d, n = self.single_infer(rgb_norm, domain=domain, num_inference_steps=denoising_steps, noise=noise)
-        h, w = d.shape[-2:]
-        depth = ops.minmax_unit_batched(d.float().reshape(B, h, w).contiguous())
-        normal = n.float()
-        if match_input_res and (h, w) != (H0, W0):
-            depth = resize_device(depth, (H0, W0), kind="bicubic")
-            normal = resize_device(normal.reshape(B * 3, h, w), (H0, W0), kind="nearest").reshape(B, 3, H0, W0)
-        return depth.clamp(0.0, 1.0), normal.clamp(-1.0, 1.0).contiguous()
+        d, n = self.single_infer(self._unit_range(rgb), domain=domain, num_inference_steps=denoising_steps, noise=noise)
+        return _post_depth(d, size, "bicubic"), _post_normals(n, size, "nearest", renorm=False)

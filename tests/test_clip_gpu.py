@@ -177,6 +177,62 @@ def test_geowizard_pipeline_hip_graph_replay(dev):
     assert len(pipe._graphs) == 2
 
 
+def _graph_and_eager_geowizard_pipes(dev, dtype=torch.float16):
+    """(unet, a pipeline with graphs enabled, an eager pipeline over the same tiny models, rgb, img_embed)"""
+    import golden_cases as gc
+    from oracle import config
+    from diffusion_e2e_ft_amd.clip import CLIPVisionModelWithProjection
+    from diffusion_e2e_ft_amd.pipeline import DepthNormalEstimationPipeline
+    from diffusion_e2e_ft_amd.scheduler import DDIMScheduler
+    from diffusion_e2e_ft_amd.unet import UNet2DConditionModel
+    from diffusion_e2e_ft_amd.vae import AutoencoderKL
+    rgb, ctx = gc.geo_pipe_inputs()
+    unet = UNet2DConditionModel(**config.TINY_GEOWIZARD_UNET)
+    unet.load_state_dict(gc.tiny_geo_sd())
+    vae = AutoencoderKL(**config.TINY_VAE)
+    vae.load_state_dict(gc.tiny_vae_sd())
+    cfg = dict(TINY, projection_dim=ctx.shape[-1])
+    enc = CLIPVisionModelWithProjection(**cfg)
+    enc.load_state_dict(tiny_clip_sd(cfg=cfg))
+    unet, vae, enc = unet.to(dev, dtype).eval(), vae.to(dev, dtype).eval(), enc.to(dev, dtype).eval()
+    pipe = DepthNormalEstimationPipeline(unet, vae, DDIMScheduler(), image_encoder=enc).enable_hip_graphs()
+    return unet, pipe, DepthNormalEstimationPipeline(unet, vae, DDIMScheduler(), image_encoder=enc), rgb, ctx
+
+
+def test_geowizard_pipeline_hip_graph_survives_a_domain_switch(dev):
+    """a captured graph reads the class embedding in place, and single_infer keeps only the embedding of the LAST (batch, domain): the cache entry has to keep
+    its own alive, or a replay after another domain was served reads a freed buffer"""
+    _, pipe, eager, rgb, _ = _graph_and_eager_geowizard_pipes(dev)
+    want = {dom: eager.single_infer(rgb, domain=dom) for dom in ("indoor", "outdoor")}
+    for dom in ("indoor", "outdoor", "indoor", "outdoor"):
+        d, n = pipe.single_infer(rgb, domain=dom)
+        assert torch.equal(d, want[dom][0]) and torch.equal(n, want[dom][1]), dom
+    assert len(pipe._graphs) == 2
+    assert not torch.equal(want["indoor"][0], want["outdoor"][0])
+
+
+def test_geowizard_pipeline_hip_graphs_evicted_on_weight_change(dev):
+    """as test_model_gpu.py::test_pipeline_hip_graphs_evicted_on_weight_change, for the joint pipeline: a weight written in place, then a bumped parameter
+    epoch, each drop the cached graphs; the next call captures one graph and gives the eager result of the new weights"""
+    from diffusion_e2e_ft_amd import autograd
+    unet, pipe, eager, rgb, ctx = _graph_and_eager_geowizard_pipes(dev)
+    old = pipe.single_infer(rgb)
+    pipe.single_infer(rgb, img_embed=ctx)
+    assert len(pipe._graphs) == 2
+    with torch.no_grad():
+        w = unet.conv_in.weight
+        w.copy_(w.flip(0).clone())               # output channels in reverse order: in place, same address, another `_version`
+    got = pipe.single_infer(rgb)
+    want = eager.single_infer(rgb)
+    assert len(pipe._graphs) == 1
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(got[0], old[0]) and not torch.equal(got[1], old[1])      # a stale graph would repeat `old`
+    autograd.bump_param_epoch()
+    again = pipe.single_infer(rgb)
+    assert torch.equal(again[0], want[0]) and torch.equal(again[1], want[1])
+    assert len(pipe._graphs) == 1
+
+
 def test_geowizard_pipeline_call(dev):
     """DepthNormalEstimationPipeline.__call__ (geowizard_pipeline.py:88-230): tensor input, resize to processing_res and back,
     ensembling of the (identical, zero-noise) passes, HWC normals"""
