@@ -73,11 +73,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         const T* src = Q + ((long)b * p.nq + (ok ? qr : 0)) * p.ldq + head * 64 + 8 * hh;
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) {
-            Vec16<T> v;
-            v.raw = ok ? *reinterpret_cast<const u32x4*>(src + 16 * ds) : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v.e[e] = from_f<T>(to_f(v.e[e]) * p.c);     // Q' = Q * scale * log2(e): the MFMA delivers exponents
-            qf[j][ds] = v.raw;
+            qf[j][ds] = ok ? *reinterpret_cast<const u32x4*>(src + 16 * ds) : u32x4{0u, 0u, 0u, 0u};
         }
     }
 
@@ -132,20 +128,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
 
     // ---- softmax state.  The kernel is bound by VALU issue (~135 VALU instructions against 16 MFMAs per 64-key tile), so two of
     // the four per-score VALU operations are moved onto the half-idle matrix pipe:
-    //  * the scores come out of the MFMA already in the exponent domain AND relative to the reference maximum: Q is pre-multiplied by
-    //    scale * log2(e) (once per workgroup) and the accumulator chain of S^T starts from a block holding -m_ref instead of 0, so a probability is
-    //    ONE v_exp_f32 of the accumulator (no fma / subtract per score);
+    //  * the scores come out of the MFMA already relative to the reference maximum: the accumulator chain of S^T starts from a block holding -m_ref
+    //    instead of 0 (m_ref in score units, q . k), so a probability is the v_exp_f32 of c * accumulator, c = scale * log2(e), and the multiplication
+    //    is packed — one v_pk_mul_f32 per TWO scores, no subtract.  Q enters the MFMA as loaded: c never meets a T-rounded operand, so the score
+    //    error does not grow with the logits (DESIGN.md §3.11 has the two forms that were measured against this one);
     //  * the row sums come from a fifth accumulator block: l^T += ones(32 x 16) P^T, 4 extra MFMAs per tile instead of 32 v_add_f32 (and the sum is
     //    taken over the ROUNDED probabilities, the ones that multiply V).
     // The reference maximum only moves when a tile exceeds it by more than 2^THR (deferred rescale, as attn512.hip): then — a uniform, rare branch
     // — the tile's scores are shifted, O^T and l^T rescaled and the -m_ref block rewritten.
     constexpr float THR = 6.0f;
+    const float thr = THR / p.c;                    // the threshold in score units
+    const float2v c2 = {p.c, p.c};
     static_assert(QB == 1, "the VALU-light scheme keeps 2 x 16 extra accumulator registers per query block: one query block per wave");
     const u32x4 ones = std::is_same<T, f16>::value ? u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u} : u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
     floatx16 o[2], lacc, cinit;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; lacc[r] = 0.f; cinit[r] = 0.f; }
-    float m_ref = 0.f;      // exponent domain; the first tile always re-references (first = true)
+    float m_ref = 0.f;      // score units (q . k); the first tile always re-references (first = true)
     bool first = true;
     asm volatile("" : "+v"(cinit));     // a register BLOCK of 16 equal values that stays put (not a splat re-materialised in front of every chain)
     u32x4 ones_v = ones;
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         const char* sk = smem + buf * KVBUF;
         const char* sv = sk + KTILE;
 
-        // ---- S'^T = K Q'^T - m_ref : two 32-key sub-tiles ----
+        // ---- S^T - m_ref = K Q^T - m_ref : two 32-key sub-tiles ----
         floatx16 s[2];
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2) {     // (round 4: alternating the two blocks' MFMAs — no dependent neighbours — measured 781 against 795 TF/s this way round)
@@ -221,11 +220,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         for (int r = 1; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[1][r]), s[1][r + 1]);
         mx = fmaxf(mx, s[1][15]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        if (first || __builtin_amdgcn_ballot_w64(mx > THR) != 0) {   // uniform; after the first tiles: rare
+        if (first || __builtin_amdgcn_ballot_w64(mx > thr) != 0) {   // uniform; after the first tiles: rare
             // per query: move the reference by delta >= 0 (first tile: to the tile maximum, whatever its sign), bring this tile's scores, O^T and
             // l^T into the new frame, rewrite the -m_ref block
-            const float delta = first ? mx : (mx > THR ? mx : 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            const float delta = first ? mx : (mx > thr ? mx : 0.f);
+            const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta * p.c);      // (first tile: O^T = l^T = 0, and 2^-delta may not be finite)
             m_ref += delta;
 #pragma unroll
             for (int kt2 = 0; kt2 < 2; ++kt2)
@@ -241,7 +240,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
             for (int w = 0; w < 8; ++w)
-                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
+            {
+                const float2v e = float2v{s[kt2][2 * w], s[kt2][2 * w + 1]} * c2;       // v_pk_mul_f32: the exponents of two scores
+                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1]));
+            }
         }
 
         // ---- O^T += V^T P^T and l^T += 1 P^T ----
@@ -276,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
         const float l_tot = lacc[0];
         const float inv = 1.f / l_tot;
         const int qr = q0 + l31;
-        if (p.lse && hh == 0 && qr < p.nq) p.lse[((long)b * p.heads + head) * p.nq + qr] = m_ref + __builtin_amdgcn_logf(l_tot);
+        if (p.lse && hh == 0 && qr < p.nq) p.lse[((long)b * p.heads + head) * p.nq + qr] = fmaf(m_ref, p.c, __builtin_amdgcn_logf(l_tot));
         if (qr < p.nq) {
             T* dst = (T*)p.out + ((long)b * p.nq + qr) * p.ldo + head * 64;
 #pragma unroll
@@ -356,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
     const int nt = (p.nk_total + KT - 1) / KT;
     fire(0);
 
-    // ---- Q'^T fragments (B operand), pre-multiplied by scale * log2(e)
+    // ---- Q^T fragments (B operand), as loaded
     u32x4 qf[4];
     {
         const int qr = q0 + l31;
@@ -364,11 +366,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
         const T* src = Q + ((long)b * p.nq + (ok ? qr : 0)) * p.ldq + head * 64 + 8 * hh;
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) {
-            Vec16<T> v;
-            v.raw = ok ? *reinterpret_cast<const u32x4*>(src + 16 * ds) : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v.e[e] = from_f<T>(to_f(v.e[e]) * p.c);
-            qf[ds] = v.raw;
+            qf[ds] = ok ? *reinterpret_cast<const u32x4*>(src + 16 * ds) : u32x4{0u, 0u, 0u, 0u};
         }
     }
     // fragment addresses inside a stage.  K: row kt2 * 32 + l31, k-step ds: chunk (2 ds + hh) ^ ((l31 >> 1) & 7)
@@ -383,6 +381,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
     const int vofs[2] = {HALF + vrow + vb1 * 64, HALF + vrow + (1 - vb1) * 64};      // dt = 0, 1
 
     constexpr float THR = 6.0f;
+    const float thr = THR / p.c;                    // the threshold in score units
+    const float2v c2 = {p.c, p.c};
     const u32x4 ones = std::is_same<T, f16>::value ? u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u} : u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
     floatx16 o[2], lacc, cinit;
 #pragma unroll
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
     asm volatile("" ::: "memory");
 
     auto tile = [&](const int t, const char* st) {
-        // ---- S'^T = K Q'^T - m_ref : two 32-key sub-tiles ----
+        // ---- S^T - m_ref = K Q^T - m_ref : two 32-key sub-tiles ----
         floatx16 s[2];
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2) {
@@ -426,9 +426,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
         for (int r = 1; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[1][r]), s[1][r + 1]);
         mx = fmaxf(mx, s[1][15]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        if (first || __builtin_amdgcn_ballot_w64(mx > THR) != 0) {   // uniform; after the first tiles: rare
-            const float delta = first ? mx : (mx > THR ? mx : 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-delta);
+        if (first || __builtin_amdgcn_ballot_w64(mx > thr) != 0) {   // uniform; after the first tiles: rare
+            const float delta = first ? mx : (mx > thr ? mx : 0.f);
+            const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta * p.c);      // (first tile: O^T = l^T = 0, and 2^-delta may not be finite)
             m_ref += delta;
 #pragma unroll
             for (int kt2 = 0; kt2 < 2; ++kt2)
@@ -443,7 +443,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
             for (int w = 0; w < 8; ++w)
-                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(s[kt2][2 * w]), __builtin_amdgcn_exp2f(s[kt2][2 * w + 1]));
+            {
+                const float2v e = float2v{s[kt2][2 * w], s[kt2][2 * w + 1]} * c2;       // v_pk_mul_f32: the exponents of two scores
+                pw[kt2][w] = pack2<T>(__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1]));
+            }
 
         // ---- O^T += V^T P^T and l^T += 1 P^T ----
 #pragma unroll
@@ -479,7 +482,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const AttnParams p
         const float l_tot = lacc[0];
         const float inv = 1.f / l_tot;
         const int qr = q0 + l31;
-        if (p.lse && hh == 0 && qr < p.nq) p.lse[((long)b * p.heads + head) * p.nq + qr] = m_ref + __builtin_amdgcn_logf(l_tot);
+        if (p.lse && hh == 0 && qr < p.nq) p.lse[((long)b * p.heads + head) * p.nq + qr] = fmaf(m_ref, p.c, __builtin_amdgcn_logf(l_tot));
         if (qr < p.nq) {
             T* dst = (T*)p.out + ((long)b * p.nq + qr) * p.ldo + head * 64;
 #pragma unroll

@@ -1,9 +1,9 @@
 // attn_bwd.hip — fused attention backward for head dim 64 (fp16 / bf16), gfx950.  Nothing of size Nq x Nk touches HBM:
 // the probabilities are recomputed from q, k and the forward's log-sum-exp (e2eft_attn_fwd_lse), exactly as in the forward.
 //
-//   P  = 2^(q' k^T - lse2)               q' = round_T(c q), c = scale * log2(e): the forward (attn.hip) multiplies its Q fragments by c ONCE and rounds them,
-//                                        so the recomputation does the same — with c applied to the fp32 score instead, P would differ from the
-//                                        forward's by the rounding of q' (2^-9 relative per element in bf16) and its rows would not sum to one; lse2 from the forward
+//   P  = 2^(c (q k^T) - lse2)            c = scale * log2(e), applied to the fp32 score inside the fma that subtracts lse2 (from the forward).  The forward
+//                                        (attn.hip) contracts the same unscaled q and applies the same c to its fp32 accumulator, so this P is the
+//                                        forward's up to fp32 rounding and its rows sum to one under the saved lse2.
 //   dV = P^T dO
 //   dP = dO V^T,   dS = P o (dP - D),     D[q] = sum_d dO[q,d] O[q,d]
 //   dQ = scale * dS K,   dK = scale * dS^T Q
@@ -134,11 +134,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
         float* sl = reinterpret_cast<float*>(sdt + BTTILE);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            Vec16<T> qs;                       // the score operand is q' = round(c q) as in the forward; the transposed image below (dK's operand) stays q
-            qs.raw = gq[i];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qs.e[e] = from_f<T>(to_f(qs.e[e]) * p.c);
-            *reinterpret_cast<u32x4*>(sq + (r_r0 + 32 * i) * BROW + r_kc * 16) = qs.raw;
+            *reinterpret_cast<u32x4*>(sq + (r_r0 + 32 * i) * BROW + r_kc * 16) = gq[i];
             *reinterpret_cast<u32x4*>(sd + (r_r0 + 32 * i) * BROW + r_kc * 16) = gd[i];
         }
 #pragma unroll
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
                 float pe[4], de[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    pe[e] = __builtin_amdgcn_exp2f(s[4 * g + e] - l4[e]);
+                    pe[e] = __builtin_amdgcn_exp2f(fmaf(s[4 * g + e], p.c, -l4[e]));
                     de[e] = pe[e] * (dp[4 * g + e] - d4[e]);
                 }
                 pw[2 * g] = pack2<T>(pe[0], pe[1]); pw[2 * g + 1] = pack2<T>(pe[2], pe[3]);
@@ -270,11 +266,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
         const T* ds_ = (const T*)p.dout + row * p.lddo + head * 64 + 8 * hh;
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds) {
-            Vec16<T> qv;                       // q' = round(c q): the forward's score operand
-            qv.raw = *reinterpret_cast<const u32x4*>(qs + 16 * ds);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qv.e[e] = from_f<T>(to_f(qv.e[e]) * p.c);
-            qf[ds] = qv.raw;
+            qf[ds] = *reinterpret_cast<const u32x4*>(qs + 16 * ds);
             dof[ds] = *reinterpret_cast<const u32x4*>(ds_ + 16 * ds);
         }
         if (qvalid) {
@@ -362,8 +354,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdParams
             uint32_t dw[8];
 #pragma unroll
             for (int w = 0; w < 8; ++w) {
-                const float p0 = __builtin_amdgcn_exp2f(s[2 * w] - lse2);
-                const float p1 = __builtin_amdgcn_exp2f(s[2 * w + 1] - lse2);
+                const float p0 = __builtin_amdgcn_exp2f(fmaf(s[2 * w], p.c, -lse2));     // (a masked key: -inf c - lse2 = -inf, p = 0)
+                const float p1 = __builtin_amdgcn_exp2f(fmaf(s[2 * w + 1], p.c, -lse2));
                 dw[w] = pack2<T>(p0 * (dp[2 * w] - dsum), p1 * (dp[2 * w + 1] - dsum));
             }
             // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
