@@ -12,7 +12,8 @@
 //   x + 0.5 has 25 significant bits once x >= 2^23, so the upper half of the u's are NOT fp32 numbers (x = 2^24 - 1 would round to u = 1, r = 0 instead of
 //   2.4e-4).  Their complement 1 - u = ((2^24 - 1 - x) + 0.5) * 2^-24 is exact there, so for x >= 2^23 the kernel takes ln u = log1p(-(1 - u)) and
 //   cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u)): every u enters the arithmetic exactly.
-//   slot 0 is the base grid of a call, slot 1 + i the grid of pyramid level i; draw is the caller's per-call counter, passed by value.
+//   slot 0 is the base grid of a call, slot 1 + i the grid of pyramid level i; draw is the caller's per-call counter, passed by value — or, by e2eft_randn_fill_at,
+//   read from device memory (the low 32 bits of an int64), which is what a captured graph needs to draw fresh noise on every replay.
 //
 // Counter-based: any element of any grid is a pure function of (seed, draw, slot, e).  The pyramid kernel therefore evaluates the (at most four) bilinear
 // corners of every level on the fly — no level grid is ever stored — and the result does not depend on the launch geometry.
@@ -91,7 +92,9 @@ template <typename T> __device__ __forceinline__ void store4(T* p, const float v
 // C == 4, hw % 4 == 0, destination aligned: one thread owns four consecutive pixels of one image — four counters (one per channel, each yields that channel's
 // four pixels), four whole-pixel stores.
 template <typename T>
-__global__ __launch_bounds__(256) void randn_fill4_kernel(long groups, int hw, int ldy, uint64_t seed, uint32_t draw, uint32_t slot, T* __restrict__ y) {
+__global__ __launch_bounds__(256) void randn_fill4_kernel(long groups, int hw, int ldy, uint64_t seed, uint32_t draw, const int64_t* __restrict__ draw_at, uint32_t slot,
+                                                          T* __restrict__ y) {
+    if (draw_at) draw = (uint32_t)*draw_at;      // e2eft_randn_fill_at: the low 32 bits of a device int64 (uniform: one scalar load)
     const int gpi = hw >> 2;      // pixel groups per image
     for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < groups; it += (long)gridDim.x * 256) {
         const long b = it / gpi;
@@ -110,7 +113,9 @@ __global__ __launch_bounds__(256) void randn_fill4_kernel(long groups, int hw, i
 
 // any shape: one thread per quad of the logical NCHW index, element-wise stores
 template <typename T>
-__global__ __launch_bounds__(256) void randn_fill_kernel(long total, int c, int hw, int ldy, uint64_t seed, uint32_t draw, uint32_t slot, T* __restrict__ y) {
+__global__ __launch_bounds__(256) void randn_fill_kernel(long total, int c, int hw, int ldy, uint64_t seed, uint32_t draw, const int64_t* __restrict__ draw_at, uint32_t slot,
+                                                         T* __restrict__ y) {
+    if (draw_at) draw = (uint32_t)*draw_at;
     const long quads = (total + 3) >> 2;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
         float z[4];
@@ -263,25 +268,40 @@ static size_t pyr_tot_bytes(long total) { return ((size_t)total * sizeof(float) 
 
 using namespace e2eft;
 
-extern "C" int e2eft_randn_fill(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, uint32_t draw, uint32_t slot, void* y,
-                                void* stream) {
-    E2EFT_REQUIRE(y, "randn_fill: null pointer");
-    E2EFT_REQUIRE(dtype >= 0 && dtype <= 2, "randn_fill: bad dtype");
-    E2EFT_REQUIRE(batch > 0 && c > 0 && hw > 0 && ldy >= c, "randn_fill: shape");
+// draw_at == nullptr: `draw` by value (e2eft_randn_fill); otherwise the kernels read it from the device (e2eft_randn_fill_at) — one body, so both give the same bits
+static int randn_fill_launch(const char* what, int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, uint32_t draw, const int64_t* draw_at,
+                             uint32_t slot, void* y, void* stream) {
     const long total = (long)batch * c * hw;
-    E2EFT_REQUIRE(total < (1L << 31), "randn_fill: more than 2^31 - 1 elements");
     hipStream_t s = (hipStream_t)stream;
     const size_t pixel_bytes = 4 * dtype_size(dtype);
     const bool vec = c == 4 && hw % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y % pixel_bytes) == 0;
     E2EFT_DISPATCH_DTYPE(dtype, T, {
         if (vec) {
             const long groups = (long)batch * (hw / 4);
-            hipLaunchKernelGGL((randn_fill4_kernel<T>), dim3(blocks_for(groups, 16384)), dim3(256), 0, s, groups, hw, ldy, seed, draw, slot, (T*)y);
+            hipLaunchKernelGGL((randn_fill4_kernel<T>), dim3(blocks_for(groups, 16384)), dim3(256), 0, s, groups, hw, ldy, seed, draw, draw_at, slot, (T*)y);
         } else {
-            hipLaunchKernelGGL((randn_fill_kernel<T>), dim3(blocks_for((total + 3) / 4, 16384)), dim3(256), 0, s, total, c, hw, ldy, seed, draw, slot, (T*)y);
+            hipLaunchKernelGGL((randn_fill_kernel<T>), dim3(blocks_for((total + 3) / 4, 16384)), dim3(256), 0, s, total, c, hw, ldy, seed, draw, draw_at, slot, (T*)y);
         }
     });
-    return check_launch("randn_fill");
+    return check_launch(what);
+}
+
+extern "C" int e2eft_randn_fill(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, uint32_t draw, uint32_t slot, void* y,
+                                void* stream) {
+    E2EFT_REQUIRE(y, "randn_fill: null pointer");
+    E2EFT_REQUIRE(dtype >= 0 && dtype <= 2, "randn_fill: bad dtype");
+    E2EFT_REQUIRE(batch > 0 && c > 0 && hw > 0 && ldy >= c, "randn_fill: shape");
+    E2EFT_REQUIRE((long)batch * c * hw < (1L << 31), "randn_fill: more than 2^31 - 1 elements");
+    return randn_fill_launch("randn_fill", dtype, batch, c, hw, ldy, seed, draw, nullptr, slot, y, stream);
+}
+
+extern "C" int e2eft_randn_fill_at(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, const int64_t* draw, uint32_t slot, void* y,
+                                   void* stream) {
+    E2EFT_REQUIRE(y && draw, "randn_fill_at: null pointer");
+    E2EFT_REQUIRE(dtype >= 0 && dtype <= 2, "randn_fill_at: bad dtype");
+    E2EFT_REQUIRE(batch > 0 && c > 0 && hw > 0 && ldy >= c, "randn_fill_at: shape");
+    E2EFT_REQUIRE((long)batch * c * hw < (1L << 31), "randn_fill_at: more than 2^31 - 1 elements");
+    return randn_fill_launch("randn_fill_at", dtype, batch, c, hw, ldy, seed, 0u, draw, slot, y, stream);
 }
 
 extern "C" size_t e2eft_pyramid_noise_workspace_bytes(int32_t batch, int32_t c, int32_t hw) {

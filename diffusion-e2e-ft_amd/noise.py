@@ -5,8 +5,12 @@ The generator is counter-based (Philox4x32-10 on the logical NCHW index, include
 nothing is synchronised with the host, the result does not depend on memory layout or launch geometry, and a host restatement reproduces it
 (tests/noise_ref.py).  Bit parity with torch's own RNG streams is not a goal — torch's CPU and device generators already disagree with each other.
 
-NOT capture-safe: `draw` is a host counter passed to the kernels by value, so a replayed hipGraph repeats the noise it was captured with.  The captured
-paths of the pipelines remain the zeros ones.
+Capture: `draw` is a host counter.  `randn_into` / `pyramid_noise_into` pass it to the kernels by value, so a replayed hipGraph would repeat the noise it was
+captured with — they stay on the eager paths.  `randn_at` is the capture-safe Gaussian draw (`e2eft_randn_fill_at`): the kernel reads `draw` from a one-element
+int64 device tensor that belongs to the graph, and the caller sets it with `set_draw(tensor, gen)` — `fill_(gen.next_draw())`, one launch with the value as a
+kernel argument, no host-to-device copy, no synchronisation — before each replay.  The host counter stays the single source of truth: eager and captured calls on
+one generator interleave and see the sequence they see without capture.  "pyramid" is not captured: its level sizes are fresh host draws of Python's `random`
+per call, as in the reference, so its launch arguments differ from call to call.
 """
 import random
 
@@ -44,6 +48,16 @@ def pyramid_level_sizes(rows, cols, rng=random):
 def randn_into(dst_nhwc_slice, gen):
     """standard normals into an NHWC view [B,H,W,C] (e.g. `xin[..., 4:]`); advances `gen.draw`"""
     return ops.randn_fill_(dst_nhwc_slice, gen.seed, gen.next_draw(), slot=0)
+
+
+def set_draw(draw_dev, gen):
+    """advance `gen.draw` and put the value drawn into the one-element int64 device tensor a captured `randn_at` reads (one fill launch, nothing is copied or read)"""
+    return draw_dev.fill_(gen.next_draw())
+
+
+def randn_at(dst_nhwc_slice, seed, draw_dev):
+    """`randn_into` with the draw read on the device from `draw_dev` (see `set_draw`): the same bits for the same value, safe inside a hipGraph capture"""
+    return ops.randn_fill_at_(dst_nhwc_slice, seed, draw_dev, slot=0)
 
 
 def pyramid_noise_into(dst_nhwc_slice, gen, discount=0.9, sizes=None):

@@ -955,6 +955,29 @@ def randn_fill_(dst, seed, draw, slot=0):
     return dst
 
 
+def randn_fill_at_(dst, seed, draw, slot=0):
+    """`randn_fill_` with `draw` a one-element int64 DEVICE tensor read when the kernel runs (its low 32 bits): the capture-safe form — a replayed graph draws
+    what the tensor holds at replay time.  Same (seed, draw value, slot, shape) -> the bits of `randn_fill_`."""
+    _check_cuda(dst, draw)
+    if draw.dtype != torch.int64 or draw.numel() != 1:
+        raise TypeError("randn_fill_at_: draw must be a one-element int64 tensor, got %s %s" % (draw.dtype, tuple(draw.shape)))
+    B, H, W, Cc = dst.shape
+    check(_lib.load().e2eft_randn_fill_at(dtype_id(dst.dtype), B, Cc, H * W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(draw), int(slot), _ptr(dst), _stream()))
+    return dst
+
+
+def ddim_step_(x, v, coef):
+    """x = coef[0] * x + coef[1] * v in place for NHWC views [B,H,W,C] of one shape (x typically the latent channels of the UNet input); coef: fp32 DEVICE tensor
+    [2], one row of `DDIMScheduler.step_coefficients` — read when the kernel runs, so a captured graph serves every step.  The arithmetic of `latent_x0`."""
+    _check_cuda(x, v, coef)
+    assert x.shape == v.shape and x.dtype == v.dtype, (x.shape, v.shape, x.dtype, v.dtype)
+    if coef.dtype != torch.float32 or coef.numel() != 2 or not coef.is_contiguous():
+        raise TypeError("ddim_step_: coef must be a contiguous fp32 tensor of two elements, got %s %s" % (coef.dtype, tuple(coef.shape)))
+    xa, va = _as_rows(x), _as_rows(v)
+    check(_lib.load().e2eft_ddim_step(dtype_id(x.dtype), xa.shape[0], x.shape[-1], _rows_ld(xa), _rows_ld(va), _ptr(coef), _ptr(xa), _ptr(va), _stream()))
+    return x
+
+
 def pyramid_noise_(dst, seed, draw, sizes, discount=0.9):
     """dst[..., :] = multi-resolution noise (training/util/noise.py:8-18): base + sum_i discount^i * bilinear_up(level_i), divided by its unbiased std over the
     whole tensor, for an NHWC view [B,H,W,C]; sizes: up to 10 (rows, cols) level sizes (host ints, passed by value: no host-to-device copy, no synchronisation)."""

@@ -80,7 +80,9 @@ class _LatentPipeline:
     def enable_hip_graphs(self, enabled=True):
         """Replay the one-step zero-latent `single_infer` from a hipGraph captured per key (Marigold: input shape, dtype, modality, context; GeoWizard: batch
         shape, dtype, domain, embedding source): ~1.4k launches per batch become one graph launch, which removes the host-side gaps on the small UNet levels
-        (at 2 GeoWizard images per step the CLIP tower is launch-bound as well).  Weights are baked in by address: call this again after changing them
+        (at 2 GeoWizard images per step the CLIP tower is launch-bound as well).  Every other step count or start the device can produce inside a capture
+        (zeros, an explicit latent, gaussian from a `noise.DeviceNoise`) runs through `_denoise`: a head, ONE step and a tail graph per key, the DDIM update fused
+        into the step graph; a `torch.Generator` and "pyramid" keep the host-driven loop.  Weights are baked in by address: call this again after changing them
         (load_state_dict, .to(), an optimizer step)."""
         self._graphs = {} if enabled else None
         return self
@@ -112,6 +114,160 @@ class _LatentPipeline:
                 s.copy_(t)
         g.replay()
         return s_out.clone() if isinstance(s_out, torch.Tensor) else tuple(o.clone() for o in s_out)
+
+    # ---- multi-step inference with the DDIM update fused on the device ----
+    _dn_copies = 1        # row blocks of the UNet input that share the rgb latent and the initial noise (GeoWizard: a depth block and a normal block)
+
+    def _fused_denoise(self, num_inference_steps, noise, generator):
+        """does this call run through `_denoise`?  Graphs on, not the one-step zeros case (its own captured path), and a start the device can produce inside a
+        capture: zeros, an explicit latent, or gaussian from a `noise.DeviceNoise`.  A `torch.Generator` and "pyramid" keep the host-driven loop."""
+        if self._graphs is None:
+            return False
+        if isinstance(noise, torch.Tensor):
+            return True
+        if noise == "zeros":
+            return num_inference_steps != 1
+        from .noise import DeviceNoise
+        return noise == "gaussian" and isinstance(generator, DeviceNoise)
+
+    def _denoise(self, rgb, num_inference_steps, noise, generator=None, captured=True, rows=None, img_embed=None, **mode):
+        """Multi-step DDIM inference as three pieces over one set of static buffers per key, each piece a hipGraph when `captured`:
+          head  VAE encode -> the rgb latent into channels 0:C of the persistent UNet input `xin`, the initial latent into C:2C (a memset, a copy of the explicit
+                tensor, or `noise.randn_at` reading the draw from the device), the context / class embedding;
+          step  ONE graph for every step of every schedule: the UNet on `xin` at `t`, then `ops.ddim_step_` in place on xin[..., C:].  Its inputs `t` (int64 [1])
+                and `coef` ([2]) are refreshed before each replay by device-to-device copies from `scheduler.timesteps[i:i+1]` and row i of
+                `scheduler.step_coefficients`; the host loop is n times (two tiny copies + one graph launch) and reads nothing back;
+          tail  decode + head from xin[..., C:], which holds the predicted x0 after the last step (the table's last row).
+        The key leaves the step count out: three steps and four steps share the graphs.  A generator's seed is a launch argument of the head graph (its draw
+        counter is not: `noise.set_draw`), so a generator with another seed recaptures the entry in place — keep one generator per pipeline.  rows: encode ONE image (rgb [1,3,H,W]) and broadcast its latent into
+        `rows` rows — the members of an ensemble (the encoder is batch-invariant bit for bit, tests/test_multistep_graph_gpu.py).  captured=False issues the same
+        launches eagerly on fresh buffers (and needs no graph cache): the capture can then be checked bit for bit, apart from the arithmetic.
+        Everything stays on the current stream; the graphs have no parallel branches."""
+        from . import autograd as F
+        from . import noise as N
+        device, dt = self.device, self.dtype
+        rgb = rgb.to(device=device, dtype=dt)
+        n = int(num_inference_steps)
+        self.scheduler.set_timesteps(n, device=device)
+        table = self.scheduler.step_coefficients(n, device)
+        B = rgb.shape[0] if rows is None else int(rows)
+        if rows is not None and rgb.shape[0] != 1:
+            raise ValueError("_denoise: rows= broadcasts ONE encoded image, got %d" % rgb.shape[0])
+        kind = "tensor" if isinstance(noise, torch.Tensor) else noise
+        if kind == "gaussian" and not isinstance(generator, N.DeviceNoise):
+            raise TypeError("_denoise: noise='gaussian' needs a noise.DeviceNoise generator")
+        if kind not in ("tensor", "zeros", "gaussian"):
+            raise ValueError("_denoise: noise must be 'zeros', 'gaussian' or a tensor, got %s" % (noise,))
+        seed = generator.seed if kind == "gaussian" else None
+        if img_embed is not None:
+            img_embed = img_embed.to(device=device, dtype=dt)
+        ent = None
+        if captured:
+            if self._graphs is None:
+                raise RuntimeError("_denoise(captured=True) needs enable_hip_graphs()")
+            w0 = self.unet.conv_in.weight
+            weights = (F.PARAM_EPOCH, w0.data_ptr(), w0._version)
+            key = ("denoise", tuple(rgb.shape), B, dt, kind, None if img_embed is None else tuple(img_embed.shape)) + self._dn_key(mode) + (weights,)
+            ent = self._graphs.get(key)
+            if ent is not None and ent["seed"] != seed:      # the seed travels by value: another generator seed is another head graph, which REPLACES this one
+                ent = None
+        if ent is None:
+            ent = self._dn_entry(rgb, B, kind, seed, img_embed, mode)
+        st = ent["static"]
+        st["rgb"].copy_(rgb)
+        if img_embed is not None:
+            st["embed"].copy_(img_embed)
+        if kind == "tensor":
+            if tuple(noise.shape) != tuple(st["noise"].permute(0, 3, 1, 2).shape):
+                raise ValueError("_denoise: the explicit latent must be %s, got %s" % (tuple(st["noise"].permute(0, 3, 1, 2).shape), tuple(noise.shape)))
+            st["noise"].copy_(noise.to(device=device, dtype=dt).permute(0, 2, 3, 1))
+        elif kind == "gaussian":
+            N.set_draw(st["draw"], generator)
+        timesteps = self.scheduler.timesteps
+        if captured and "graphs" not in ent:
+            for k in [k for k in self._graphs if k[-1] != weights]:      # as _replay: graphs of an older weight state are unreachable
+                del self._graphs[k]
+            st["t"].copy_(timesteps[:1])
+            st["coef"].copy_(table[0])
+            self._dn_step(ent, *self._dn_head(ent))      # eager pass: fills the packed-weight caches
+            self._dn_tail(ent)
+            torch.cuda.synchronize()
+            graphs = [torch.cuda.CUDAGraph() for _ in range(3)]
+            with torch.cuda.graph(graphs[0]):
+                cond = self._dn_head(ent)
+            with torch.cuda.graph(graphs[1]):
+                self._dn_step(ent, *cond)
+            with torch.cuda.graph(graphs[2]):
+                out = self._dn_tail(ent)
+            # the folded cross-attention the step graph reads in place (modules.Attention._fold keeps ONE entry per layer; another context would free it)
+            folds = [m.__dict__.get("_fold_cache") for m in self.unet.modules() if "_fold_cache" in m.__dict__]
+            ent["graphs"], ent["cond"], ent["out"], ent["alive"] = graphs, cond, out, (w0, folds)
+            self._graphs[key] = ent
+        if captured:
+            g_head, g_step, g_tail = ent["graphs"]
+            g_head.replay()
+        else:
+            cond = self._dn_head(ent)
+        for i in range(n):
+            st["t"].copy_(timesteps[i:i + 1])
+            st["coef"].copy_(table[i])
+            if captured:
+                g_step.replay()
+            else:
+                self._dn_step(ent, *cond)
+        if captured:
+            g_tail.replay()
+            out = ent["out"]
+        else:
+            out = self._dn_tail(ent)
+        return out.clone() if isinstance(out, torch.Tensor) else tuple(o.clone() for o in out)
+
+    def _dn_entry(self, rgb, B, kind, seed, img_embed, mode):
+        """the static buffers and constants of one `_denoise` key.  Data only: an entry must not refer back to the pipeline (a closure over `self` would), or
+        pipeline -> graph cache -> entry -> pipeline is a reference cycle, the graphs are then destroyed by the cyclic collector whenever it runs — and a graph
+        destroyed in the middle of a LATER stream capture aborts the process."""
+        device, dt = rgb.device, rgb.dtype
+        _, C, h, w = self.encode_rgb(rgb).shape      # (the latent's shape; warms the encoder up as well)
+        st = {"rgb": torch.empty_like(rgb), "embed": None if img_embed is None else torch.empty_like(img_embed),
+              "noise": torch.empty((B, h, w, C), dtype=dt, device=device) if kind == "tensor" else None,
+              "draw": torch.zeros(1, dtype=torch.int64, device=device), "t": torch.zeros(1, dtype=torch.int64, device=device),
+              "coef": torch.zeros(2, dtype=torch.float32, device=device)}
+        return {"static": st, "xin": torch.zeros((self._dn_copies * B, h, w, 2 * C), dtype=dt, device=device), "consts": self._dn_setup(B, dt, device, mode),
+                "seed": seed, "kind": kind, "rows": B, "mode": dict(mode)}
+
+    # the three pieces of `_denoise` over an entry: only device work on the current stream (capturable)
+    def _dn_head(self, ent):
+        from . import noise as N
+        st, xin, B, kind = ent["static"], ent["xin"], ent["rows"], ent["kind"]
+        C = xin.shape[-1] // 2
+        lat = self.encode_rgb(st["rgb"]).permute(0, 2, 3, 1)
+        for r in range(self._dn_copies):
+            blk = xin[r * B:(r + 1) * B]
+            if lat.shape[0] == B:
+                ops.copy_scale(lat, blk[..., :C])
+            else:                                   # ONE encoded image broadcast into the rows of an ensemble batch
+                for j in range(B):
+                    ops.copy_scale(lat, blk[j:j + 1, ..., :C])
+        first = xin[:B, ..., C:]
+        if kind == "zeros":
+            xin[..., C:].zero_()
+        else:
+            if kind == "tensor":
+                ops.copy_scale(st["noise"], first)
+            else:
+                N.randn_at(first, ent["seed"], st["draw"])
+            for r in range(1, self._dn_copies):      # the SAME initial noise for every row block (geowizard_pipeline.py:271)
+                ops.copy_scale(first, xin[r * B:(r + 1) * B, ..., C:])
+        return self._dn_context(st["rgb"], st["embed"], ent["consts"], B)
+
+    def _dn_step(self, ent, ctx, cls):
+        xin = ent["xin"]
+        v = self.unet(to_nchw_view(xin), ent["static"]["t"], encoder_hidden_states=ctx, class_labels=cls).sample
+        ops.ddim_step_(xin[..., xin.shape[-1] // 2:], v.permute(0, 2, 3, 1), ent["static"]["coef"])
+
+    def _dn_tail(self, ent):
+        xin = ent["xin"]
+        return self._dn_decode(xin[..., xin.shape[-1] // 2:].permute(0, 3, 1, 2), ent["rows"], ent["mode"])
 
 
 class MarigoldPipeline(_LatentPipeline):
@@ -209,6 +365,8 @@ class MarigoldPipeline(_LatentPipeline):
             # cross-attention layers derived from it (modules.Attention._fold) — a changed embedding is another graph, not a copy into a static buffer
             key = (tuple(rgb_in.shape), rgb_in.dtype, bool(normals), tuple(ctx.shape), float(sb), ctx.data_ptr(), ctx._version)
             return self._replay(key, (rgb_in, t_dev), ctx, lambda r, t: self._e2e_ft_zero_latent(r, t, sb, ctx, normals))
+        if self._fused_denoise(num_inference_steps, noise, generator):
+            return self._denoise(rgb_in, num_inference_steps, noise, generator, normals=normals)
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         rgb_latent = self.encode_rgb(rgb_in)  # [B,4,h,w] logical NCHW
         B, C = rgb_latent.shape[:2]
@@ -226,6 +384,25 @@ class MarigoldPipeline(_LatentPipeline):
             latent = self._ddim_step(v, t_host, cur, i == num_inference_steps - 1)
             ops.copy_scale(latent.permute(0, 2, 3, 1).contiguous(), xin[..., C:])
         return self._decode_head(latent, normals)
+
+    # ---- the pieces `_denoise` asks its pipeline for ----
+    def _dn_key(self, mode):
+        if self.empty_text_embed is None:
+            self.encode_empty_text()
+        ctx = self._empty_ctx(self.device, self.dtype)      # by identity, as the one-step graphs key it (the step graph reads what is derived from it in place)
+        return (bool(mode.get("normals", False)), tuple(ctx.shape), ctx.data_ptr(), ctx._version)
+
+    def _dn_setup(self, B, dt, device, mode):
+        if self.empty_text_embed is None:
+            self.encode_empty_text()
+        src = self._empty_ctx(device, dt)
+        return {"src": src, "ctx": src.repeat(B, 1, 1)}                     # the context single_infer's host-driven loop hands to the UNet
+
+    def _dn_context(self, rgb, embed, consts, B):
+        return consts["ctx"], None
+
+    def _dn_decode(self, x0, B, mode):
+        return self._decode_head(x0, mode.get("normals", False))
 
     def _one_step(self):
         """(t_dev, sb, ctx) of the E2E-FT path: the one-step schedule and the empty-prompt context (encoded on first use)"""
@@ -313,11 +490,16 @@ class MarigoldPipeline(_LatentPipeline):
             rgb = resize_max_res(rgb, processing_res, resample_method)
         rgb_norm = self._unit_range(rgb)
         assert rgb_norm.min() >= -1.0 and rgb_norm.max() <= 1.0
-        dup = torch.stack([rgb_norm] * ensemble_size)
         bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size, max(rgb_norm.shape[1:]), self.dtype)   # :254-261
         preds = []
-        for s in range(0, ensemble_size, bs):
-            preds.append(self.single_infer(dup[s:s + bs], denoising_steps, show_progress_bar, noise=noise, normals=normals, generator=generator))
+        if ensemble_size > 1 and self._fused_denoise(denoising_steps, noise, generator):
+            # the members of a batch share ONE encode: the rgb latent is broadcast into the rows of the UNet input (the encoder is batch-invariant bit for bit)
+            for s in range(0, ensemble_size, bs):
+                preds.append(self._denoise(rgb_norm[None], denoising_steps, noise, generator, rows=min(bs, ensemble_size - s), normals=normals))
+        else:
+            dup = torch.stack([rgb_norm] * ensemble_size)
+            for s in range(0, ensemble_size, bs):
+                preds.append(self.single_infer(dup[s:s + bs], denoising_steps, show_progress_bar, noise=noise, normals=normals, generator=generator))
         preds = torch.cat(preds, dim=0).float().squeeze()
         if ensemble_size > 1:   # marigold_pipeline.py:293-297 (E2E-FT checkpoints are run with ensemble_size=1)
             from .ensemble import ensemble_depths, ensemble_normals
@@ -682,6 +864,24 @@ class DepthNormalEstimationPipeline(_LatentPipeline):
         normal = ops.normal_head(self._decode(geo[B:]).permute(0, 2, 3, 1), clamp=False, sign=-1.0)
         return depth, normal
 
+    # ---- the pieces `_denoise` asks its pipeline for ----
+    _dn_copies = 2
+
+    def _dn_key(self, mode):
+        return (mode.get("domain", "indoor"),)
+
+    def _dn_setup(self, B, dt, device, mode):
+        return {"cls": self.class_embedding(B, mode.get("domain", "indoor"), dt, device)}
+
+    def _dn_context(self, rgb, embed, consts, B):
+        e = self.encode_img_embed(rgb) if embed is None else embed
+        if e.shape[0] != B:                                   # one encoded image broadcast over the rows of an ensemble batch
+            e = e.repeat(B, 1, 1)
+        return e.to(rgb.dtype).repeat(2, 1, 1), consts["cls"]
+
+    def _dn_decode(self, x0, B, mode):
+        return self._decode_heads(x0, B)
+
     def _device_path(self, rgb, img_embed, t_dev, sb, cls):
         """everything after the host-side setup; only device work on the current stream (capturable)"""
         if img_embed is None:
@@ -728,6 +928,8 @@ class DepthNormalEstimationPipeline(_LatentPipeline):
         rgb = input_rgb.to(device=device, dtype=dt)
         B = rgb.shape[0]
         if num_inference_steps != 1 or isinstance(noise, torch.Tensor) or noise != "zeros":
+            if self._fused_denoise(num_inference_steps, noise, generator):
+                return self._denoise(rgb, num_inference_steps, noise, generator, img_embed=img_embed, domain=domain)
             cls = self.class_embedding(B, domain, dt, device)
             return self._multi_step(rgb, None if img_embed is None else img_embed.to(device=device, dtype=dt), cls, num_inference_steps, noise, generator)
         t_dev, sb = self._one_step_schedule()
@@ -760,10 +962,14 @@ class DepthNormalEstimationPipeline(_LatentPipeline):
             rgb = resize_max_res(rgb, processing_res)
         rgb_norm = self._unit_range(rgb)
         bs = batch_size if batch_size > 0 else 1
-        dup = torch.stack([rgb_norm] * ensemble_size)
+        fused = ensemble_size > 1 and self._fused_denoise(denoising_steps, noise, None)
+        dup = None if fused else torch.stack([rgb_norm] * ensemble_size)
         depths, normals = [], []
         for s0 in range(0, ensemble_size, bs):
-            d, n = self.single_infer(dup[s0:s0 + bs], domain=domain, num_inference_steps=denoising_steps, noise=noise)
+            if fused:      # the members of a batch share ONE encode (MarigoldPipeline.__call__)
+                d, n = self._denoise(rgb_norm[None], denoising_steps, noise, rows=min(bs, ensemble_size - s0), img_embed=self.img_embed, domain=domain)
+            else:
+                d, n = self.single_infer(dup[s0:s0 + bs], domain=domain, num_inference_steps=denoising_steps, noise=noise)
             depths.append(d)
             normals.append(n)
         depth_preds = torch.cat(depths, 0).float().squeeze(1)         # [N, H, W]

@@ -53,18 +53,22 @@ class DDIMScheduler:
         with open(os.path.join(save_directory, self.config_name), "w") as f:
             json.dump(cfg, f, indent=2)
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        n, T = num_inference_steps, self.config.num_train_timesteps
-        self.num_inference_steps = n
+    def _spaced(self, n):
+        """the n timesteps of the configured spacing, descending (a float numpy array of whole numbers)"""
+        T = self.config.num_train_timesteps
         sp = self.config.timestep_spacing
         if sp == "trailing":
-            ts = np.round(np.arange(T, 0, -T / n)) - 1
-        elif sp == "leading":
-            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy() + self.config.steps_offset
-        elif sp == "linspace":
-            ts = np.linspace(0, T - 1, n).round()[::-1].copy()
-        else:
-            raise ValueError(sp)
+            return np.round(np.arange(T, 0, -T / n)) - 1
+        if sp == "leading":
+            return (np.arange(0, n) * (T // n)).round()[::-1].copy() + self.config.steps_offset
+        if sp == "linspace":
+            return np.linspace(0, T - 1, n).round()[::-1].copy()
+        raise ValueError(sp)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        n = num_inference_steps
+        self.num_inference_steps = n
+        ts = self._spaced(n)
         self.timesteps_host = [int(v) for v in ts]           # host copy: reading a timestep must not synchronise with the device
         key = (tuple(self.timesteps_host), str(device))
         if getattr(self, "_ts_key", None) != key:            # same schedule as last call: keep the device tensor (no H2D per image)
@@ -101,6 +105,47 @@ class DDIMScheduler:
         sa, _ = self.x0_coefficients(t)
         pt = self.config.prediction_type
         return {"v_prediction": sa, "epsilon": 1.0 / sa, "sample": 0.0}[pt], c_v
+
+    def step_coefficients_f64(self, num_inference_steps):
+        """float64 [n, 2] host tensor: row i < n - 1 is (c_x, c_v) with `step(model_output, t_i, x_t).prev_sample = c_x * x_t + c_v * model_output`, row n - 1 gives
+        `pred_original_sample` (what the pipelines decode after the last step).  With eta = 0 and no clipping the step is linear in (x_t, model_output); with
+        sa = sqrt(abar_t), sb = sqrt(1 - abar_t), sp = sqrt(abar_prev), sq = sqrt(1 - abar_prev), from the values step() reads (the fp32 table entries widened):
+            v_prediction  (sp sa + sq sb,  sq sa - sp sb)        epsilon  (sp / sa,  sq - sp sb / sa)        sample  (sq / sb,  sp - sq sa / sb)
+        and the last row is `x0_coefficients_for` in float64.  clip_sample / thresholding configurations are refused as `zero_latent_x0_scale` refuses them."""
+        if self.config.clip_sample or self.config.thresholding:
+            raise NotImplementedError("the fused multi-step path does not clip / threshold x0 (scheduler config clip_sample=%s, thresholding=%s)"
+                                      % (self.config.clip_sample, self.config.thresholding))
+        n = int(num_inference_steps)
+        pt = self.config.prediction_type
+        if pt not in ("v_prediction", "epsilon", "sample"):
+            raise ValueError("Unknown prediction type %s" % pt)
+        rows = []
+        for i, t in enumerate(int(v) for v in self._spaced(n)):
+            a_t = self.alphas_cumprod[t].item()
+            sa, sb = a_t ** 0.5, (1 - a_t) ** 0.5
+            if i == n - 1:
+                rows.append({"v_prediction": (sa, -sb), "epsilon": (1.0 / sa, -sb / sa), "sample": (0.0, 1.0)}[pt])
+                continue
+            prev_t = t - self.config.num_train_timesteps // n
+            a_prev = (self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod).item()
+            sp, sq = a_prev ** 0.5, (1 - a_prev) ** 0.5
+            rows.append({"v_prediction": (sp * sa + sq * sb, sq * sa - sp * sb), "epsilon": (sp / sa, sq - sp * sb / sa),
+                         "sample": (sq / sb, sp - sq * sa / sb)}[pt])
+        return torch.tensor(rows, dtype=torch.float64)
+
+    def step_coefficients(self, num_inference_steps, device=None):
+        """`step_coefficients_f64` rounded once to fp32, on `device`: [n, 2], row i is what `ops.ddim_step_` reads at step i.  Kept per (schedule, device) as
+        `timesteps` is: no host-to-device copy per image."""
+        c = self.config
+        key = (int(num_inference_steps), str(device), c.prediction_type, c.timestep_spacing, c.steps_offset, c.num_train_timesteps)
+        cache = self.__dict__.setdefault("_coef_cache", {})
+        tab = cache.get(key)
+        if tab is None:
+            if len(cache) > 64:
+                cache.clear()
+            tab = self.step_coefficients_f64(num_inference_steps).to(torch.float32)
+            tab = cache[key] = (tab if device is None else tab.to(device)).contiguous()
+        return tab
 
     def step(self, model_output, timestep, sample, eta=0.0, **kw):
         """DDIM step for epsilon / sample / v_prediction with eta = 0 (elementwise torch ops on tiny latents; the

@@ -37,7 +37,7 @@ extern "C" {
 #define E2EFT_VERSION 119 /* 0.1.1: backward entry points; 111: test-time ensembling, CLIP towers, sample preparation; 119 later gained one export
                              (e2eft_attn_f32split_supported) and one option (E2EFT_OPT_F32_SPLIT_ATTN) without a new number; so did the
                              workspace of e2eft_sumsq and the queries e2eft_sumsq_workspace_bytes / e2eft_ssi_loss_bwd_workspace_bytes
-                             (a stale binary is told apart by e2eft_build_id) */
+                             (a stale binary is told apart by e2eft_build_id); so did e2eft_ddim_step and e2eft_randn_fill_at */
 
 enum {
     E2EFT_OK = 0,
@@ -743,7 +743,7 @@ int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accu
  * kernel then works from 1 - u, which is exact in fp32 there: ln u = log1p(-(1 - u)), cos / sin by the reflection theta -> 2 pi - theta.)  slot 0 is the base grid of a call, slot 1 + i the grid
  * of pyramid level i; `draw` is the caller's per-call counter.  Same (seed, draw, slot, shape) -> the same bits, on every launch:
  * the values do not depend on the launch geometry and no floating-point atomics are used.  `draw` travels by value, so a
- * captured graph that contains one of these calls repeats its noise on replay.
+ * captured graph that contains one of these calls repeats its noise on replay — except e2eft_randn_fill_at, which reads it from the device.
  * ---------------------------------------------------------------------------------------------------- */
 #define E2EFT_PYRAMID_MAX_LEVELS 10
 /* y[p, 0:c] = standard normals for the NHWC destination [batch, hw, (ldy)] — element (b, ch, pix) is e = (b*c + ch)*hw + pix; channels
@@ -751,6 +751,12 @@ int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accu
  * stores when c == 4, hw % 4 == 0, ldy % 4 == 0 and y is aligned to 4 elements.  batch*c*hw < 2^31. */
 int e2eft_randn_fill(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, uint32_t draw, uint32_t slot, void* y,
                      void* stream);
+/* e2eft_randn_fill with `draw` read from DEVICE memory when the kernel runs: the low 32 bits of the int64 at `draw` (a one-element int64 tensor holds
+ * it).  Everything else is e2eft_randn_fill's contract, and the same (seed, draw, slot, element) gives the same bits as e2eft_randn_fill on both of its
+ * paths (one kernel body).  This is the capture-safe form: a graph that contains the call draws what the int64 holds at replay time, so the host writes the
+ * next value of its counter there (one fill launch, no copy, no synchronisation) before each replay. */
+int e2eft_randn_fill_at(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int32_t ldy, uint64_t seed, const int64_t* draw, uint32_t slot, void* y,
+                        void* stream);
 /* Multi-resolution noise (training/util/noise.py:8-18 = marigold_pipeline.py:76-86):
  *   total = base + sum_i discount^i * bilinear_up(level_i),  y = total / std(total)      (std unbiased, over the whole tensor, batch included)
  * base is the grid of slot 0 ([batch,c,rows,cols]), level_i the grid of slot 1 + i ([batch,c,level_sizes[2i],level_sizes[2i+1]]); bilinear_up is
@@ -765,6 +771,14 @@ int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, i
  * coefficients).  x_t is read in place from the noise channels of the UNet input (pixel stride ldxt), v and x0 have their own pixel strides. */
 int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,
                     const void* v, void* x0, void* stream);
+/* One DDIM update (eta = 0, no clipping) of multi-step inference, IN PLACE on the latent channels of the UNet input (csrc/denoise.hip):
+ *   x[p, 0:c] = fmaf(c_x, x[p, 0:c], c_v * v[p, 0:c])      fp32, rounded once to `dtype` — e2eft_latent_x0's arithmetic: equal fp32 coefficients, equal bits.
+ * coef = (c_x, c_v) is a DEVICE array of two floats read when the kernel runs, so one captured graph serves every step of every schedule (row i of
+ * DDIMScheduler.step_coefficients: prev_sample for i < n - 1, the predicted x0 for the last step).  x has pixel stride ldx (channels c..ldx of a pixel and
+ * everything in front of x[p, 0] are never written), v pixel stride ldv; both aligned to their element size.  One whole-pixel access (16 bytes fp32, 8 bytes
+ * f16 / bf16) when c == 4, ldx % 4 == 0, ldv % 4 == 0 and x, v are aligned to 4 elements; one element per item otherwise.  Every thread reads the elements
+ * it owns before it writes them.  x and v must not overlap. */
+int e2eft_ddim_step(int32_t dtype, int64_t pixels, int32_t c, int32_t ldx, int32_t ldv, const float* coef, void* x, const void* v, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Diffusion-objective training step of the GeoWizard trainer (csrc/diffusion.hip): GeoWizard/geowizard/training/train_depth_normal.py:606-609
