@@ -223,6 +223,7 @@ SIGNATURES = {
     "e2eft_randn_fill": (_I, [_I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     "e2eft_pyramid_noise_workspace_bytes": (_Z, [_I, _I, _I]),
     "e2eft_pyramid_noise": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _F, _I, C.POINTER(C.c_int32), _P, _P, _Z, _P]),
+    "e2eft_pyramid_noise_weighted": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _F, _I, C.POINTER(C.c_int32), _P, _F, _P, _P, _Z, _P]),
     "e2eft_latent_x0": (_I, [_I, _L, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "e2eft_randn_fill_at": (_I, [_I, _I, _I, _I, _I, C.c_uint64, _P, C.c_uint32, _P, _P]),
     # multi-step inference (csrc/denoise.hip)

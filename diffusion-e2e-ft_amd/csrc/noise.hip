@@ -164,8 +164,15 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {      // 
 }
 
 // pass 1: total = base + sum_i discount^i * bilinear_up(level_i) in fp32, stored pixel-major ([pixel][channel], dense) in the workspace; per-block partial sums.
+// WEIGHTED (e2eft_pyramid_noise_weighted; GeoWizard/geowizard/training/train_depth_normal.py:286-296): level i of sample b enters with the weight
+//   tw_b = (float)timesteps[b] / timestep_div          one fp32 division, timesteps[b] read from the device
+//   acc  = fmaf(w_i * tw_b, up_i, acc)                 w_i = (float)discount^i; ONE fp32 product, then the fused multiply-add of the unweighted form
+// — the CONTRACT of the weight (include/e2eft.h repeats it; tests/geowizard_pyramid_ref.py restates it from that text).  tw_b == 1 gives the unweighted bits,
+// tw_b == 0 leaves the base grid.  The unweighted instantiation never touches `timesteps` and keeps its arithmetic.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void pyramid_total_kernel(long total, int c, int rows, int cols, PyrLevels lv, uint64_t seed, uint32_t draw,
-                                                            float* __restrict__ tot, double* __restrict__ partial) {
+                                                            const int64_t* __restrict__ timesteps, float timestep_div, float* __restrict__ tot,
+                                                            double* __restrict__ partial) {
     __shared__ double sh[256];
     const int hw = rows * cols;
     float s1 = 0.f, s2 = 0.f;
@@ -176,6 +183,8 @@ __global__ __launch_bounds__(256) void pyramid_total_kernel(long total, int c, i
         const int pix = (int)(gp - b * hw);
         const int yy = pix / cols, xx = pix - yy * cols;
         const long plane = b * c + ch;
+        float tw = 1.f;
+        if constexpr (WEIGHTED) tw = (float)timesteps[b] / timestep_div;
         float acc = normal_at(seed, draw, 0u, (uint64_t)(plane * hw + pix));
         for (int i = 0; i < lv.n; ++i) {
             const int lr = lv.rows[i], lc = lv.cols[i];
@@ -194,7 +203,8 @@ __global__ __launch_bounds__(256) void pyramid_total_kernel(long total, int c, i
                     const float w = wy[a] * wx[d];
                     if (w != 0.f) up = fmaf(w, normal_at(seed, draw, 1u + (uint32_t)i, base + (uint64_t)(ys[a] * lc + xs[d])), up);      // (a level of the output's own size: one corner)
                 }
-            acc = fmaf(lv.weight[i], up, acc);
+            if constexpr (WEIGHTED) acc = fmaf(lv.weight[i] * tw, up, acc);
+            else acc = fmaf(lv.weight[i], up, acc);
         }
         tot[it] = acc;
         s1 += acc;
@@ -309,8 +319,10 @@ extern "C" size_t e2eft_pyramid_noise_workspace_bytes(int32_t batch, int32_t c, 
     return pyr_tot_bytes((long)batch * c * hw) + (size_t)PYR_MAX_BLOCKS * 2 * sizeof(double);
 }
 
-extern "C" int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
-                                   int32_t n_levels, const int32_t* level_sizes, void* y, void* workspace, size_t workspace_bytes, void* stream) {
+// timesteps == nullptr: e2eft_pyramid_noise; otherwise e2eft_pyramid_noise_weighted — one validation, one launcher, one pass-1 body (a template on "weighted")
+static int pyramid_noise_launch(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
+                                int32_t n_levels, const int32_t* level_sizes, const int64_t* timesteps, float timestep_div, void* y, void* workspace,
+                                size_t workspace_bytes, void* stream) {
     E2EFT_REQUIRE(y && workspace && (level_sizes || n_levels == 0), "pyramid_noise: null pointer");
     E2EFT_REQUIRE(dtype >= 0 && dtype <= 2, "pyramid_noise: bad dtype");
     E2EFT_REQUIRE(batch > 0 && c > 0 && rows > 0 && cols > 0 && (long)rows * cols < (1L << 31) && ldy >= c, "pyramid_noise: shape");
@@ -337,7 +349,8 @@ extern "C" int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int3
     float* tot = (float*)workspace;
     double* partial = (double*)((char*)workspace + pyr_tot_bytes(total));
     const unsigned g1 = blocks_for(total, PYR_MAX_BLOCKS);
-    hipLaunchKernelGGL(pyramid_total_kernel, dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, tot, partial);
+    if (timesteps) hipLaunchKernelGGL((pyramid_total_kernel<true>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, timesteps, timestep_div, tot, partial);
+    else hipLaunchKernelGGL((pyramid_total_kernel<false>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, (const int64_t*)nullptr, 1.f, tot, partial);
     const size_t pixel_bytes = 4 * dtype_size(dtype);
     const bool vec = c == 4 && ldy % 4 == 0 && ((uintptr_t)y % pixel_bytes) == 0;
     E2EFT_DISPATCH_DTYPE(dtype, T, {
@@ -345,6 +358,20 @@ extern "C" int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int3
         else hipLaunchKernelGGL((pyramid_scale_kernel<T, false>), dim3(blocks_for(total, 16384)), dim3(256), 0, s, total, c, ldy, (int)g1, tot, partial, (T*)y);
     });
     return check_launch("pyramid_noise");
+}
+
+extern "C" int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
+                                   int32_t n_levels, const int32_t* level_sizes, void* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, nullptr, 1.f, y, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2eft_pyramid_noise_weighted(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw,
+                                            float discount, int32_t n_levels, const int32_t* level_sizes, const int64_t* timesteps, float timestep_div, void* y,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    E2EFT_REQUIRE(timesteps, "pyramid_noise_weighted: null timesteps");
+    E2EFT_REQUIRE(timestep_div > 0.f, "pyramid_noise_weighted: timestep_div must be positive");
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, timesteps, timestep_div, y, workspace, workspace_bytes,
+                                stream);
 }
 
 extern "C" int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,

@@ -11,8 +11,14 @@ int64 device tensor that belongs to the graph, and the caller sets it with `set_
 kernel argument, no host-to-device copy, no synchronisation — before each replay.  The host counter stays the single source of truth: eager and captured calls on
 one generator interleave and see the sequence they see without capture.  "pyramid" is not captured: its level sizes are fresh host draws of Python's `random`
 per call, as in the reference, so its launch arguments differ from call to call.
+
+The GeoWizard trainer has a multi-resolution noise of its own (GeoWizard/geowizard/training/train_depth_normal.py:286-296): level sizes shrunk from the original size by
+numpy's global stream, every level weighted per sample by `timesteps / 1000`.  `geowizard_pyramid_level_sizes` / `geowizard_pyramid_noise_into` are that function
+(`e2eft_pyramid_noise_weighted`; the timesteps are read on the device); the trainers call it `noise_type="geowizard_pyramid"`.
 """
 import random
+
+import numpy as np
 
 from . import ops
 
@@ -67,6 +73,33 @@ def pyramid_noise_into(dst_nhwc_slice, gen, discount=0.9, sizes=None):
     if sizes is None:
         sizes = pyramid_level_sizes(H, W)
     return ops.pyramid_noise_(dst_nhwc_slice, gen.seed, gen.next_draw(), sizes, discount)
+
+
+def geowizard_pyramid_level_sizes(rows, cols, rng=np.random, scale=1.5):
+    """the (rows, cols) of every level grid the GeoWizard trainer's `pyramid_noise_like` (GeoWizard/geowizard/training/train_depth_normal.py:286-296) draws for a
+    [.., rows, cols] latent: one `rng.random()` per level in the reference's order (level 0 included, where r ** 0 = 1), `r = rng.random() * scale + scale`, every
+    level shrunk from the ORIGINAL size — `max(1, int(rows / r ** i))`, not cumulative as `pyramid_level_sizes` — stopping after the first level with a dimension
+    of 1, at most 10 levels.  rng defaults to numpy's global stream (`np.random`), the reference's: `np.random.seed(s)` gives the reference's sizes and leaves the
+    stream where the reference leaves it."""
+    sizes = []
+    for level in range(10):
+        r = rng.random() * scale + scale
+        lr, lc = max(1, int(rows / (r ** level))), max(1, int(cols / (r ** level)))
+        sizes.append((lr, lc))
+        if lr == 1 or lc == 1:
+            break
+    return sizes
+
+
+def geowizard_pyramid_noise_into(dst_nhwc_slice, gen, timesteps, discount=0.9, sizes=None):
+    """the GeoWizard trainer's timestep-weighted multi-resolution noise (train_depth_normal.py:286-296, called at :658-659) of unit std into an NHWC view [B,H,W,C]:
+    level i of sample b weighted by timesteps[b] / 1000 * discount^i (the literal 1000 of :294).  timesteps: int64 device tensor [B], read on the device; `sizes`
+    defaults to `geowizard_pyramid_level_sizes(H, W)` (numpy's global stream, as the reference); advances `gen.draw` once.  Not captured, for `pyramid_noise_into`'s
+    reason: the sizes are fresh host draws per call."""
+    _, H, W, _ = dst_nhwc_slice.shape
+    if sizes is None:
+        sizes = geowizard_pyramid_level_sizes(H, W)
+    return ops.pyramid_noise_weighted_(dst_nhwc_slice, gen.seed, gen.next_draw(), sizes, timesteps, discount, 1000.0)
 
 
 def noise_into(kind, dst_nhwc_slice, gen):

@@ -995,6 +995,34 @@ def pyramid_noise_(dst, seed, draw, sizes, discount=0.9):
     return dst
 
 
+def pyramid_noise_weighted_(dst, seed, draw, sizes, timesteps, discount=0.9, timestep_div=1000.0):
+    """dst[..., :] = the GeoWizard trainer's multi-resolution noise (GeoWizard/geowizard/training/train_depth_normal.py:286-296): `pyramid_noise_` with level i of
+    sample b weighted by timesteps[b] / timestep_div * discount^i (include/e2eft.h states the fp32 expression), divided by the unbiased std of the whole tensor, for an
+    NHWC view [B,H,W,C] (a strided channel slice allowed).  timesteps: a contiguous int64 DEVICE tensor of B elements, read when the kernel runs — nothing is copied to or
+    read by the host, and a captured graph sees what the tensor holds at replay time."""
+    if not isinstance(timesteps, torch.Tensor) or timesteps.dtype != torch.int64:
+        raise TypeError("pyramid_noise_weighted_: timesteps must be an int64 tensor, got %s" % (timesteps.dtype if isinstance(timesteps, torch.Tensor) else type(timesteps)))
+    if dst.dim() != 4:
+        raise ValueError("pyramid_noise_weighted_: dst must be an NHWC view [B,H,W,C], got %s" % (tuple(dst.shape),))
+    B, H, W, Cc = dst.shape
+    if timesteps.numel() != B or not timesteps.is_contiguous():
+        raise ValueError("pyramid_noise_weighted_: timesteps must be contiguous with one entry per sample (%d), got shape %s stride %s"
+                         % (B, tuple(timesteps.shape), tuple(timesteps.stride())))
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    if len(sizes) > 10:
+        raise ValueError("pyramid_noise_weighted_: at most 10 levels, got %d" % len(sizes))
+    if not float(timestep_div) > 0.0:
+        raise ValueError("pyramid_noise_weighted_: timestep_div must be positive, got %r" % (timestep_div,))
+    _check_cuda(dst, timesteps)
+    lib = _lib.load()
+    table = (C.c_int32 * max(2 * len(sizes), 2))(*[v for rc in sizes for v in rc])
+    nbytes = lib.e2eft_pyramid_noise_workspace_bytes(B, Cc, H * W)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dst.device)
+    check(lib.e2eft_pyramid_noise_weighted(dtype_id(dst.dtype), B, Cc, H, W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(discount),
+                                           len(sizes), table, _ptr(timesteps), float(timestep_div), _ptr(dst), _ptr(ws), nbytes, _stream()))
+    return dst
+
+
 def latent_x0(x_t, v, c_x, c_v, out=None):
     """out = c_x * x_t + c_v * v for NHWC views [B,H,W,C] of one shape (x_t typically the noise channels of the UNet input, read in place)."""
     _check_cuda(x_t, v, out)

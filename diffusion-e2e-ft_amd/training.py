@@ -155,12 +155,15 @@ def geowizard_class_embedding(batch, domain, dtype, device):
 
 GEOWIZARD_PYRAMID_MESSAGE = ("noise_type='pyramid' is not built for the GeoWizard trainer: its multi-resolution noise weights every level per sample by t / 1000 "
                              "(GeoWizard/geowizard/training/train_depth_normal.py:286-296), which is a different function from e2eft_pyramid_noise "
-                             "(training/util/noise.py:8-18, no timestep weight)")
+                             "(training/util/noise.py:8-18, no timestep weight); the trainer's own function is noise_type='geowizard_pyramid' "
+                             "(e2eft_pyramid_noise_weighted): map the trainer's `--noise_type pyramid` to that name")
+GEOWIZARD_NOISE_TYPES = ("zeros", "gaussian", "pyramid", "geowizard_pyramid")      # "pyramid" is known and refused (GEOWIZARD_PYRAMID_MESSAGE)
 
 
-def _geowizard_noise(noise_type, generator, noise, rows, C, h, w, dt, dev):
-    """the geometry noise [2b,4,h,w] of the GeoWizard trainer (train_depth_normal.py:656-663) as an NHWC tensor [2b,h,w,4]: an explicit `noise`, zeros, or
-    standard normals drawn on the device by a noise.DeviceNoise"""
+def _geowizard_noise(noise_type, generator, noise, rows, C, h, w, dt, dev, timesteps=None):
+    """the geometry noise [2b,4,h,w] of the GeoWizard trainer (train_depth_normal.py:656-663) as an NHWC tensor [2b,h,w,4]: an explicit `noise`, zeros,
+    standard normals drawn on the device by a noise.DeviceNoise (:661-662), or — "geowizard_pyramid" — the trainer's `pyramid_noise_like(geo_latents, timesteps)`
+    (:286-296, called at :658-659) drawn on the device from the doubled int64 device `timesteps` [2b], which are read there and never by the host"""
     if noise_type == "pyramid":
         raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
     if noise is not None:
@@ -174,6 +177,11 @@ def _geowizard_noise(noise_type, generator, noise, rows, C, h, w, dt, dev):
         if not isinstance(generator, N.DeviceNoise):
             raise TypeError("noise_type='gaussian' draws on the device: pass generator=noise.DeviceNoise(seed)")
         return N.randn_into(torch.empty((rows, h, w, C), dtype=dt, device=dev), generator)
+    if noise_type == "geowizard_pyramid":
+        from . import noise as N
+        if not isinstance(generator, N.DeviceNoise):
+            raise TypeError("noise_type='geowizard_pyramid' draws on the device: pass generator=noise.DeviceNoise(seed)")
+        return N.geowizard_pyramid_noise_into(torch.empty((rows, h, w, C), dtype=dt, device=dev), generator, timesteps)
     raise ValueError("Unknown noise type %s" % noise_type)
 
 
@@ -184,7 +192,10 @@ def geowizard_e2e_ft_loss(unet, vae, batch, imgs_embed, domain="indoor", depth_s
     embedding, the frozen decoder decodes both halves, loss = 0.5 * SSI(depth) + 1.0 * angular(normals vs -GT).
     imgs_embed: CLIP image embeddings [b,1,768] (an input here).
     noise_type (:656-668): "zeros" (default), "gaussian" (drawn on the device by `generator`, a noise.DeviceNoise) or an explicit `noise` [2b,4,h,w]: x_t = noise
-    (:668) goes into channels 4:8 of the UNet input and x0 comes from that x_t; "pyramid" is refused (the trainer's variant is weighted by t / 1000)."""
+    (:668) goes into channels 4:8 of the UNet input and x0 comes from that x_t.  "geowizard_pyramid" (also a noise.DeviceNoise) is the trainer's own
+    `--noise_type pyramid`: `pyramid_noise_like(geo_latents, timesteps)` (:286-296, called at :658-659) with the constant 999 timesteps of :651-652, every level
+    weighted by 999 / 1000; its level sizes come from numpy's global stream as in the reference.  The name "pyramid" itself is refused: in this package it means
+    training/util/noise.py's unweighted function (GEOWIZARD_PYRAMID_MESSAGE)."""
     core = getattr(unet, "module", unet)
     with ops.on_device_of(next(core.parameters())):
         return _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts, noise_type, generator, noise)
@@ -193,7 +204,7 @@ def geowizard_e2e_ft_loss(unet, vae, batch, imgs_embed, domain="indoor", depth_s
 def _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_scale, normal_scale, return_parts, noise_type="zeros", generator=None, noise=None):
     dev = core.device
     dt = getattr(core, "compute_dtype", core.dtype)
-    if noise_type not in ("zeros", "gaussian", "pyramid"):
+    if noise_type not in GEOWIZARD_NOISE_TYPES:
         raise ValueError("Unknown noise type %s" % noise_type)
     if noise_type == "pyramid":
         raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
@@ -219,7 +230,7 @@ def _geowizard_e2e_ft_loss(unet, core, vae, batch, imgs_embed, domain, depth_sca
         ops.copy_scale(lat, xin[:b, ..., :C])
         ops.copy_scale(lat, xin[b:, ..., :C])
         x_t = xin[..., C:]
-        ops.copy_scale(_geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev), x_t)
+        ops.copy_scale(_geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev, timesteps), x_t)      # (:651-652: all 999 under --e2e_ft)
         noise_pred = unet(xin.permute(0, 3, 1, 2), timesteps, ctx, class_labels=cls, return_dict=False)[0]
         c_x, c_v = DDIMScheduler().x0_coefficients_for(999)
         x0 = F.latent_x0(noise_pred, x_t, c_x / sf, c_v / sf)
@@ -241,7 +252,10 @@ def geowizard_diffusion_loss(unet, vae, batch, imgs_embed, domain="indoor", nois
     own arithmetic is five launches of csrc/diffusion.hip and synchronises nothing with the host.
     batch: rgb [b,3,H,W], depth [b,3,H,W] (the normalised depth on three channels), normals [b,3,H,W], val_mask [b,1,H,W]; H and W multiples of 8.
     noise_scheduler: a scheduler.DDPMScheduler (default: a fresh one); prediction_type overrides its config's (:674-676), "epsilon" or "v_prediction".
-    noise_type: "gaussian" (drawn on the device by `generator`, a noise.DeviceNoise), "zeros", or an explicit `noise` [2b,4,h,w]; "pyramid" is refused.
+    noise_type: "gaussian" (drawn on the device by `generator`, a noise.DeviceNoise), "zeros", an explicit `noise` [2b,4,h,w], or "geowizard_pyramid" — the trainer's
+    own `--noise_type pyramid`, `pyramid_noise_like(geo_latents, timesteps)` (:286-296, called at :658-659): drawn by the same kind of generator straight after the
+    doubled timesteps exist, level i of row r weighted by timesteps[r] / 1000 * 0.9^i on the device (no read-back), level sizes from numpy's global stream as in the
+    reference; it then goes through add_noise and the masked MSE as "gaussian" does.  The name "pyramid" is refused (GEOWIZARD_PYRAMID_MESSAGE).
     timesteps: int64 [b] instead of drawn ones (drawn on the device from torch's generator, no read-back).
     No selected cell: the loss is 0 and its gradient is zero everywhere, as e2e_ft_loss does for an all-invalid batch (the reference skips the term, :714).
     Returns the loss; return_parts: (loss, n_selected int64 [1], target fp32 [2b,4,h,w], x_t [2b,4,h,w])."""
@@ -254,7 +268,7 @@ def geowizard_diffusion_loss(unet, vae, batch, imgs_embed, domain="indoor", nois
 def _geowizard_diffusion_loss(unet, core, vae, batch, imgs_embed, domain, noise_scheduler, noise_type, generator, noise, timesteps, prediction_type, return_parts):
     dev = core.device
     dt = getattr(core, "compute_dtype", core.dtype)
-    if noise_type not in ("zeros", "gaussian", "pyramid"):
+    if noise_type not in GEOWIZARD_NOISE_TYPES:
         raise ValueError("Unknown noise type %s" % noise_type)
     if noise_type == "pyramid":
         raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
@@ -280,7 +294,7 @@ def _geowizard_diffusion_loss(unet, core, vae, batch, imgs_embed, domain, noise_
     elif timesteps.numel() != b:
         raise ValueError("timesteps must hold one entry per image (%d), got %d" % (b, timesteps.numel()))
     timesteps = timesteps.to(device=dev, dtype=torch.long).reshape(b).repeat(2)
-    nz = _geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev)
+    nz = _geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev, timesteps)      # (:656-663; the weighted pyramid reads the doubled timesteps on the device)
     abar = noise_scheduler.alphas_cumprod_on(dev)
     xin = torch.empty((2 * b, h, w, 2 * C), dtype=dt, device=dev)
     ops.copy_scale(rgb_latents, xin[:b, ..., :C])

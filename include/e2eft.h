@@ -767,6 +767,19 @@ int e2eft_randn_fill_at(int32_t dtype, int32_t batch, int32_t c, int32_t hw, int
 size_t e2eft_pyramid_noise_workspace_bytes(int32_t batch, int32_t c, int32_t hw);
 int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
                         int32_t n_levels, const int32_t* level_sizes, void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The GeoWizard trainer's timestep-weighted multi-resolution noise (GeoWizard/geowizard/training/train_depth_normal.py:286-296):
+ *   total[b] = base[b] + sum_i (timesteps[b] / timestep_div) * discount^i * bilinear_up(level_i)[b],  y = total / std(total)
+ * Generator, slots, bilinear taps, the two launches, the fixed-order fp64 std and the workspace are e2eft_pyramid_noise's; level_sizes are
+ * whatever the caller drew (the trainer shrinks from the ORIGINAL size at every level, noise.geowizard_pyramid_level_sizes).  The weight, exactly:
+ *   tw_b = (float)timesteps[b] / timestep_div        one fp32 division
+ *   acc  = fmaf(w_i * tw_b, up_i, acc)               w_i = (float)discount^i (the double power rounded once, as e2eft_pyramid_noise); ONE fp32
+ *                                                    product, then the fused multiply-add of the unweighted form
+ * so timesteps[b] == timestep_div gives the bits of e2eft_pyramid_noise and timesteps[b] == 0 leaves row b its base grid (before the common division).
+ * timesteps is a DEVICE array of `batch` int64 read when the kernel runs — nothing is copied to or read by the host, and a captured graph sees the values
+ * the array holds at replay time.  timestep_div > 0 (the trainer's literal 1000, not num_train_timesteps). */
+int e2eft_pyramid_noise_weighted(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
+                                 int32_t n_levels, const int32_t* level_sizes, const int64_t* timesteps, float timestep_div, void* y, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 /* x0[p, 0:c] = c_x * x_t[p, 0:c] + c_v * v[p, 0:c] in fp32 (train.py:509-518 by prediction_type; the caller folds 1 / scaling_factor, :528, into both
  * coefficients).  x_t is read in place from the noise channels of the UNet input (pixel stride ldxt), v and x0 have their own pixel strides. */
 int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,
