@@ -36,7 +36,10 @@ struct IgemmParams {
     int nzi;
     long sa_o, sa_i, sw_o, sw_i, so_o, so_i, sr_o, sr_i;
     int mtiles, ntiles;
-    float* gn_partial;   // optional: [img][gn_nslabs][N][3] (n, mean, M2) GroupNorm partials of the rounded output
+    float* gn_partial;   // optional: [img][gn_nslabs][N][3] (n, mean, M2) GroupNorm partials of the output.  Every vector epilogue (the full-tile path of
+                         // igemm_epilogue_rows, igemm_persistent_epilogue.inc) takes them from the fp32 value BEFORE it is rounded to the output type; only
+                         // the generic branch of igemm_epilogue_rows would take them from the rounded value, and no launch reaches it with statistics
+                         // (the hosts keep gn_partial for full, vector-aligned tiles only).  tests/gn_stats_model.py: TARGET
     int gn_nslabs;       // row slabs (one per M-tile) per image
     int ksplit_taps;     // conv split-K: batch index zi covers filter taps [zi * ksplit_taps, (zi + 1) * ksplit_taps) (0 = whole K)
     const float* nrm_ad; // optional (igemm6 only): the A operand is read through GroupNorm(+SiLU): [image][cin][2] fp32 (a, mean) pairs of e2eft_groupnorm_fwd_stats ...

@@ -68,33 +68,37 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(GnGeom g, const T* __re
             n += 1.f;
         }
     }
-    // per-thread triples -> LDS [pl][chl][e]
+    // per-thread (pivot, mean - pivot, M2) -> LDS [pl][chl][e]; the count of a lane follows from the slab: lane q reads pixels p0 + q, p0 + q + pl, ...
     if (active) {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
-            float mean = 0.f, m2 = 0.f;
+            float ds = 0.f, m2 = 0.f;
             if (n > 0.f) {
-                const float ds = s[e] / n;
-                mean = piv[e] + ds;
+                ds = s[e] / n;
                 m2 = fmaxf(ss[e] - s[e] * ds, 0.f);
             }
             float* o = sm + ((pl * g.cpb + chl) * EPC + e) * 3;
-            o[0] = n; o[1] = mean; o[2] = m2;
+            o[0] = piv[e]; o[1] = ds; o[2] = m2;
         }
     }
     __syncthreads();
-    // merge across pixel lanes: one thread per channel of this block
+    // merge across pixel lanes: one thread per channel of this block.  The lanes' means are merged RELATIVE to lane 0's pivot — (pivot_q - pivot_0) + ds_q, numbers
+    // of the size of the data's spread — and the pivot is added back once at the end: merging absolute means rounds at the size of the mean in every step, which
+    // costs delta its low bits (the M2 of a 2 x 9-pixel slab of bf16 data at mean / sigma = 260 came out 3.5 x the fp32 bound of tests/gn_stats_model.py).
     const int cblk = g.cpb * EPC;
+    const int len = p1 - p0, nlo = len / g.pl, nrem = len - nlo * g.pl;   // lanes q < nrem hold nlo + 1 pixels, the others nlo
+    const int nq = min(g.pl, len);
     for (int cc = tid; cc < cblk; cc += 256) {
+        const float p00 = sm[cc * 3];
         Triple acc = {0.f, 0.f, 0.f};
-        for (int q = 0; q < g.pl; ++q) {
+        for (int q = 0; q < nq; ++q) {
             const float* o = sm + (q * cblk + cc) * 3;
-            Triple t = {o[0], o[1], o[2]};
+            Triple t = {(float)(nlo + (q < nrem ? 1 : 0)), (o[0] - p00) + o[1], o[2]};
             acc = merge(acc, t);
         }
         const int cg = blockIdx.z * cblk + cc;
         float* o = partial + (((long)b * g.nslabs + blockIdx.x) * g.C + cg) * 3;
-        o[0] = acc.n; o[1] = acc.mean; o[2] = acc.m2;
+        o[0] = acc.n; o[1] = p00 + acc.mean; o[2] = acc.m2;
     }
 }
 
