@@ -44,7 +44,7 @@ def _hipcc():
     raise RuntimeError("hipcc not found (need ROCm >= 7.0 to build libe2eft.so for gfx950)")
 
 
-HEADERS = ["common.h", "reduce.h", "select.h", "gfx950.h", "igemm.h", "attn32.h", "attn512_regs.inc", "igemm_persistent_epilogue.inc"]      # csrc files that are included, not compiled
+HEADERS = ["common.h", "reduce.h", "select.h", "gfx950.h", "igemm.h", "igemm_epilogue.h", "attn32.h", "attn512_regs.inc"]      # csrc files that are included, not compiled
 
 
 def _inputs():

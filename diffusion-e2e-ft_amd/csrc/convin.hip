@@ -13,7 +13,7 @@
 // Persistent workgroups (one per CU) walk contiguous per-XCD chunks of the tile range.  Bound: the output stream.
 // Eligibility (host, launch_conv_thin_in returns -1): 16-bit, 3x3 / stride 1 / pad 1, exactly 8 input channels at pixel stride 8, one source, no
 // residual / row vector, width % 32 == 0, height % 8 == 0, Cout % 8 == 0, at least two tiles per CU.  Summation order: taps in order, fp32.
-#include "igemm.h"
+#include "igemm_epilogue.h"
 #include <atomic>
 #include <type_traits>
 
@@ -31,7 +31,6 @@ template <typename T>
 __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, const int total_tiles) {
     using namespace thin;
     __shared__ __attribute__((aligned(16))) char smem[LDS];
-    typedef float f2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -49,15 +48,11 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
     if (u >= cend) return;
 
     const T* __restrict__ bias = (const T*)p.bias;
-    const T* __restrict__ rowadd = nullptr;       // (names the shared epilogue expects; this kernel has neither a row vector nor a residual)
-    constexpr bool has_res = false;
-    const bool has_ra = false, stats = p.gn_partial != nullptr;
-    Vec16<T> pre_res[4], pre_bias, pre_ra;
-    T col_bias[2], col_ra[2];
-    long c_orow = 0, c_rrow = 0;
-    int c_n0 = -1, c_mt = 0, c_ncl = 0;
+    const bool stats = p.gn_partial != nullptr;
+    EpiOperands<T, false> ops;                    // (the bias of the lane's two columns; this kernel has neither a row vector nor a residual)
+    long c_orow = 0;
+    int c_n0 = -1, c_mt = 0;
     bool c_colok = false;
-    (void)pre_res; (void)pre_bias; (void)pre_ra; (void)rowadd; (void)c_rrow; (void)c_ncl;
 
     const __amdgpu_buffer_rsrc_t rsx = whole_range_rsrc(p.x1);
     // tile -> (M tile, N tile) with N fastest, M tile -> (image, 8 x 32 block)
@@ -102,15 +97,8 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
     };
 
     floatx16 acc[2][2];
-    auto epi_rofs = [&](const int r) -> long { return (long)(r & 31) + (long)(r >> 5) * W; };
-    auto epi_rows_left = [&]() -> int { return 0x40000000; };
-    constexpr int EPI_DEP = WIN;
-    constexpr bool EPI_M16 = false;      // (the 32x32 accumulator layout)
-    auto epi_srow = [&](const int s) -> int { return 8 * s; };
-#define EPI_STAMP(i) do { } while (0)
-#include "igemm_persistent_epilogue.inc"
-#undef EPI_STAMP
-    (void)epilogue;
+    const RowsBlock rows{W};
+    const EpiCtx<T, false, floatx16[2][2], RowsBlock> epi{p, smem, acc, ops, rows, wave, lane, l31, h, er, ec, bias, false, stats, c_orow, c_colok};
 
     coords(u);
     load_a();
@@ -118,12 +106,11 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
         // ---- this tile: epilogue addressing, weights (if the N tile changed), the 20 MFMAs
         if (t_n0 != c_n0) {
             load_b(t_n0);
-            const int cA = t_n0 + wn * 64 + l31, cB = cA + 32;
-            if (bias) { col_bias[0] = bias[cA < p.N ? cA : t_n0]; col_bias[1] = bias[cB < p.N ? cB : t_n0]; }
+            ops.request_cols(p, bias, (const T*)nullptr, false, lane, t_n0, t_n0 + wn * 64, 0);
         }
         c_n0 = t_n0; c_mt = t_mt;
         c_colok = c_n0 + wn * 64 + ec * 8 < p.N;
-        c_ncl = c_colok ? c_n0 + wn * 64 + ec * 8 : c_n0;
+        const int c_ncl = c_colok ? c_n0 + wn * 64 + ec * 8 : c_n0;
         c_orow = (((long)t_img * H + t_oy0 + 2 * wm) * W + t_ox0 + er) * p.ldo + c_ncl;
         const floatx16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         acc[0][0] = Mma32x32x16<T>::run(afr[0][0], bfr[0][0], z);
@@ -141,12 +128,12 @@ __global__ __launch_bounds__(512) void conv_thin_in_kernel(const IgemmParams p, 
         u += nslots;
         const bool more = u < cend;
         if (more) { coords(u); load_a(); }
-        epilogue_packed(0, 0L);                    // windows at LDS offset 0 (+ wave * 4096 inside)
+        epilogue_packed<WIN>(epi, 0, 0L);          // windows at LDS offset 0 (+ wave * 4096 inside), deposits behind them
         if (stats) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();            // every wave's deposits are written
             asm volatile("" ::: "memory");
-            { const int img = c_mt / tpi; combine(img, c_mt - img * tpi, c_n0); }
+            { const int img = c_mt / tpi; combine(p, reinterpret_cast<const float*>(smem + WIN), tid, BN, img, c_mt - img * tpi, c_n0); }
             __builtin_amdgcn_s_barrier();            // ... and merged, before the next tile's deposits overwrite them
             asm volatile("" ::: "memory");
         }

@@ -1,4 +1,4 @@
-// igemm.h — parameter block shared by the implicit-GEMM kernel variants.
+// igemm.h — parameter block, stamp macros, planner and launcher declarations of the implicit-GEMM kernel variants (their epilogues: igemm_epilogue.h).
 #pragma once
 #include "gfx950.h"
 
@@ -36,10 +36,9 @@ struct IgemmParams {
     int nzi;
     long sa_o, sa_i, sw_o, sw_i, so_o, so_i, sr_o, sr_i;
     int mtiles, ntiles;
-    float* gn_partial;   // optional: [img][gn_nslabs][N][3] (n, mean, M2) GroupNorm partials of the output.  Every vector epilogue (the full-tile path of
-                         // igemm_epilogue_rows, igemm_persistent_epilogue.inc) takes them from the fp32 value BEFORE it is rounded to the output type; only
-                         // the generic branch of igemm_epilogue_rows would take them from the rounded value, and no launch reaches it with statistics
-                         // (the hosts keep gn_partial for full, vector-aligned tiles only).  tests/gn_stats_model.py: TARGET
+    float* gn_partial;   // optional: [img][gn_nslabs][N][3] (n, mean, M2) GroupNorm partials of the output.  Every epilogue that emits them (igemm_epilogue.h: the full-tile
+                         // path of igemm_epilogue_rows, the persistent kernels' epilogues) takes them from the fp32 value BEFORE it is rounded to the output
+                         // type; the hosts keep gn_partial for full, vector-aligned tiles only.  tests/gn_stats_model.py: TARGET
     int gn_nslabs;       // row slabs (one per M-tile) per image
     int ksplit_taps;     // conv split-K: batch index zi covers filter taps [zi * ksplit_taps, (zi + 1) * ksplit_taps) (0 = whole K)
     const float* nrm_ad; // optional (igemm6 only): the A operand is read through GroupNorm(+SiLU): [image][cin][2] fp32 (a, mean) pairs of e2eft_groupnorm_fwd_stats ...
@@ -62,318 +61,6 @@ struct IgemmParams {
                          // delivery: profiles/r03d_a_operand_delivery_probe.txt, "what an A-reuse scheme could buy at most")
 };
 
-// ---------------------------------------------------------------------------------------------------------------
-// Shared epilogue: the 32x32 MFMA accumulator layout (lane = column, registers = rows) would give 2-byte scattered
-// stores and one dependent residual load per element.  Instead the fp32 tile goes through LDS once (the k-loop is
-// finished, its buffers are free) and is written back row-wise: every thread owns 8 consecutive columns of a row,
-// residual / output move as 16-byte vectors, a wave covers 4 full 256-byte rows per instruction.
-//   out = alpha * (acc + bias + rowadd[img(m)]) + residual
-// Optionally (p.gn_partial) the epilogue also emits the GroupNorm statistics of the tile it just wrote — per column, Welford
-// over each thread's rows, butterfly + LDS merge over the workgroup — so that the consuming GroupNorm skips its statistics
-// pass over HBM (one of its three passes).
-template <typename T, int BM_, int BN_, int NT_>
-__device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, char* smem, int m0, int n0, int zo, int zi);
-
-template <typename T, int BM_, int BN_, int NT_>
-__device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, char* smem, floatx16 (&acc)[2][2], int wm, int wn, int l31,
-                                               int h, int m0, int n0, int zo, int zi) {
-    constexpr int LDT = BN_ + 4;            // fp32 row stride of the staged tile (528 B for BN = 128)
-    float* tile = reinterpret_cast<float*>(smem);
-    __syncthreads();                        // every wave is done reading the last k-tile
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                tile[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * LDT + wn * 64 + j * 32 + l31] = acc[i][j][r];
-    __syncthreads();
-    E2EFT_STAMP(3);
-    igemm_epilogue_rows<T, BM_, BN_, NT_>(p, smem, m0, n0, zo, zi);
-}
-
-// the row passes over a tile that is already staged in LDS as fp32 [BM_][BN_ + 4] (all threads past a barrier): bias / rowadd / alpha /
-// residual, rounding, 16-byte stores, optional GroupNorm statistics.  
-template <typename T, int BM_, int BN_, int NT_>
-__device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, char* smem, int m0, int n0, int zo, int zi) {
-    constexpr int EPC = 16 / (int)sizeof(T);
-    constexpr int LDT = BN_ + 4;            // fp32 row stride of the staged tile (528 B for BN = 128)
-    constexpr int CPR = BN_ / 8;            // 8-column chunks per row
-    constexpr int RPP = NT_ / CPR;          // rows per pass
-    constexpr int NPASS = BM_ / RPP;        // rows per thread
-    constexpr int NWV = NT_ / 64;
-    float* tile = reinterpret_cast<float*>(smem);
-    float* gst = tile + BM_ * LDT;          // [NWV][16 chunks][8 cols][2] wave partials of the GroupNorm statistics
-
-    const T* __restrict__ bias = (const T*)p.bias;
-    const T* __restrict__ rowadd = (const T*)p.rowadd;
-    const T* __restrict__ res = p.residual ? (const T*)p.residual + zo * p.sr_o + zi * p.sr_i : nullptr;
-    T* __restrict__ out = (T*)p.out + zo * p.so_o + zi * p.so_i;
-    const int chunk = threadIdx.x % CPR, rbase = threadIdx.x / CPR;
-    const int n = n0 + chunk * 8;
-    const bool col_ok = n < p.N;
-    const bool vec = (p.N % 8 == 0) && (p.ldo % EPC == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) &&
-                     (!res || (p.ldr % EPC == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0));
-    const bool stats = p.gn_partial != nullptr;   // host guarantees: vec, whole tile inside one image, all rows valid
-    const int nv = min(8, p.N - n);
-    float bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bv[e] = (bias && !p.bias_along_m && col_ok && e < nv) ? to_f(bias[n + e]) : 0.f;
-    float s_mean[8], s_m2[8];   // Welford state over this thread's NPASS rows (per column)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s_mean[e] = s_m2[e] = 0.f;
-
-    // ---- fast path: vector epilogue on a tile that lies completely inside the problem; every condition is workgroup-uniform and
-    // hoisted, so the pass loop is straight-line code: x = fma(acc, alpha, bias*alpha) [+ rowadd*alpha] [+ residual], one
-    // v_cvt_pk per column pair, one 16-byte store per row chunk.  (The generic loop below costs ~9k cycles per 256x128 tile in
-    // exec-mask branches and scalar fallbacks even when none is taken — scripts/stamp_bench.py.)
-    const bool full = vec && m0 + BM_ <= p.M && !(bias && p.bias_along_m);   // a ragged last N-tile only idles the threads of its missing chunks
-    if (full) {
-        const float al = p.alpha;
-        float bva[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bva[e] = bv[e] * al;
-        const bool one_img = p.rows_per_img % BM_ == 0 || p.rows_per_img >= p.M;
-        const int img0 = rowadd ? m0 / p.rows_per_img : 0;
-        T* __restrict__ orow = out + (long)(m0 + rbase) * p.ldo + n;
-        const T* __restrict__ rrow = res ? res + (long)(m0 + rbase) * p.ldr + n : nullptr;
-        const long ostep = (long)RPP * p.ldo, rstep = (long)RPP * p.ldr;
-        // GroupNorm statistics: every thread of a column accumulates sum(x - pv), sum((x - pv)^2) about the same pivot pv (the tile's
-        // first row before rowadd / residual: any value near the data does), so partial results merge by plain addition.  They are
-        // taken from the fp32 value; rounding to T adds a variance of ~2^-22 x^2 (fp16) / 2^-16 x^2 (bf16) — below the kernels' noise.
-        float pv[8];
-        if (stats) {
-            const floatx4 q0 = *reinterpret_cast<const floatx4*>(tile + chunk * 8);
-            const floatx4 q1 = *reinterpret_cast<const floatx4*>(tile + chunk * 8 + 4);
-            const float pr[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pv[e] = fmaf(pr[e], al, bva[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pv[e] = 0.f;
-        }
-        // The row passes work on float2 values: explicit packed math (v_pk_fma_f32 / v_pk_add_f32 on NATURAL register pairs — the pairs
-        // are the dword pairs of the ds_read_b128 results, so no operand swizzle is needed; the swizzled forms the SLP vectorizer used
-        // to generate here are the ones that misread on gfx950, DESIGN.md §3.6, and build.py keeps that vectorizer off).  The
-        // statistics cost 4.6k cycles per 256x128 tile as scalar code (3 VALU per element) against 3.6k packed.
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 al2 = {al, al};
-        f2 bva2[4], pv2[4], sm2[4], sq2[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            bva2[q] = f2{bva[2 * q], bva[2 * q + 1]};
-            pv2[q] = f2{pv[2 * q], pv[2 * q + 1]};
-            sm2[q] = f2{0.f, 0.f};
-            sq2[q] = f2{0.f, 0.f};
-        }
-        // p.out_seg > 0 (e2eft_upconv2x_fwd: one parity phase of a 2x-upsampled image): GEMM row m lands on output row m + (m / out_seg) * out_seg
-        auto seg_off = [&](const int row) -> long { return p.out_seg > 0 ? (long)((m0 + row) / p.out_seg) * p.out_seg * p.ldo : 0L; };
-        auto run = [&](auto has_res, auto has_ra) {
-            constexpr bool HAS_RES = decltype(has_res)::value, HAS_RA = decltype(has_ra)::value;
-#pragma unroll
-            for (int pass = 0; pass < NPASS; ++pass) {
-                const int row = rbase + pass * RPP;
-                const floatx4 t0 = *reinterpret_cast<const floatx4*>(tile + row * LDT + chunk * 8);
-                const floatx4 t1 = *reinterpret_cast<const floatx4*>(tile + row * LDT + chunk * 8 + 4);
-                f2 x2[4] = {f2{t0[0], t0[1]}, f2{t0[2], t0[3]}, f2{t1[0], t1[1]}, f2{t1[2], t1[3]}};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) x2[q] = __builtin_elementwise_fma(x2[q], al2, bva2[q]);
-                if constexpr (HAS_RA) {
-                    const int img = one_img ? img0 : (m0 + row) / p.rows_per_img;
-                    const T* ra = rowadd + (long)img * p.N + n;
-#pragma unroll
-                    for (int q = 0; q < 8 / EPC; ++q) {
-                        const Vec16<T> t = ld16(ra + q * EPC);
-#pragma unroll
-                        for (int e = 0; e < EPC; e += 2) {
-                            const int j = (q * EPC + e) >> 1;
-                            x2[j] = __builtin_elementwise_fma(f2{to_f(t.e[e]), to_f(t.e[e + 1])}, al2, x2[j]);
-                        }
-                    }
-                }
-                if constexpr (HAS_RES) {
-#pragma unroll
-                    for (int q = 0; q < 8 / EPC; ++q) {
-                        const Vec16<T> t = ld16(rrow + pass * rstep + q * EPC);
-#pragma unroll
-                        for (int e = 0; e < EPC; e += 2) {
-                            const int j = (q * EPC + e) >> 1;
-                            x2[j] += f2{to_f(t.e[e]), to_f(t.e[e + 1])};
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 8 / EPC; ++q) {
-                    Vec16<T> o;
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) o.e[e] = from_f<T>(x2[(q * EPC + e) >> 1][(q * EPC + e) & 1]);
-                    st16(orow + pass * ostep + seg_off(row) + q * EPC, o);
-                }
-                if (stats) {   // uniform: shifted sums about a per-column pivot shared by the whole tile (sm2 = sum, sq2 = sum of squares)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f2 d = x2[q] - pv2[q];
-                        sm2[q] += d;
-                        sq2[q] = __builtin_elementwise_fma(d, d, sq2[q]);
-                    }
-                }
-            }
-        };
-        if (col_ok) {
-            if (res) {
-                if (rowadd) run(std::true_type{}, std::true_type{});
-                else run(std::true_type{}, std::false_type{});
-            } else {
-                if (rowadd) run(std::false_type{}, std::true_type{});
-                else run(std::false_type{}, std::false_type{});
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            s_mean[2 * q] = sm2[q][0]; s_mean[2 * q + 1] = sm2[q][1];
-            s_m2[2 * q] = sq2[q][0]; s_m2[2 * q + 1] = sq2[q][1];
-        }
-        if (stats) {   // uniform.  lanes l, l^16, l^32, l^48 own the same 8 columns: add; then the waves through LDS
-#pragma unroll
-            for (int off = 16; off <= 32; off <<= 1)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    s_mean[e] += __shfl_xor(s_mean[e], off, 64);
-                    s_m2[e] += __shfl_xor(s_m2[e], off, 64);
-                }
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-            float* piv = gst + NWV * 16 * 8 * 2;
-            if (lane < 16) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    gst[((wv * 16 + lane) * 8 + e) * 2] = s_mean[e];
-                    gst[((wv * 16 + lane) * 8 + e) * 2 + 1] = s_m2[e];
-                    if (wv == 0) piv[lane * 8 + e] = pv[e];
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x < BN_ && n0 + (int)threadIdx.x < p.N) {
-                const int c = threadIdx.x;
-                float su = 0.f, sq = 0.f;
-#pragma unroll
-                for (int w = 0; w < NWV; ++w) {
-                    su += gst[((w * 16 + c / 8) * 8 + (c & 7)) * 2];
-                    sq += gst[((w * 16 + c / 8) * 8 + (c & 7)) * 2 + 1];
-                }
-                const float nrow = (float)BM_;
-                const int img = m0 / p.rows_per_img;
-                const int slab = (m0 - img * p.rows_per_img) / BM_;
-                float* o = p.gn_partial + (((long)img * p.gn_nslabs + slab) * p.N + n0 + c) * 3;
-                o[0] = nrow;
-                o[1] = piv[c] + su / nrow;
-                o[2] = fmaxf(sq - su * su / nrow, 0.f);
-            }
-        }
-        return;
-    }
-    {
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-        const int row = rbase + pass * RPP;
-        const int m = m0 + row;
-        if (m >= p.M || !col_ok) continue;
-        const floatx4 t0 = *reinterpret_cast<const floatx4*>(tile + row * LDT + chunk * 8);
-        const floatx4 t1 = *reinterpret_cast<const floatx4*>(tile + row * LDT + chunk * 8 + 4);
-        float v[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-        const float bm = (bias && p.bias_along_m) ? to_f(bias[m]) : 0.f;
-        const T* ra = rowadd ? rowadd + (long)(m / p.rows_per_img) * p.N + n : nullptr;
-        if (vec) {
-            float rv[8];
-            if (res) {
-#pragma unroll
-                for (int q = 0; q < 8 / EPC; ++q) {
-                    Vec16<T> t = ld16(res + (long)m * p.ldr + n + q * EPC);
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) rv[q * EPC + e] = to_f(t.e[e]);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float x = v[e] + bv[e] + bm;
-                if (ra) x += to_f(ra[e]);
-                x *= p.alpha;
-                if (res) x += rv[e];
-                v[e] = x;
-            }
-#pragma unroll
-            for (int q = 0; q < 8 / EPC; ++q) {
-                Vec16<T> o;
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) o.e[e] = from_f<T>(v[q * EPC + e]);
-                st16(out + ((long)m + (p.out_seg > 0 ? (long)(m / p.out_seg) * p.out_seg : 0L)) * p.ldo + n + q * EPC, o);
-                if (stats) {
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) {   // statistics of what GroupNorm will read back: the rounded value
-                        const float xr = to_f(o.e[e]);
-                        const float d = xr - s_mean[q * EPC + e];
-                        s_mean[q * EPC + e] += d * (1.0f / (float)(pass + 1));
-                        s_m2[q * EPC + e] += d * (xr - s_mean[q * EPC + e]);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if (e < nv) {
-                    float x = v[e] + bv[e] + bm;
-                    if (ra) x += to_f(ra[e]);
-                    x *= p.alpha;
-                    if (res) x += to_f(res[(long)m * p.ldr + n + e]);
-                    out[((long)m + (p.out_seg > 0 ? (long)(m / p.out_seg) * p.out_seg : 0L)) * p.ldo + n + e] = from_f<T>(x);
-                }
-            }
-        }
-    }
-    }
-    if (stats) {   // uniform branch
-        // lanes l, l^16, l^32, l^48 own the same 8 columns (rbase differs): butterfly-merge equal-count triples
-        float cnt = (float)NPASS;
-#pragma unroll
-        for (int off = 16; off <= 32; off <<= 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float om = __shfl_xor(s_mean[e], off, 64), o2 = __shfl_xor(s_m2[e], off, 64);
-                const float dlt = om - s_mean[e];
-                s_m2[e] = s_m2[e] + o2 + dlt * dlt * cnt * 0.5f;
-                s_mean[e] = 0.5f * (s_mean[e] + om);
-            }
-            cnt *= 2.0f;
-        }
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane < 16) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                gst[((wv * 16 + lane) * 8 + e) * 2] = s_mean[e];
-                gst[((wv * 16 + lane) * 8 + e) * 2 + 1] = s_m2[e];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < BN_ && n0 + (int)threadIdx.x < p.N) {   // one thread per column: merge the waves (4*NPASS rows each)
-            const int c = threadIdx.x;
-            float mean = gst[((0 * 16 + c / 8) * 8 + (c & 7)) * 2], m2 = gst[((0 * 16 + c / 8) * 8 + (c & 7)) * 2 + 1];
-            float na = 4.0f * NPASS;
-            const float nb = 4.0f * NPASS;
-#pragma unroll
-            for (int w = 1; w < NWV; ++w) {
-                const float om = gst[((w * 16 + c / 8) * 8 + (c & 7)) * 2], o2 = gst[((w * 16 + c / 8) * 8 + (c & 7)) * 2 + 1];
-                const float dlt = om - mean, nt = na + nb;
-                mean += dlt * (nb / nt);
-                m2 += o2 + dlt * dlt * na * (nb / nt);
-                na = nt;
-            }
-            const int img = m0 / p.rows_per_img;
-            const int slab = (m0 - img * p.rows_per_img) / BM_;
-            float* o = p.gn_partial + (((long)img * p.gn_nslabs + slab) * p.N + n0 + c) * 3;
-            o[0] = na; o[1] = mean; o[2] = m2;
-        }
-    }
-}
-
 // ---- host side: one planner for the family (definitions and the dispatch order: igemm.hip) ---------------------------------------------------------------
 // Eligibility tests READ the parameter block and fill a TilePlan; only the launcher that takes the launch applies the plan to the block it launches.
 struct TilePlan { int grid; long total; int mtiles, ntiles, gn_nslabs; };
@@ -388,7 +75,7 @@ int persistent_grid();
 // the common tail of the persistent kernels' tests: bm x bn tiles on `grid` workgroups, at least min_tiles4 / 4 of them (the caller's bar), tile and row indices within
 // the kernels' float-reciprocal splits (quotients below 2^22), one statistics slab per M tile
 bool plan_tiles(const IgemmParams& p, int nz, int bm, int bn, int grid, long min_tiles4, TilePlan& t);
-// the 16-bit vector epilogue (igemm_persistent_epilogue.inc): whole 16-byte units of output, residual and bias
+// the 16-bit vector epilogues of the persistent kernels (igemm_epilogue.h): whole 16-byte units of output, residual and bias
 inline bool vec_epilogue_ok(const IgemmParams& p) {
     return p.N % 8 == 0 && p.ldo % 8 == 0 && al16(p.out) && (!p.residual || (p.ldr % 8 == 0 && al16(p.residual))) && (!p.bias || al16(p.bias));
 }

@@ -16,7 +16,7 @@
 //   * DMA pieces are issued between the MFMA groups, fragments are fetched two groups ahead of their MFMAs.
 // Two geometries (NW = waves per workgroup, wave tile always 64x64 = 2x2 MFMA 32x32, BN = 128):
 //   NW = 8: 256x128 tile, 3-stage ring, one workgroup per CU;   NW = 4: 128x128 tile, 2 stages, two workgroups per CU.
-#include "igemm.h"
+#include "igemm_epilogue.h"
 #include <type_traits>
 
 namespace e2eft {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
         }
     }
 
-    // ---- epilogue: LDS-staged, vectorised (igemm.h) ----
+    // ---- epilogue: LDS-staged, vectorised (igemm_epilogue.h) ----
     E2EFT_STAMP(2);
     igemm_epilogue<T, BM2, BN2, NW * 64>(p, smem, acc, wm, wn, l31, h, m0, n0, zo, zi);
     E2EFT_STAMP(4);
@@ -436,8 +436,8 @@ __global__ __launch_bounds__(NW * 64) void igemm2_kernel(const IgemmParams p) {
 template <typename T, int MODE, int NW> static int launch2(IgemmParams& p, int nz, hipStream_t s) {
     p.mtiles = cdiv(p.M, Geo<NW>::BM);
     p.ntiles = cdiv(p.N, BN2);
-    if (p.gn_partial) {   // statistics need whole tiles inside one image and the vector epilogue
-        const bool ok = nz == 1 && p.rows_per_img % Geo<NW>::BM == 0 && p.M % p.rows_per_img == 0 && p.N % 8 == 0 &&
+    if (p.gn_partial) {   // statistics need whole tiles inside one image and the vector epilogue: the full-tile path of igemm_epilogue_rows, the only one that emits them
+        const bool ok = nz == 1 && !(p.bias && p.bias_along_m) && p.rows_per_img % Geo<NW>::BM == 0 && p.M % p.rows_per_img == 0 && p.N % 8 == 0 &&
                         p.ldo % (16 / (int)sizeof(T)) == 0 && al16(p.out) &&
                         (!p.residual || (p.ldr % (16 / (int)sizeof(T)) == 0 && al16(p.residual)));
         if (ok) p.gn_nslabs = p.rows_per_img / Geo<NW>::BM;

@@ -36,7 +36,7 @@
 // 1400 W package power cap that is +6 % wall time on conv 128->128 @768^2, +14 % with a residual, +1-3 % at K >= 2304.  Tried and not
 // kept: a 4th fragment slot requested across the barrier, row-table reads one MFMA group early, statistics merge under the next tile's
 // MFMAs, a register-only (operand-swapped) epilogue for GEMM tiles, tap offsets after the fragment requests.
-#include "igemm.h"
+#include "igemm_epilogue.h"
 #include <atomic>
 #include <type_traits>
 
@@ -63,7 +63,7 @@ static __device__ long long g_stamps5[512 * 32 * 8];
 // RES: the launch has a residual operand (fp32 sliced epilogue); otherwise the packed epilogue — one of the two per instantiation, for the register budget
 // F32O (round 6, csrc/f32split.hip): an fp32 convolution / GEMM whose products are formed on the f16 matrix pipe.  A holds the two f16 planes [x0 | x1] of an fp32 operand
 // side by side (split_c columns each), the weights arrive as [w0 | w1 | w0] per tap, K runs over the three blocks (x0, w0), (x0, w1), (x1, w0): the A offset walks
-// split_c columns, starts over, then walks on into the second plane.  Bias / residual / output are fp32 (epilogue_f32 of the .inc).
+// split_c columns, starts over, then walks on into the second plane.  Bias / residual / output are fp32 (epilogue_f32).
 template <typename T, int MODE, bool RES, bool F32O = false>
 __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const int total_tiles) {
     using namespace pers;
@@ -72,7 +72,6 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     constexpr int EPC = 8;                 // elements per 16 bytes
     constexpr int BK = 64;
     constexpr int RSTEP = 8 * NW;          // row distance between a wave's consecutive DMA pieces
-    typedef float f2 __attribute__((ext_vector_type(2)));
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -301,12 +300,11 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
 
     // ---- epilogue operands requested ahead of their use
     const int er = lane >> 3, ec = lane & 7;          // row inside an 8-row slice, 8-column chunk inside the wave's 64 columns
+    constexpr EpiKind EK = F32O ? EPI_F32 : RES ? EPI_ROWS : EPI_PACKED;      // (F32O requests its fp32 bias / residual inside epilogue_f32)
     const T* __restrict__ bias = (const T*)p.bias;
     const T* __restrict__ rowadd = (const T*)p.rowadd;
-    constexpr bool has_res = RES && !F32O;            // (F32O requests its fp32 bias / residual inside epilogue_f32)
     const bool has_ra = rowadd != nullptr, stats = p.gn_partial != nullptr;
-    Vec16<T> pre_res[4], pre_bias, pre_ra;            // residual rows of slices 0-3, bias and rowadd chunk of this lane
-    T col_bias[2], col_ra[2];                          // packed epilogue (no residual): bias / rowadd of the two COLUMNS this lane owns in the accumulator layout
+    EpiOperands<T, false> ops;
     long c_orow = 0, c_rrow = 0;                       // element offsets of this lane's first output / residual row in the MFMA-side tile
     int c_m0 = 0, c_n0 = 0, c_img = 0, c_ncl = 0;
     int c_mb = 0, c_seg0 = 0;                          // first GEMM row of this wave's 64-row block and (p.out_seg > 0) the output segment it starts in
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
     // every LDS read of k-tile g has been requested by then, and the barrier skew of the eight waves disappears under 8 MFMAs (igemm2's
     // unrolled loop gets the same placement from the compiler's scheduler; a rolled loop has to spell it out).  nextwait: 0 none,
     // 2 vmcnt(6), 3 vmcnt(6 + NPRE) with NPRE = the operand requests issued at the top of a KIND-1 k-tile.
-    const int npre = F32O ? 0 : has_res ? 4 + (bias ? 1 : 0) + (has_ra ? 1 : 0) : 2 * ((bias ? 1 : 0) + (has_ra ? 1 : 0));
+    const int npre = ops.template vmem_count<EK>(bias != nullptr, has_ra);
     bool nxt = false;                                  // the workgroup has a tile after the current one (set at the top of a tile)
     long zoff_o = 0;
     auto enter_tile = [&]() {   // the MFMA side enters the tile the loader is (still) on; then the loader's coordinates move to the workgroup's next tile
@@ -370,19 +368,8 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (KIND == 3) enter_tile();   // index arithmetic of this tile's epilogue and of the next tile: under the first MFMAs
         if constexpr (KIND == 1) {
-            // every lane requests (columns beyond N read the tile's first chunk instead: the count of VMEM instructions must not depend on exec)
-            if constexpr (F32O) {
-            } else if (has_res) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) pre_res[s] = ld16((const T*)p.residual + c_rrow + (long)(s * 8) * p.ldr);
-                if (bias) pre_bias = ld16(bias + c_ncl);
-                if (has_ra) pre_ra = ld16(rowadd + (long)c_img * p.N + c_ncl);
-            } else {   // packed epilogue: two column scalars per operand (columns beyond N read the tile's first column: unused, but the count stays)
-                const int cA = c_n0 + wn * 64 + l31, cB = cA + 32;
-                const int nA = cA < p.N ? cA : c_n0, nB = cB < p.N ? cB : c_n0;
-                if (bias) { col_bias[0] = bias[nA]; col_bias[1] = bias[nB]; }
-                if (has_ra) { col_ra[0] = rowadd[(long)c_img * p.N + nA]; col_ra[1] = rowadd[(long)c_img * p.N + nB]; }
-            }
+            if constexpr (EK == EPI_ROWS) ops.request_rows(p, bias, rowadd, has_ra, c_rrow, c_ncl, c_img);
+            else if constexpr (EK == EPI_PACKED) ops.request_cols(p, bias, rowadd, has_ra, lane, c_n0, c_n0 + wn * 64, c_img);
             u_dma += nslots;
             if (nxt) {
                 finish_setup();
@@ -425,20 +412,10 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         rotate();
     };
 
-    // ---- epilogues and statistics merge: shared with igemm6.hip (rows of a wave's block are consecutive GEMM rows here)
-    // p.out_seg > 0 (e2eft_upconv2x_fwd): row r (a multiple of 8; of 16 in the packed epilogue, out_seg is a multiple of 16) of the block may lie in a later output
-    // segment than row 0 — every segment passed adds out_seg pixel rows (wave-uniform: one float-reciprocal division per slice)
-    auto epi_rows_left = [&]() -> int { return F32O ? p.M - (c_m0 + wm * 64 + er) : 0x40000000; };   // (epilogue_f32: rows of this lane's column of slices that exist)
-    auto epi_rofs = [&](const int r) -> long {
-        if (p.out_seg <= 0) return (long)r;
-        return (long)r + (long)(fast_div(c_mb + r, p.out_seg) - c_seg0) * p.out_seg;
-    };
-    constexpr int EPI_DEP = RING;
-    constexpr bool EPI_M16 = false;      // (the 32x32 accumulator layout)
-    auto epi_srow = [&](const int s) -> int { return 8 * s; };
-#define EPI_STAMP(i) STAMP5(tseq, i)
-#include "igemm_persistent_epilogue.inc"
-#undef EPI_STAMP
+    // ---- epilogues and statistics merge (igemm_epilogue.h): rows of a wave's block are consecutive GEMM rows here, the deposits sit behind the ring
+    const RowsConsecutive rows{p, c_mb, c_seg0};
+    const EpiCtx<T, false, floatx16[2][2], RowsConsecutive> epi{p, smem, acc, ops, rows, wave, lane, l31, h, er, ec, bias, has_ra, stats, c_orow, c_colok};
+    auto stamp = [&](const int i) { STAMP5(tseq, i); (void)i; };
     const float al_f32 = F32O ? p.alpha * (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.alpha_dev2 ? *p.alpha_dev2 : 1.f) : 0.f;
     // ================================ main ==========================================================================
     tile_coords(u_dma);
@@ -462,15 +439,15 @@ __global__ __launch_bounds__(512) void igemm5_kernel(const IgemmParams p, const 
         ktile(IConst<2>{}, 0);    // opens the epilogue: barrier only
         STAMP5(tseq, 2);
         // after the rotation of the last k-tile its stage is s_dst (the next DMA destination): scratch until the next barrier
-        if constexpr (F32O) epilogue_f32(s_dst, al_f32);
-        else if constexpr (RES) epilogue(s_dst, zoff_o);
-        else epilogue_packed(s_dst, zoff_o);
+        if constexpr (EK == EPI_F32) epilogue_f32<RING>(epi, s_dst, al_f32, c_rrow, c_ncl);
+        else if constexpr (EK == EPI_ROWS) epilogue<RING>(epi, s_dst, zoff_o, c_rrow, stamp);
+        else epilogue_packed<RING>(epi, s_dst, zoff_o);
         STAMP5(tseq, 3);
         ++tseq;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // statistics deposits written; every slice window read
         __builtin_amdgcn_s_barrier();                        // opens k-tile 0 of the next tile (its pieces landed before slice 4 of every wave)
         asm volatile("" ::: "memory");
-        if (stats) { const int img = c_m0 / p.rows_per_img; combine(img, (c_m0 - img * p.rows_per_img) / BM, c_n0); }
+        if (stats) { const int img = c_m0 / p.rows_per_img; combine(p, reinterpret_cast<const float*>(smem + RING), tid, BN, img, (c_m0 - img * p.rows_per_img) / BM, c_n0); }
         STAMP5(tseq - 1, 7);
         if (dma_done) break;
         first = false;

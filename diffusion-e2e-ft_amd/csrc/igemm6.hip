@@ -35,7 +35,7 @@
 // wall time per shape, the step 88.6 -> 86.5 ms (profiles/mfma_shape_ab.txt).  The fused-norm variants and the fp32-from-splits variant stay on 32x32x16.
 // Summation order: per output element k runs (chunk, tap) instead of (tap, chunk) — fp32 accumulation, results differ from igemm5 in the
 // last bits (documented in include/e2eft.h; deterministic run to run).
-#include "igemm.h"
+#include "igemm_epilogue.h"
 #include <atomic>
 #include <type_traits>
 
@@ -359,20 +359,17 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
 
     // ---- epilogue operands requested ahead of their use (as igemm5)
     const int er = lane >> 3, ec = lane & 7;
+    constexpr EpiKind EK = F32O ? EPI_F32 : RES ? EPI_ROWS : EPI_PACKED;      // (F32O requests its fp32 bias / residual inside epilogue_f32)
     const T* __restrict__ bias = (const T*)p.bias;
     const T* __restrict__ rowadd = (const T*)p.rowadd;
-    constexpr bool has_res = RES && !F32O;      // (F32O requests its fp32 bias / residual inside epilogue_f32)
     const bool has_ra = rowadd != nullptr, stats = p.gn_partial != nullptr;
-    Vec16<T> pre_res[4], pre_bias, pre_ra;
-    T col_bias[M16 ? 4 : 2], col_ra[M16 ? 4 : 2];
+    EpiOperands<T, M16> ops;
     long c_orow = 0, c_rrow = 0;              // element offsets of output / residual pixel (image row 2 wm of the tile, column er) at this lane's chunk
     int c_n0 = 0, c_img = 0, c_mt = 0, c_ncl = 0;
     bool c_colok = false;
-    const int npre = F32O ? 0 : has_res ? 4 + (bias ? 1 : 0) + (has_ra ? 1 : 0) : (M16 ? 4 : 2) * ((bias ? 1 : 0) + (has_ra ? 1 : 0));
-    // M16 with a residual: slice s of the fp32-window epilogue holds rows 4 (er >> 1) + (er & 1) + epi_srow(s) of the wave's block (igemm_persistent_epilogue.inc)
+    const int npre = ops.template vmem_count<EK>(bias != nullptr, has_ra);   // VMEM instructions of the operand request in the tile's last-but-one k-tile
+    // M16 with a residual: slice s of the fp32-window epilogue holds rows 4 (er >> 1) + (er & 1) + epi_srow(s) of the wave's block (igemm_epilogue.h)
     const int er_row = (M16 && RES) ? 4 * (er >> 1) + (er & 1) : er;
-    constexpr bool EPI_M16 = M16;
-    auto epi_srow = [&](const int s) -> int { return M16 ? 16 * (s >> 1) + 2 * (s & 1) : 8 * s; };
     bool nxt = false;
 
     auto enter_tile = [&]() {   // the MFMA side enters the tile the loader is on; then the loader's coordinates move to the workgroup's next tile
@@ -463,26 +460,8 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
             else set_chunk(c + 1);
         }
         if constexpr (CK == 2 && t == NT - 2) {
-            // every lane requests (columns beyond N read the tile's first chunk instead: the count of VMEM instructions must not depend on exec)
-            if constexpr (F32O) {
-            } else if (has_res) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) pre_res[s] = ld16((const T*)p.residual + c_rrow + (long)epi_srow(s) * p.ldr);   // (slices 0-3: the wave's first image row)
-                if (bias) pre_bias = ld16(bias + c_ncl);
-                if (has_ra) pre_ra = ld16(rowadd + (long)c_img * p.N + c_ncl);
-            } else if constexpr (M16) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int cj = c_n0 + wn * 64 + 16 * j + r15, nj = cj < p.N ? cj : c_n0;
-                    if (bias) col_bias[j] = bias[nj];
-                    if (has_ra) col_ra[j] = rowadd[(long)c_img * p.N + nj];
-                }
-            } else {
-                const int cA = c_n0 + wn * 64 + l31, cB = cA + 32;
-                const int nA = cA < p.N ? cA : c_n0, nB = cB < p.N ? cB : c_n0;
-                if (bias) { col_bias[0] = bias[nA]; col_bias[1] = bias[nB]; }
-                if (has_ra) { col_ra[0] = rowadd[(long)c_img * p.N + nA]; col_ra[1] = rowadd[(long)c_img * p.N + nB]; }
-            }
+            if constexpr (EK == EPI_ROWS) ops.request_rows(p, bias, rowadd, has_ra, c_rrow, c_ncl, c_img);   // (slices 0-3: the wave's first image row)
+            else if constexpr (EK == EPI_PACKED) ops.request_cols(p, bias, rowadd, has_ra, lane, c_n0, c_n0 + wn * 64, c_img);
             u_dma += nslots;
             set_b(nxt);
             if (!nxt) dma_done = true;
@@ -528,15 +507,11 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         }
     };
 
-    // ---- epilogues and statistics merge: shared with igemm5.hip; rows of a wave's 64-row block are two image rows of 32 pixels here.
+    // ---- epilogues and statistics merge (igemm_epilogue.h); rows of a wave's 64-row block are two image rows of 32 pixels here.
     // Packed (no residual): rounds of 16 rows = half an image row; fp32 (residual): slices 4-7 = the wave's second image row.
-    auto epi_rofs = [&](const int r) -> long { return (long)(r & 31) + (long)(r >> 5) * Wo; };
-    auto epi_rows_left = [&]() -> int { return 0x40000000; };      // (tiles are whole 8 x 32 blocks of one image)
-    constexpr int EPI_DEP = OFF_DEP;
-#define EPI_STAMP(i) do { } while (0)
-#include "igemm_persistent_epilogue.inc"
-#undef EPI_STAMP
-    const float al_f32 = F32O ? p.alpha * (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.alpha_dev2 ? *p.alpha_dev2 : 1.f) : 0.f;      // (epilogue_f32 of the .inc)
+    const RowsBlock rows{Wo};
+    const EpiCtx<T, M16, decltype(acc), RowsBlock> epi{p, smem, acc, ops, rows, wave, lane, l31, h, er, ec, bias, has_ra, stats, c_orow, c_colok};
+    const float al_f32 = F32O ? p.alpha * (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.alpha_dev2 ? *p.alpha_dev2 : 1.f) : 0.f;      // (epilogue_f32)
     // ================================ main ==========================================================================
     tile_coords(u_dma);
     set_a(true);
@@ -561,13 +536,13 @@ __global__ __launch_bounds__(512) void igemm6_kernel(const IgemmParams p, const 
         for (int c = 1; c < nch - 1; ++c) chunk(IConst<0>{}, c);
         chunk(IConst<2>{}, nch - 1);
         // the patch buffer of the last chunk (pnext after the swap) is scratch until the next tile's second patch is requested
-        if constexpr (F32O) epilogue_f32(pnext, al_f32);
-        else if constexpr (RES) epilogue(pnext, 0L);
-        else epilogue_packed(pnext, 0L);
+        if constexpr (EK == EPI_F32) epilogue_f32<OFF_DEP>(epi, pnext, al_f32, c_rrow, c_ncl);
+        else if constexpr (EK == EPI_ROWS) epilogue<OFF_DEP>(epi, pnext, 0L, c_rrow);
+        else epilogue_packed<OFF_DEP>(epi, pnext, 0L);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // statistics deposits written; every slice window read
         __builtin_amdgcn_s_barrier();                        // opens k-tile 0 of the next tile
         asm volatile("" ::: "memory");
-        if (stats) { const int img = c_mt / tpi; combine(img, c_mt - img * tpi, c_n0); }
+        if (stats) { const int img = c_mt / tpi; combine(p, reinterpret_cast<const float*>(smem + OFF_DEP), tid, BN, img, c_mt - img * tpi, c_n0); }
         if (dma_done) break;
     }
 }

@@ -1,7 +1,7 @@
 """Trace of the host layer: every call ops.py / autograd.py make into libe2eft, argument for argument, over a fixed list of seeded cases.
 
     python scripts/host_trace.py run <package directory> <output directory> [name]      one package (any checkout's `diffusion-e2e-ft_amd/`) -> trace.json, tensors.pt
-    python scripts/host_trace.py compare <output directory A> <output directory B> [report file]
+    python scripts/host_trace.py compare [--other-build] <output directory A> <output directory B> [report file]
 
 `run` loads the package from the directory it is given (not the one next to this script), wraps every function of `_lib.SIGNATURES` on the loaded library and records
 per call: the symbol, every field of a descriptor argument, every scalar, for each pointer null-or-not and its low four bits, the return value, and the kernel symbol
@@ -9,8 +9,11 @@ the library's dispatch picked (`ops._last_kernel()`) after each launch.  ops.TIM
 region are recorded too (no times).  The script sets the library options itself (persistent grid 0 and 8; for fp32 the split-plane route on and off), so a trace does
 not depend on the environment it was started in.  The last leg is `__graft_entry__.smoke()` whole, with the peak of allocated bytes over it.
 
-`compare` wants two traces to be the same JSON, every saved tensor bit-equal and the peaks equal: a refactor of the host layer that changes no library call.  Run the
-two `run`s as fresh processes (each initialises the GPU once)."""
+Every result that is kept is saved, and with it the GroupNorm statistics partials its producer attached (`_e2eft_gn`).
+
+`compare` wants two traces to be the same JSON, every saved tensor bit-equal and the peaks equal: a refactor of the host layer that changes no library call.  With
+--other-build the two libraries may carry different build ids (a refactor of the device code: same calls, same kernels picked, same bits); nothing else may differ.
+Run the two `run`s as fresh processes (each initialises the GPU once)."""
 import ctypes as C
 import json
 import os
@@ -98,6 +101,9 @@ def run(pkg_dir, out_dir, name=None):
                 keep(*t)
             elif t is not None:
                 saved.append(t.detach().float().cpu() if t.dtype == torch.bfloat16 else t.detach().cpu())
+                st = getattr(t, "_e2eft_gn", None)                         # the statistics partials the producer attached: [images, nslabs, C, 3] fp32
+                if st is not None:
+                    saved.append(st.partial.detach().cpu())
 
     def conv_mod(cin, cout, k, stride, dt, frozen=False):
         m = torch.nn.Conv2d(cin, cout, k, stride, k // 2)
@@ -270,7 +276,7 @@ def run(pkg_dir, out_dir, name=None):
     return 0
 
 
-def compare(a_dir, b_dir, report=None):
+def compare(a_dir, b_dir, report=None, other_build=False):
     import torch
     lines, bad = [], 0
     ja, jb = (json.load(open(os.path.join(d, "trace.json"))) for d in (a_dir, b_dir))
@@ -300,9 +306,12 @@ def compare(a_dir, b_dir, report=None):
         bad += 1
     lines.append("tensors: %d / %d saved, %d not bit-equal%s" % (len(ta), len(tb), len(neq), (" (first: #%d)" % neq[0]) if neq else ""))
     if ma["build_id"] != mb["build_id"]:
-        bad += 1
-        lines.append("the two libraries differ")
-    lines.append("differences: %d%s" % (bad, "" if bad else " (the two host layers make the same library calls and compute the same bits)"))
+        if other_build:
+            lines.append("the two libraries differ, as expected (--other-build)")
+        else:
+            bad += 1
+            lines.append("the two libraries differ")
+    lines.append("differences: %d%s" % (bad, "" if bad else " (the two sides make the same library calls, pick the same kernels and compute the same bits)"))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if report:
@@ -315,5 +324,6 @@ if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "run":
         sys.exit(run(*sys.argv[2:5]))
     if len(sys.argv) >= 4 and sys.argv[1] == "compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None))
+        args = [a for a in sys.argv[2:] if a != "--other-build"]
+        sys.exit(compare(args[0], args[1], args[2] if len(args) > 2 else None, other_build="--other-build" in sys.argv))
     sys.exit(__doc__)

@@ -31,12 +31,11 @@ NPAT = 8             # input channels that carry the slab / image pattern
 DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 
 # what the statistics of each producer describe: "pre" = the exact fp32 value before rounding to the output type, "written" = the rounded tensor.  Read from the code:
-# every vector epilogue accumulates x - pivot from the fp32 value it is about to round; only the stand-alone pass (which reads the tensor back) and the generic
-# branch of igemm_epilogue_rows (statistics of to_f(o.e[e]); no launch reaches it with statistics, see test_gn_statistics_gpu.py) describe the rounded tensor.
+# every vector epilogue accumulates x - pivot from the fp32 value it is about to round; only the stand-alone pass (which reads the tensor back) describes the rounded
+# tensor.  (The generic branch of igemm_epilogue_rows emits none: its hosts decline statistics off the full-tile path, see test_gn_statistics_gpu.py.)
 TARGET = {
     "gn_partial_kernel": "written",
     "igemm_epilogue_rows/full (igemm2: conv and GEMM)": "pre",
-    "igemm_epilogue_rows/generic Welford branch": "written",
     "epilogue_packed (igemm5, convin, igemm6; 32x32 and 16x16x32)": "pre",
     "epilogue, fp32 window (igemm5, igemm6; 32x32 and 16x16x32)": "pre",
     "epilogue_f32 (f32split: igemm5, igemm6)": "pre",
@@ -355,7 +354,7 @@ def emu_lanes(x, piv, lanes=8):
 
 
 def emu_welford(x, piv=None):
-    """Welford's update row by row, on x - piv (piv = None: on x itself, from zero — the form of the generic branch of igemm_epilogue_rows; its mean picks up a
+    """Welford's update row by row, on x - piv (piv = None: on x itself, from zero — the form the generic branch of igemm_epilogue_rows once had; its mean picks up a
     rounding of |mean| u / 2 per row, which the mean bar does not allow when |mean| >> n R: test_gn_stats_model_cpu.py pins that)"""
     x = _f(x)
     piv = torch.zeros_like(x[0]) if piv is None else _f(piv)

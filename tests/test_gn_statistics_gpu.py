@@ -17,10 +17,10 @@ One listed case cannot emit statistics: (64, 8, 8, 64 -> 128), several images pe
 image for statistics, so the library declines them there (the consuming GroupNorm runs its own pass); the case asserts exactly that, and the exact output; the
 nearest shape that does emit them, one image per tile (16, 16, 16), is checked in its place as well.
 
-The generic (Welford) branch of igemm_epilogue_rows: with statistics the host (launch2 of igemm2.hip) keeps gn_partial only when rows_per_img is a multiple of the
-tile height and M a multiple of rows_per_img, N % 8 == 0, ldo (and ldr) whole 16-byte units and the bases 16-byte aligned — which is `full` of the epilogue except for
-bias_along_m, and e2eft_gemm_gnstats drops the statistics for bias_along_m while convolutions never set it; split-K launches clear gn_partial.  No launch reaches the
-branch with statistics; test_no_launch_reaches_the_welford_branch pins the three requests that come closest.
+The generic branch of igemm_epilogue_rows emits no statistics (its Welford update of the rounded values is gone): the host (launch2 of igemm2.hip) keeps gn_partial
+only when rows_per_img is a multiple of the tile height and M a multiple of rows_per_img, N % 8 == 0, ldo (and ldr) whole 16-byte units, the bases 16-byte aligned and
+no bias along M — which is `full` of the epilogue; e2eft_gemm_gnstats drops the statistics for bias_along_m as well, convolutions never set it, split-K launches
+clear gn_partial.  test_hosts_decline_statistics_off_the_full_tile_path pins the three requests that come closest.
 
 Measured on the MI355X (worst ratio to the mean bar / the M2 bar): the exact inputs make the epilogues' shifted sums nearly exact — every conv / GEMM producer is below
 0.001 / 0.16 in every type (fp32-window epilogues with a residual 0.11 - 0.16 of the M2 bar, packed ones 0.03 - 0.06); the stand-alone pass 0.15 - 0.47 / 0.0005 - 0.15;
@@ -347,7 +347,7 @@ def test_finalize_with_producer_partials(dev, dt):
 
 
 # ---- the generic branch of igemm_epilogue_rows ------------------------------------------------------------------------------------------------------------------
-def test_no_launch_reaches_the_welford_branch(dev):
+def test_hosts_decline_statistics_off_the_full_tile_path(dev):
     """The three requests that come closest to `stats && !full` are all answered on the host: a ragged M (rows per image no multiple of the tile) and an output
     whose row stride is no whole 16-byte unit lose their statistics, bias_along_m never gets any"""
     from diffusion_e2e_ft_amd import ops

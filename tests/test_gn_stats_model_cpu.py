@@ -131,9 +131,9 @@ def test_standalone_cases_are_separated(shape, dt):
 
 
 def test_welford_from_zero_misses_the_mean_bar_far_from_zero():
-    """the row-by-row Welford update of the generic branch of igemm_epilogue_rows, started at zero on the values themselves: fine for M2, but its running mean is
+    """the row-by-row Welford update the generic branch of igemm_epilogue_rows used to hold (deleted: no launch reached it), started at zero on the values themselves: fine for M2, but its running mean is
     rounded at the size of the mean in every row — on the ladder (|mean| up to 2000, R ~ 5, n = 128) that is several times the mean bar; about a pivot it is not.
-    No launch reaches that branch with statistics (tests/test_gn_statistics_gpu.py); if one ever does, it will not meet the bars as it stands."""
+    Statistics for that branch would need another form: this one does not meet the bars."""
     c = gm.get_conv_case("rows_3x3")
     cols = gm.slab_columns(c["pre"], c["slab_id"], c["nslabs"])
     n, mu, m2, R = gm.triple(cols)

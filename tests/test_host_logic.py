@@ -594,3 +594,19 @@ def test_wgrad_batch_step_limits():
     assert ops._wgrad_batch_step(576 * 576 * 256 * 2, 576 * 576, 32) == 25          # 170 MB per image: 25 images stay below 0xFFFF0000 bytes
     assert ops._wgrad_batch_step(1 << 10, 1 << 22, 32) == 3                         # 2^22 pixels per image: three images stay below 2^24
     assert ops._wgrad_batch_step(1 << 33, 1, 4) == 1 and ops._wgrad_batch_step(0, 0, 4) == 4
+
+
+@pytest.mark.parametrize("header", ["igemm.h", "igemm_epilogue.h"])
+def test_igemm_headers_compile_on_their_own(header, tmp_path):
+    """each header of the implicit-GEMM family is a translation unit by itself: everything its templates name is declared by what it includes (device-side syntax
+    check only, nothing is instantiated or linked)"""
+    import shutil
+    import subprocess
+    from diffusion_e2e_ft_amd import build
+    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
+    if hipcc is None:
+        pytest.skip("hipcc not found")
+    tu = tmp_path / "tu.hip"
+    tu.write_text('#include "%s"\n' % header)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only", "-I", build.CSRC, str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
