@@ -361,8 +361,24 @@ __global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ 
 // sum of squares: finite -> state[0] += 1, coef = {clip factor, 1 - beta1^step, sqrt(1 - beta2^step), 1}; not finite (overflow in a 16-bit
 // forward, NaN input) -> state[1] += 1, coef[3] = 0 and adamw_guarded_kernel leaves parameters AND moments alone.  So a skipped step does not
 // advance the bias correction, the skip is visible to the caller (state[1]), and the host never waits for the device.
+//
+// Where lr and grad_scale come from is the one thing the two entry points differ in: HyperArgs carries them as launch arguments (e2eft_adamw_step_guarded),
+// HyperDev reads them when the kernel runs from a two-float device array {lr, grad_scale} (e2eft_adamw_step_guarded_at: a captured graph then serves every
+// learning rate).  Both kernels are ONE body over that loader, so the two forms cannot drift: the same fp32 values give the same bits.
+struct HyperArgs {
+    float lr_, gscale_;
+    __device__ float lr() const { return lr_; }
+    __device__ float gscale() const { return gscale_; }
+};
+struct HyperDev {
+    const float* h;
+    __device__ float lr() const { return h[0]; }
+    __device__ float gscale() const { return h[1]; }
+};
+
+template <typename Hyper>
 __global__ void adamw_prepare_kernel(long long* __restrict__ state, float* __restrict__ coef, const double* __restrict__ sumsq, float b1, float b2,
-                                     float gscale, float max_norm) {
+                                     Hyper hyper, float max_norm) {
     const double ss = sumsq[0];
     if (!isfinite(ss)) {
         state[1] += 1;
@@ -371,6 +387,7 @@ __global__ void adamw_prepare_kernel(long long* __restrict__ state, float* __res
     }
     const long long step = state[0] + 1;
     state[0] = step;
+    const float gscale = hyper.gscale();
     float clip = gscale;
     if (max_norm > 0.f) clip *= fminf(1.f, max_norm / ((float)sqrt(ss) * gscale + 1e-6f));
     coef[0] = clip;
@@ -379,11 +396,13 @@ __global__ void adamw_prepare_kernel(long long* __restrict__ state, float* __res
     coef[3] = 1.f;
 }
 
+template <typename Hyper>
 __global__ __launch_bounds__(256) void adamw_guarded_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, float lr, float b1, float b2, float eps, float wd,
+                                                            float* __restrict__ v, Hyper hyper, float b1, float b2, float eps, float wd,
                                                             const float* __restrict__ coef) {
     if (coef[3] == 0.f) return;
     const float clip = coef[0], bc1 = coef[1], bc2_sqrt = coef[2];
+    const float lr = hyper.lr();
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float gi = g[i] * clip;
         float pi = p[i];
@@ -607,15 +626,31 @@ extern "C" int e2eft_adamw_step(int64_t n, float* param, const float* grad, floa
     return check_launch("adamw");
 }
 
+template <typename Hyper>
+static int adamw_guarded_launch(const char* what, int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, Hyper hyper, float beta1,
+                                float beta2, float eps, float weight_decay, int64_t* state, float* coef, const double* grad_sumsq, float max_norm, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((adamw_prepare_kernel<Hyper>), dim3(1), dim3(1), 0, s, (long long*)state, coef, grad_sumsq, beta1, beta2, hyper, max_norm);
+    hipLaunchKernelGGL((adamw_guarded_kernel<Hyper>), dim3(grid_for(n)), dim3(256), 0, s, (long)n, param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps,
+                       weight_decay, (const float*)coef);
+    return check_launch(what);
+}
+
 extern "C" int e2eft_adamw_step_guarded(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                                         float eps, float weight_decay, int64_t* state, float* coef, const double* grad_sumsq, float grad_scale,
                                         float max_norm, void* stream) {
     E2EFT_REQUIRE(param && grad && exp_avg && exp_avg_sq && state && coef && grad_sumsq && n > 0, "adamw_guarded: bad args");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adamw_prepare_kernel, dim3(1), dim3(1), 0, s, (long long*)state, coef, grad_sumsq, beta1, beta2, grad_scale, max_norm);
-    hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(n)), dim3(256), 0, s, (long)n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
-                       weight_decay, (const float*)coef);
-    return check_launch("adamw_guarded");
+    return adamw_guarded_launch("adamw_guarded", n, param, grad, exp_avg, exp_avg_sq, HyperArgs{lr, grad_scale}, beta1, beta2, eps, weight_decay, state, coef,
+                                grad_sumsq, max_norm, stream);
+}
+
+extern "C" int e2eft_adamw_step_guarded_at(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* hyper, float beta1,
+                                           float beta2, float eps, float weight_decay, int64_t* state, float* coef, const double* grad_sumsq, float max_norm,
+                                           void* stream) {
+    E2EFT_REQUIRE(param && grad && exp_avg && exp_avg_sq && hyper && state && coef && grad_sumsq && n > 0, "adamw_guarded_at: bad args");
+    E2EFT_REQUIRE(((uintptr_t)hyper & 3) == 0, "adamw_guarded_at: hyper must be a 4-byte aligned float[2]");
+    return adamw_guarded_launch("adamw_guarded_at", n, param, grad, exp_avg, exp_avg_sq, HyperDev{hyper}, beta1, beta2, eps, weight_decay, state, coef,
+                                grad_sumsq, max_norm, stream);
 }
 
 extern "C" int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accumulate, const void* x, void* y, void* stream) {

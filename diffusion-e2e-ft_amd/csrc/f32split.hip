@@ -50,6 +50,14 @@ __global__ __launch_bounds__(256) void absmax_f32_kernel(long pixels, int c, int
     }
 }
 
+// the maxima start from zero.  A kernel, not hipMemsetAsync: in a training step these entry points also run on autograd's backward thread, and under a stream capture
+// begun on another thread (training.CapturedTrainStep) the replayed graph behaved as if it held their kernels but not their memsets — the maxima of one replay leaked
+// into the next
+__global__ __launch_bounds__(256) void clear_words_kernel(int n, unsigned* __restrict__ p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0u;
+}
+
 // power-of-two scale that brings amax into [2^14, 2^15): (s, 1 / s); 1 for an all-zero or non-finite tensor
 __device__ __forceinline__ void split_scale(const unsigned amax_bits, float& s, float& inv) {
     const int ex = (int)((amax_bits >> 23) & 0xffu);        // biased exponent: amax in [2^(ex - 127), 2^(ex - 126))
@@ -208,12 +216,16 @@ static bool f32split_params(const E2eftConvDesc* d, IgemmParams& p) {
 
 using namespace e2eft;
 
+static void clear_words(float* p, int n, hipStream_t s) {
+    hipLaunchKernelGGL(clear_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, reinterpret_cast<unsigned*>(p));
+}
+
 extern "C" int e2eft_f32_split2(const float* x, int64_t pixels, int32_t c, int32_t ldx, void* planes, int32_t ldp, float* scale, void* stream) {
     E2EFT_REQUIRE(x && planes && scale && pixels > 0, "f32_split2: null pointer / empty tensor");
     E2EFT_REQUIRE(c > 0 && c % 8 == 0 && ldx >= c && ldx % 4 == 0 && ldp >= 2 * c && ldp % 8 == 0, "f32_split2: c=%d ldx=%d ldp=%d (c %% 8, ldx %% 4, ldp %% 8, ldp >= 2 c)", c, ldx, ldp);
     E2EFT_REQUIRE(al16(x) && al16(planes) && ((uintptr_t)scale & 3) == 0, "f32_split2: alignment");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2: memset failed");
+    clear_words(scale, 1, s);
     const long units = pixels * (c / 8);
     long nb = (units + 255) / 256;
     const long nbm = nb > 1024 ? 1024 : nb;          // the reduction: few atomics
@@ -232,7 +244,7 @@ extern "C" int e2eft_f32_split_weight(const float* w, int64_t rows, int32_t c, v
     E2EFT_REQUIRE(c > 0 && c % 8 == 0, "f32_split_weight: c=%d must be a multiple of 8", c);
     E2EFT_REQUIRE(al16(w) && al16(w_split) && ((uintptr_t)scale & 3) == 0, "f32_split_weight: alignment");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split_weight: memset failed");
+    clear_words(scale, 1, s);
     const long units = rows * (c / 8);
     long nb = (units + 255) / 256;
     const long nbm = nb > 1024 ? 1024 : nb;
@@ -251,7 +263,7 @@ extern "C" int e2eft_f32_split2_cat(const float* x1, int32_t c1, int32_t ldx1, c
                   "f32_split2_cat: c1=%d c2=%d ldx1=%d ldx2=%d ldp=%d", c1, c2, ldx1, ldx2, ldp);
     E2EFT_REQUIRE(al16(x1) && al16(x2) && al16(planes) && ((uintptr_t)scale & 3) == 0, "f32_split2_cat: alignment");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(scale, 0, sizeof(float), s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2_cat: memset failed");
+    clear_words(scale, 1, s);
     const float* xs[2] = {x1, x2};
     const int cs[2] = {c1, c2}, lds[2] = {ldx1, ldx2};
     for (int i = 0; i < 2; ++i) {      // one maximum over both sources
@@ -280,7 +292,7 @@ extern "C" int e2eft_f32_split2_cols(const float* x1, int32_t c1, int32_t ldx1, 
     E2EFT_REQUIRE(al16(x1) && al16(x2) && al16(planes) && ((uintptr_t)colscale & 3) == 0, "f32_split2_cols: alignment");
     hipStream_t s = (hipStream_t)stream;
     const int ctot = c1 + c2;
-    if (hipMemsetAsync(colscale, 0, sizeof(float) * ctot, s) != hipSuccess) return fail(E2EFT_ERR_LAUNCH, "f32_split2_cols: memset failed");
+    clear_words(colscale, ctot, s);
     const float* xs[2] = {x1, x2};
     const int cs[2] = {c1, c2}, lds[2] = {ldx1, ldx2}, offs[2] = {0, c1};
     // workgroups for `units` work items of `per` columns groups per pixel: at most `cap`, a multiple of what makes gridDim.x * 256 a multiple of `per`

@@ -32,6 +32,10 @@ def conv_nhwc(conv, x, x2=None, up_to=None, rowadd=None, residual=None, alpha=1.
     return F.conv(conv, x, x2=x2, up_to=up_to, rowadd=rowadd, residual=residual, alpha=alpha, pad=pad, gn_stats=gn_stats, norm=norm)
 
 
+PRESERVE_RNG_STATE = True     # torch.utils.checkpoint's RNG stashing; training.CapturedTrainStep switches it off while it captures (reading the device generator's
+                              # state is not allowed inside a stream capture, and the recomputed segments draw no random numbers)
+
+
 def checkpointed(enabled, fn, *args):
     """Activation recompute of one block (the reference: `torch.utils.checkpoint.checkpoint(create_custom_forward(resnet), ...)` inside
     every UNet block when `unet.enable_gradient_checkpointing()` was called, unet_2d_blocks.py:1136-1161, training/train.py:342-343).
@@ -40,7 +44,7 @@ def checkpointed(enabled, fn, *args):
     statistics ride on the tensors as attributes and survive (the block's input / output objects are the same ones)."""
     if enabled and torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
         from torch.utils.checkpoint import checkpoint
-        return checkpoint(fn, *args, use_reentrant=False)
+        return checkpoint(fn, *args, use_reentrant=False, preserve_rng_state=PRESERVE_RNG_STATE)
     return fn(*args)
 
 

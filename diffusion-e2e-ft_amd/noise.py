@@ -9,7 +9,8 @@ Capture: `draw` is a host counter.  `randn_into` / `pyramid_noise_into` pass it 
 captured with — they stay on the eager paths.  `randn_at` is the capture-safe Gaussian draw (`e2eft_randn_fill_at`): the kernel reads `draw` from a one-element
 int64 device tensor that belongs to the graph, and the caller sets it with `set_draw(tensor, gen)` — `fill_(gen.next_draw())`, one launch with the value as a
 kernel argument, no host-to-device copy, no synchronisation — before each replay.  The host counter stays the single source of truth: eager and captured calls on
-one generator interleave and see the sequence they see without capture.  "pyramid" is not captured: its level sizes are fresh host draws of Python's `random`
+one generator interleave and see the sequence they see without capture.  `DrawAt(seed, draw_dev)` is the generator-shaped handle for code that takes a
+`generator=`: `randn_into` on it is `randn_at` (training.CapturedTrainStep).  "pyramid" is not captured: its level sizes are fresh host draws of Python's `random`
 per call, as in the reference, so its launch arguments differ from call to call.
 
 The GeoWizard trainer has a multi-resolution noise of its own (GeoWizard/geowizard/training/train_depth_normal.py:286-296): level sizes shrunk from the original size by
@@ -37,6 +38,18 @@ class DeviceNoise:
         return d
 
 
+class DrawAt(DeviceNoise):
+    """a DeviceNoise whose draw is read ON THE DEVICE: `randn_into` with it is `randn_at(dst, seed, draw_dev)`.  What a captured graph is handed in place of the
+    caller's generator (training.CapturedTrainStep); the caller's generator stays the source of truth and feeds `draw_dev` through `set_draw`."""
+
+    def __init__(self, seed, draw_dev):
+        super().__init__(seed)
+        self.draw_dev = draw_dev
+
+    def next_draw(self):
+        raise RuntimeError("noise.DrawAt holds no host counter: only the Gaussian draw (randn_into) can read its draw on the device")
+
+
 def pyramid_level_sizes(rows, cols, rng=random):
     """the (rows, cols) of every level grid `pipeline.pyramid_noise_like` (training/util/noise.py:8-18) would draw for a [.., rows, cols] latent: one
     `rng.random()` per level in the reference's order (level 0 included, where shrink ** 0 = 1), the shrink cumulative, stopping after the first level
@@ -52,7 +65,9 @@ def pyramid_level_sizes(rows, cols, rng=random):
 
 
 def randn_into(dst_nhwc_slice, gen):
-    """standard normals into an NHWC view [B,H,W,C] (e.g. `xin[..., 4:]`); advances `gen.draw`"""
+    """standard normals into an NHWC view [B,H,W,C] (e.g. `xin[..., 4:]`); advances `gen.draw` (a `DrawAt` reads its draw on the device instead)"""
+    if isinstance(gen, DrawAt):
+        return randn_at(dst_nhwc_slice, gen.seed, gen.draw_dev)
     return ops.randn_fill_(dst_nhwc_slice, gen.seed, gen.next_draw(), slot=0)
 
 

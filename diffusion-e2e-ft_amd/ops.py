@@ -1623,6 +1623,20 @@ def adamw_step_guarded_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
     return param
 
 
+def adamw_step_guarded_at_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2, eps, weight_decay, state, coef, grad_sumsq, max_norm=0.0):
+    """`adamw_step_guarded_` with lr and grad_scale read when the kernels run from `hyper`, a two-element fp32 DEVICE tensor {lr, grad_scale}: the capture-safe
+    form — a replayed graph steps with what the tensor holds at replay time.  Same fp32 values -> the bits of `adamw_step_guarded_`."""
+    _check_cuda(param, grad, exp_avg, exp_avg_sq, hyper, state, coef, grad_sumsq)
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel()
+    if hyper.dtype != torch.float32 or hyper.numel() != 2 or not hyper.is_contiguous():
+        raise TypeError("adamw_step_guarded_at_: hyper must be a contiguous two-element fp32 tensor {lr, grad_scale}, got %s %s" % (hyper.dtype, tuple(hyper.shape)))
+    assert state.dtype == torch.int64 and state.numel() == 2 and coef.dtype == torch.float32 and coef.numel() == 4 and grad_sumsq.dtype == torch.float64
+    check(_lib.load().e2eft_adamw_step_guarded_at(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(hyper), beta1, beta2, eps,
+                                                  weight_decay, _ptr(state), _ptr(coef), _ptr(grad_sumsq), max_norm, _stream()))
+    return param
+
+
 def ema_step_(shadow, param, one_minus_decay):
     """shadow -= one_minus_decay * (shadow - param) over flat fp32 buffers (diffusers EMAModel.step; csrc/bwd.hip ema_kernel)"""
     _check_cuda(shadow, param)

@@ -76,7 +76,8 @@ def e2e_ft_loss(unet, vae, batch, empty_encoding, modality="depth", noise_schedu
     noise_type (train.py:483-499): "zeros" (default: the zeros latent, x0 = c * model_pred), "gaussian" / "pyramid" (drawn on the device by
     `generator`, a noise.DeviceNoise, straight into channels 4:8 of the UNet input; x0 by the scheduler's prediction_type from that x_t), None
     (a 4-channel UNet fed the rgb latent alone).  noise: an explicit x_t [b,4,h,w] instead of a drawn one (tests, reproducibility across devices).
-    The drawn settings are not capture-safe (noise.py): a replayed graph repeats its noise."""
+    The drawn settings are not capture-safe (noise.py): a replayed graph repeats its noise — except "gaussian" with a `noise.DrawAt` generator, whose draw is read
+    on the device (what CapturedTrainStep hands in)."""
     if noise_type not in NOISE_TYPES:
         raise ValueError("Unknown noise type %s" % noise_type)
     core = getattr(unet, "module", unet)
@@ -146,8 +147,23 @@ def _e2e_ft_loss(unet, core, vae, batch, empty_encoding, modality, noise_schedul
 
 
 def geowizard_class_embedding(batch, domain, dtype, device):
-    """hybrid switcher + domain class, rows [depth (b); normal (b)]  (train_depth_normal.py:684-700)"""
-    geo = torch.tensor([[0.0, 1.0], [1.0, 0.0]], dtype=torch.float32, device=device).repeat_interleave(batch, 0)
+    """hybrid switcher + domain class, rows [depth (b); normal (b)]  (train_depth_normal.py:684-700).  A function of its arguments alone: kept per
+    (batch, domain, dtype, device), so that a call inside a stream capture (CapturedTrainStep, after its eager first step) copies nothing from the host.
+    The result is shared: read it, do not write it."""
+    key = (int(batch), domain, dtype, str(device))
+    hit = _CLASS_EMBEDDINGS.get(key)
+    if hit is None:
+        if len(_CLASS_EMBEDDINGS) >= 16:
+            _CLASS_EMBEDDINGS.clear()
+        hit = _CLASS_EMBEDDINGS[key] = _geowizard_class_embedding(batch, domain, dtype, device)
+    return hit
+
+
+_CLASS_EMBEDDINGS = {}
+
+
+def _geowizard_class_embedding(batch, domain, dtype, device):
+    geo =torch.tensor([[0.0, 1.0], [1.0, 0.0]], dtype=torch.float32, device=device).repeat_interleave(batch, 0)
     dom = {"indoor": [1.0, 0.0, 0.0], "outdoor": [0.0, 1.0, 0.0], "object": [0.0, 0.0, 1.0]}[domain]
     dom = torch.tensor([dom], dtype=torch.float32, device=device).repeat(2 * batch, 1)
     return torch.cat([torch.sin(geo), torch.cos(geo), torch.sin(dom), torch.cos(dom)], dim=-1).to(dtype)
@@ -593,10 +609,36 @@ class FlatAdamW(torch.optim.Optimizer):
             ops.adamw_step_guarded_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, float(g["lr"]) * lr_scale, g["betas"][0], g["betas"][1],
                                     g["eps"], g["weight_decay"], self._steps, self._coef, sumsq, grad_scale=grad_scale / self.world,
                                     max_norm=float(self.max_grad_norm or 0.0))
+        self._after_step()
+        return loss
+
+    def _after_step(self):
+        """the host half of `step()`: what the host must know once the device has stepped (also after a replayed graph did, CapturedTrainStep)"""
         self._rearm_exchange()
         self._claimed = [False] * len(self.params)       # a loop that clears gradients with model.zero_grad() instead of ours still gets the sink next step
         F.bump_param_epoch()
-        return loss
+
+    def set_hyper(self, hyper, lr_scale=1.0, grad_scale=1.0):
+        """hyper (fp32 device tensor [2]) <- {lr * lr_scale, grad_scale / world}, each formed in double and rounded ONCE to fp32 as the scalar entry point's
+        `c_float` argument is, written by one small fill launch each: nothing is copied from the host or read back"""
+        import ctypes
+        hyper[0:1].fill_(ctypes.c_float(float(self.param_groups[0]["lr"]) * lr_scale).value)
+        hyper[1:2].fill_(ctypes.c_float(grad_scale / self.world).value)
+        return hyper
+
+    @torch.no_grad()
+    def step_at(self, hyper):
+        """The DEVICE half of `step()` for one process, with lr and grad_scale read on the device from `hyper` (`set_hyper`): adopt, `sumsq`, and
+        `e2eft_adamw_step_guarded_at` — bit for bit the update of `step()` for the same fp32 values.  Capture-safe; the caller does the host half
+        (`_after_step`) once per executed step, i.e. also after every replay."""
+        if self.world != 1:
+            raise NotImplementedError("FlatAdamW.step_at: the gradient exchange is not part of it (world size %d)" % self.world)
+        with ops.on_device_of(self.flat_param):
+            self._adopt_grads()
+            g = self.param_groups[0]
+            sumsq = ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws)
+            ops.adamw_step_guarded_at_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, hyper, g["betas"][0], g["betas"][1], g["eps"],
+                                       g["weight_decay"], self._steps, self._coef, sumsq, max_norm=float(self.max_grad_norm or 0.0))
 
     def grad_norm(self):
         """global L2 norm of the (averaged) gradient — host value, synchronises.  With world > 1 and `sync_grads` this completes the exchange (each slice
@@ -821,6 +863,196 @@ def train_step(unet, vae, optimizer, batches, empty_encoding, modality="depth", 
     optimizer.step(lr_scale=lr_scale)
     optimizer.zero_grad()
     return total / n
+
+
+class CapturedTrainStep:
+    """`train_step` replayed from hipGraphs: `step = CapturedTrainStep(unet, vae, optimizer, empty_encoding, modality, ...)`, then
+    `step(batches, lr_scale=1.0)` is one optimizer step over `len(batches) == accumulation` micro-batches followed by `zero_grad`, and returns the mean micro-loss
+    as a device tensor — `train_step`'s contract, and its results bit for bit.  `CapturedTrainStep.geowizard(unet, vae, optimizer, domain, depth_scale,
+    normal_scale, ...)` is the same object around `geowizard_e2e_ft_loss`; it is called as `step(batches, lr_scale, imgs_embed=[one [b,1,X] embedding per
+    micro-batch])`.
+
+    Per key — micro-batch shapes and dtypes, modality / loss, noise_type (and the generator's seed, which travels by value), activation recompute, compute dtype,
+    accumulation, the optimizer's by-value hyper-parameters — the FIRST call runs eagerly and is a real step (it fills what the library sizes lazily), the
+    SECOND captures and then replays, later calls only replay.  An entry is up to three graphs over one memory pool:
+      first   micro-step 0: the parameter epoch is bumped before the capture, so every weight derived from the parameters (the 16-bit twin's cast, packed /
+              concatenated / phase weights) is REBUILT inside it, and the gradients are written into the flat buffer;
+      later   micro-steps 1 .. accumulation-1 (absent for accumulation == 1): derived weights reused, gradients accumulated in place;
+      update  `FlatAdamW.step_at`: adopt, `sumsq`, `e2eft_adamw_step_guarded_at`, which reads lr and grad_scale from two device words the host fills before the
+              replay — a scheduler-driven lr and a changing lr_scale need no recapture.
+    The micro-batch is copied into static buffers before each replay (host or device tensors).  After every step, replayed or not, the host does what
+    `FlatAdamW.step()` + `zero_grad()` leave behind: slices re-armed, claims cleared, `.grad` None, the parameter epoch bumped — so an eager forward of the same
+    UNet between steps rebuilds its derived weights from the new parameters, and `state_dict()` / `skipped_steps()` / `step_count` read the device words the
+    graph advanced.  Gradients: the optimizer's own mode (direct_grads: the captured backward kernels write the flat buffer's slots, exactly as eagerly — what the
+    host decides while capturing is what an eager step decides, and the replay repeats its launches).
+
+    noise_type "zeros" / None are captured as they are; "gaussian" needs a `noise.DeviceNoise` and draws through `noise.randn_at`, the draw set before each
+    micro-step's replay (`noise.set_draw`): every micro-step sees what the eager sequence on that generator would have drawn.
+
+    Refused: "pyramid" / "geowizard_pyramid" (their level sizes are host draws, so the launches differ from call to call); a world size above 1 or an optimizer
+    with exchange hooks (RCCL inside a capture is not built); `gather_loss`; the diffusion objective (its timesteps are drawn per step); an EMA inside the step
+    (call `EMAModel.step` after it, eagerly).  A changed frozen VAE, or `unet.to(...)`, needs a new object: graphs bake addresses."""
+
+    MAX_ENTRIES = 4
+
+    def __init__(self, unet, vae, optimizer, empty_encoding=None, modality="depth", noise_type="zeros", generator=None, accumulation=1, gather_loss=False,
+                 ema=None, loss="e2e_ft", domain="indoor", depth_scale=0.5, normal_scale=1.0):
+        from . import noise as N
+        if loss == "diffusion":
+            raise NotImplementedError("CapturedTrainStep: the diffusion objective draws its timesteps per step on the host's generator; it is not captured")
+        if loss not in ("e2e_ft", "geowizard"):
+            raise ValueError("CapturedTrainStep: loss must be 'e2e_ft' or 'geowizard', got %r" % (loss,))
+        if noise_type in ("pyramid", "geowizard_pyramid"):
+            raise ValueError("CapturedTrainStep: noise_type=%r is not captured: its level sizes are fresh host draws per call, so the launches of one step are "
+                             "not the launches of the next; use train_step" % noise_type)
+        if noise_type not in ("zeros", "gaussian") + ((None,) if loss == "e2e_ft" else ()):
+            raise ValueError("Unknown noise type %s" % noise_type)
+        if noise_type == "gaussian" and (not isinstance(generator, N.DeviceNoise) or isinstance(generator, N.DrawAt)):
+            raise TypeError("CapturedTrainStep: noise_type='gaussian' draws on the device: pass generator=noise.DeviceNoise(seed)")
+        if gather_loss:
+            raise NotImplementedError("CapturedTrainStep: gather_loss is a collective per micro-step; RCCL inside a capture is not built")
+        if ema is not None:
+            raise NotImplementedError("CapturedTrainStep: the EMA stays an eager call after the step (EMAModel.step)")
+        if not isinstance(optimizer, FlatAdamW):
+            raise TypeError("CapturedTrainStep steps a FlatAdamW (the update it captures is FlatAdamW.step_at)")
+        if getattr(optimizer, "world", 1) != 1 or optimizer._hooks:
+            raise NotImplementedError("CapturedTrainStep: world size %s / gradient-exchange hooks: RCCL inside a capture is not built; use train_step"
+                                      % getattr(optimizer, "world", 1))
+        if loss == "e2e_ft" and empty_encoding is None:
+            raise ValueError("CapturedTrainStep: empty_encoding is required")
+        if int(accumulation) < 1:
+            raise ValueError("CapturedTrainStep: accumulation must be >= 1")
+        self.unet, self.vae, self.optimizer = unet, vae, optimizer
+        self.empty_encoding, self.modality, self.noise_type, self.generator = empty_encoding, modality, noise_type, generator
+        self.accumulation, self.loss = int(accumulation), loss
+        self.domain, self.depth_scale, self.normal_scale = domain, depth_scale, normal_scale
+        self._entries = {}
+        with ops.on_device_of(optimizer.flat_param):
+            self._hyper = torch.zeros(2, dtype=torch.float32, device=optimizer.flat_param.device)
+
+    @classmethod
+    def geowizard(cls, unet, vae, optimizer, domain="indoor", depth_scale=0.5, normal_scale=1.0, noise_type="zeros", generator=None, accumulation=1, **kw):
+        """the same step around `geowizard_e2e_ft_loss`; call it as `step(batches, lr_scale, imgs_embed=[...])`"""
+        return cls(unet, vae, optimizer, None, None, noise_type, generator, accumulation, loss="geowizard", domain=domain, depth_scale=depth_scale,
+                   normal_scale=normal_scale, **kw)
+
+    # ---- one entry: static buffers + graphs.  Data only — no bound method, no closure over self (a cycle would hand the graphs to the cyclic collector, and a
+    # graph destroyed inside a later capture aborts the process; pipeline._dn_entry) -------------------------------------------------------------------------
+    def _fields(self):
+        if self.loss == "geowizard":
+            return ("rgb", "val_mask", "metric", "normals")
+        return ("rgb", "val_mask", "metric" if self.modality == "depth" else "normals")
+
+    def _mode_key(self):
+        """the part of the key that does not depend on the micro-batch (read once per call: the recompute flag walks the modules)"""
+        core = getattr(self.unet, "module", self.unet)
+        recompute = core.training and any(getattr(m, "gradient_checkpointing", False) for net in (core, self.vae) for m in net.modules())
+        g = self.optimizer.param_groups[0]
+        return (self.loss, self.modality, self.domain, self.depth_scale, self.normal_scale, self.noise_type,
+                self.generator.seed if self.noise_type == "gaussian" else None, bool(recompute), getattr(core, "compute_dtype", core.dtype), self.accumulation,
+                tuple(g["betas"]), g["eps"], g["weight_decay"], float(self.optimizer.max_grad_norm or 0.0), self.optimizer.direct_grads)
+
+    def _batch_key(self, batch, embed):
+        return (tuple((k, tuple(batch[k].shape), batch[k].dtype) for k in self._fields()), None if embed is None else (tuple(embed.shape), embed.dtype))
+
+    def _new_entry(self, batch, embed):
+        from . import noise as N
+        core = getattr(self.unet, "module", self.unet)
+        dev, dt = core.device, getattr(core, "compute_dtype", core.dtype)
+        ent = {"batch": {k: torch.empty(batch[k].shape, dtype=batch[k].dtype, device=dev) for k in self._fields()},
+               "embed": None if embed is None else torch.empty(embed.shape, dtype=embed.dtype, device=dev),
+               "ctx": None if self.empty_encoding is None else self.empty_encoding.detach().to(device=dev, dtype=dt),
+               "total": torch.zeros((), dtype=torch.float32, device=dev), "draw": torch.zeros(1, dtype=torch.int64, device=dev), "graphs": None, "alive": None}
+        ent["gen"] = N.DrawAt(self.generator.seed, ent["draw"]) if self.noise_type == "gaussian" else None
+        return ent
+
+    def _micro(self, ent, first):
+        """one micro-step on the entry's static buffers: `train_step`'s loop body.  Only device work on the current stream."""
+        if self.loss == "geowizard":
+            loss = geowizard_e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["embed"], self.domain, self.depth_scale, self.normal_scale,
+                                         noise_type=self.noise_type, generator=ent["gen"])
+        else:
+            loss = e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["ctx"], self.modality, noise_type=self.noise_type, generator=ent["gen"])
+        (loss / self.accumulation).backward()
+        if first:
+            ent["total"].copy_(loss.detach())
+        else:
+            ent["total"].add_(loss.detach())
+
+    def _capture(self, ent):
+        from . import modules as M
+        opt = self.optimizer
+        if self.loss == "geowizard":      # what the captured forward reads in place must exist before the capture and outlive it
+            core = getattr(self.unet, "module", self.unet)
+            ent["alive"] = geowizard_class_embedding(ent["batch"]["rgb"].shape[0], self.domain, getattr(core, "compute_dtype", core.dtype), core.device)
+        F.bump_param_epoch()              # every derived weight misses its cache: its builder's launches become part of the first graph
+        torch.cuda.synchronize()
+        pool = torch.cuda.graph_pool_handle()
+        graphs = {"first": torch.cuda.CUDAGraph(), "later": torch.cuda.CUDAGraph() if self.accumulation > 1 else None, "update": torch.cuda.CUDAGraph()}
+        keep, M.PRESERVE_RNG_STATE = M.PRESERVE_RNG_STATE, False
+        try:
+            with torch.cuda.graph(graphs["first"], pool=pool):
+                self._micro(ent, True)
+            if graphs["later"] is not None:
+                with torch.cuda.graph(graphs["later"], pool=pool):
+                    self._micro(ent, False)
+            with torch.cuda.graph(graphs["update"], pool=pool):
+                opt.step_at(self._hyper)
+        finally:
+            M.PRESERVE_RNG_STATE = keep
+            # nothing captured has run: the host goes back to the state before a step (gradients of the capture are addresses inside the graphs now)
+            opt._after_step()
+            opt.zero_grad()
+        ent["graphs"] = graphs
+
+    def __call__(self, batches, lr_scale=1.0, imgs_embed=None):
+        from . import noise as N
+        n = self.accumulation
+        if len(batches) != n:
+            raise ValueError("CapturedTrainStep: %d micro-batches given, accumulation is %d (the graphs of an entry are one optimizer step)" % (len(batches), n))
+        if self.loss == "geowizard":
+            if imgs_embed is None or len(imgs_embed) != n:
+                raise ValueError("CapturedTrainStep.geowizard: imgs_embed must hold one embedding per micro-batch (%d)" % n)
+        elif imgs_embed is not None:
+            raise ValueError("CapturedTrainStep: imgs_embed belongs to the GeoWizard step")
+        opt = self.optimizer
+        if opt.world != 1 or opt._hooks:
+            raise NotImplementedError("CapturedTrainStep: world size %s / gradient-exchange hooks: RCCL inside a capture is not built" % opt.world)
+        embeds = imgs_embed if imgs_embed is not None else [None] * n
+        keys = [self._batch_key(b, e) for b, e in zip(batches, embeds)]
+        if any(k != keys[0] for k in keys[1:]):
+            raise ValueError("CapturedTrainStep: the micro-batches of one step must share shapes and dtypes")
+        key = keys[0] + self._mode_key()
+        with ops.on_device_of(opt.flat_param):
+            ent = self._entries.get(key)
+            if ent is None:
+                while len(self._entries) >= self.MAX_ENTRIES:          # (released here, outside any capture)
+                    del self._entries[next(iter(self._entries))]
+                ent = self._entries[key] = self._new_entry(batches[0], embeds[0])
+            elif ent["graphs"] is None:
+                self._capture(ent)
+            graphs = ent["graphs"]
+            opt.set_hyper(self._hyper, lr_scale)
+            opt.sync_grads = True
+            for i, (batch, embed) in enumerate(zip(batches, embeds)):
+                for k, t in ent["batch"].items():
+                    t.copy_(batch[k])
+                if embed is not None:
+                    ent["embed"].copy_(embed)
+                if ent["gen"] is not None:
+                    N.set_draw(ent["draw"], self.generator)
+                if graphs is None:
+                    self._micro(ent, i == 0)
+                else:
+                    graphs["first" if i == 0 else "later"].replay()
+            if graphs is None:
+                opt.step_at(self._hyper)
+            else:
+                graphs["update"].replay()
+            opt._after_step()
+            opt._opt_called = True          # (what torch's lr schedulers look at before they warn about a scheduler stepped ahead of its optimizer)
+            opt.zero_grad()
+            return ent["total"] / n
 
 
 def synthetic_batch(batch, height, width, device, seed=0, dtype=torch.float32):

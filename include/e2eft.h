@@ -724,6 +724,14 @@ int e2eft_adamw_step(int64_t n, float* param, const float* grad, float* exp_avg,
 int e2eft_adamw_step_guarded(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                              float beta2, float eps, float weight_decay, int64_t* state, float* coef, const double* grad_sumsq,
                              float grad_scale, float max_norm, void* stream);
+/* e2eft_adamw_step_guarded with lr and grad_scale read WHEN THE KERNELS RUN from hyper = float[2] device words {lr, grad_scale} instead of
+ * launch arguments (the precedent: e2eft_randn_fill_at): a captured graph holding this launch serves every learning rate of a schedule and
+ * every lr_scale; the host writes the two words (one small fill each) before the replay.  The kernels are the scalar entry point's own
+ * body behind a loader for the two values, so for the same fp32 lr / grad_scale every element of param / exp_avg / exp_avg_sq / state /
+ * coef equals the scalar entry point's bit for bit, the skip on a non-finite norm included.  hyper is only read. */
+int e2eft_adamw_step_guarded_at(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* hyper,
+                                float beta1, float beta2, float eps, float weight_decay, int64_t* state, float* coef,
+                                const double* grad_sumsq, float max_norm, void* stream);
 /* y = (accumulate ? y : 0) + x * mul with dtype conversion (fp32 master weights -> 16-bit compute copies, 16-bit gradients
  * accumulated into the fp32 flat gradient buffer) */
 /* Exponential moving average of the parameters (diffusers `EMAModel.step`; GeoWizard/geowizard/training/train_depth_normal.py:352-353,785-786):
