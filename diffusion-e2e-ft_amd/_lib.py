@@ -91,6 +91,12 @@ DIFFUSION_ADD_NOISE, DIFFUSION_VELOCITY = range(2)      # e2eft_diffusion_mix ki
 PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1}    # e2eft_diffusion_desc.prediction (train_depth_normal.py:677-682: anything else is refused)
 
 
+class AdamwGroup(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64)] + [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+ADAMW_MAX_GROUPS = 8                        # E2EFT_ADAMW_MAX_GROUPS
+
 RGB_HWC, RGB_CHW = range(2)                 # e2eft_dsine_rgb_desc.out_layout
 DSINE_RGB_WS_INTS = 6                       # E2EFT_DSINE_RGB_WS_INTS
 
@@ -188,6 +194,8 @@ SIGNATURES = {
     "e2eft_adamw_step": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _P, _F, _F, _P]),
     "e2eft_adamw_step_guarded": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _P, _P, _F, _F, _P]),
     "e2eft_adamw_step_guarded_at": (_I, [_L, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
+    "e2eft_adamw_step_groups": (_I, [_L, _P, _P, _P, _P, C.POINTER(AdamwGroup), _I, _P, _P, _P, _F, _F, _P]),
+    "e2eft_adamw_step_groups_at": (_I, [_L, _P, _P, _P, _P, C.POINTER(AdamwGroup), _I, _P, _P, _P, _P, _F, _P]),
     "e2eft_cast": (_I, [_I, _I, _L, _F, _I, _P, _P, _P]),
     "e2eft_ema_step": (_I, [_L, _P, _P, _F, _P]),
     "e2eft_activation": (_I, [_I, _I, _L, _P, _P, _P]),

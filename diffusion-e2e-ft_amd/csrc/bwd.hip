@@ -330,6 +330,24 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(int nparts, const doub
     block_sums<1>(a, out);
 }
 
+// The per-element arithmetic of EVERY AdamW kernel of this file (adamw_kernel, adamw_guarded_kernel, adamw_groups_kernel): elements first, first + stride, ...
+// below end.  One body, so the forms cannot drift: the same fp32 scalars give the same bits whichever kernel carries them here.
+__device__ __forceinline__ void adamw_elements(long first, long end, long stride, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, float lr, float b1, float b2, float eps, float wd, float clip, float bc1,
+                                               float bc2_sqrt) {
+    for (long i = first; i < end; i += stride) {
+        const float gi = g[i] * clip;
+        float pi = p[i];
+        pi -= lr * wd * pi;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = pi - (lr / bc1) * (mi / denom);
+    }
+}
+
 // torch.optim.AdamW semantics (decoupled decay), gradient pre-scaled by min(1, max_norm / (||g|| + 1e-6)) when sumsq is given
 // (accelerator.clip_grad_norm_, train.py:562-563)
 __global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -343,17 +361,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ 
         const float nrm = (float)sqrt(sumsq[0]) * gscale;
         clip *= fminf(1.f, max_norm / (nrm + 1e-6f));
     }
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * clip;
-        float pi = p[i];
-        pi -= lr * wd * pi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
-    }
+    adamw_elements((long)blockIdx.x * 256 + threadIdx.x, n, (long)gridDim.x * 256, p, g, m, v, lr, b1, b2, eps, wd, clip, bc1, bc2_sqrt);
 }
 
 // Guarded form with the step counter ON THE DEVICE (e2eft_adamw_step_guarded).  state[0] = number of APPLIED steps (the `step` of
@@ -403,17 +411,65 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(long n, float* __res
     if (coef[3] == 0.f) return;
     const float clip = coef[0], bc1 = coef[1], bc2_sqrt = coef[2];
     const float lr = hyper.lr();
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * clip;
-        float pi = p[i];
-        pi -= lr * wd * pi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
+    adamw_elements((long)blockIdx.x * 256 + threadIdx.x, n, (long)gridDim.x * 256, p, g, m, v, lr, b1, b2, eps, wd, clip, bc1, bc2_sqrt);
+}
+
+// Parameter groups (e2eft_adamw_step_groups): up to E2EFT_ADAMW_MAX_GROUPS ranges [begin, end) of the flat buffer, each with its own lr / betas / eps / weight
+// decay, under ONE clip factor, ONE guard and ONE step counter.  The table travels BY VALUE as a launch argument (no copy, no synchronisation, capture-safe).
+// Group g owns the blocks [first_block[g], first_block[g + 1]) of a one-dimensional grid (an empty group owns none), so a block finds its group by at most seven
+// block-uniform comparisons BEFORE the element loop and then grid-strides over its group's range with uniform hyper-parameters: the loop is adamw_elements.
+// coef = {clip, live, then per group (1 - beta1^t, sqrt(1 - beta2^t))}: float[2 + 2 * n_groups].
+struct AdamwGroups {
+    long begin[E2EFT_ADAMW_MAX_GROUPS], end[E2EFT_ADAMW_MAX_GROUPS];
+    float lr[E2EFT_ADAMW_MAX_GROUPS], b1[E2EFT_ADAMW_MAX_GROUPS], b2[E2EFT_ADAMW_MAX_GROUPS], eps[E2EFT_ADAMW_MAX_GROUPS], wd[E2EFT_ADAMW_MAX_GROUPS];
+    unsigned first_block[E2EFT_ADAMW_MAX_GROUPS + 1];
+    int n;
+};
+// where grad_scale and the groups' learning rates come from: the table and a launch argument, or device words {grad_scale, lr[0], ..., lr[n - 1]} (_at)
+struct GroupHyperArgs {
+    float gscale_;
+    __device__ float lr(const AdamwGroups& t, int k) const { return t.lr[k]; }
+    __device__ float gscale() const { return gscale_; }
+};
+struct GroupHyperDev {
+    const float* h;
+    __device__ float lr(const AdamwGroups&, int k) const { return h[1 + k]; }
+    __device__ float gscale() const { return h[0]; }
+};
+
+template <typename Hyper>
+__global__ void adamw_groups_prepare_kernel(long long* __restrict__ state, float* __restrict__ coef, const double* __restrict__ sumsq, AdamwGroups t,
+                                            Hyper hyper, float max_norm) {
+    const double ss = sumsq[0];
+    if (!isfinite(ss)) {
+        state[1] += 1;
+        coef[0] = 0.f; coef[1] = 0.f;
+        for (int k = 0; k < t.n; ++k) { coef[2 + 2 * k] = 1.f; coef[3 + 2 * k] = 1.f; }
+        return;
     }
+    const long long step = state[0] + 1;
+    state[0] = step;
+    const float gscale = hyper.gscale();
+    float clip = gscale;
+    if (max_norm > 0.f) clip *= fminf(1.f, max_norm / ((float)sqrt(ss) * gscale + 1e-6f));
+    coef[0] = clip;
+    coef[1] = 1.f;
+    for (int k = 0; k < t.n; ++k) {
+        coef[2 + 2 * k] = (float)(1.0 - pow((double)t.b1[k], (double)step));
+        coef[3 + 2 * k] = (float)sqrt(1.0 - pow((double)t.b2[k], (double)step));
+    }
+}
+
+template <typename Hyper>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                           AdamwGroups t, Hyper hyper, const float* __restrict__ coef) {
+    if (coef[1] == 0.f) return;
+    int k = 0;
+    for (int j = 1; j < E2EFT_ADAMW_MAX_GROUPS; ++j)
+        if (j < t.n && blockIdx.x >= t.first_block[j]) k = j;      // (first_block ascends; an empty group's interval is empty, so the last match is the owner)
+    const long nb = t.first_block[k + 1] - t.first_block[k];
+    adamw_elements(t.begin[k] + (long)(blockIdx.x - t.first_block[k]) * 256 + threadIdx.x, t.end[k], nb * 256, p, g, m, v, hyper.lr(t, k), t.b1[k], t.b2[k],
+                   t.eps[k], t.wd[k], coef[0], coef[2 + 2 * k], coef[3 + 2 * k]);
 }
 
 template <typename TI, typename TO>
@@ -651,6 +707,60 @@ extern "C" int e2eft_adamw_step_guarded_at(int64_t n, float* param, const float*
     E2EFT_REQUIRE(((uintptr_t)hyper & 3) == 0, "adamw_guarded_at: hyper must be a 4-byte aligned float[2]");
     return adamw_guarded_launch("adamw_guarded_at", n, param, grad, exp_avg, exp_avg_sq, HyperDev{hyper}, beta1, beta2, eps, weight_decay, state, coef,
                                 grad_sumsq, max_norm, stream);
+}
+
+// validates the caller's table and builds the one the kernels carry; nothing here touches the device
+static int adamw_groups_table(const char* what, int64_t n, const e2eft_adamw_group* groups, int32_t n_groups, AdamwGroups* t) {
+    if (!groups) return fail(E2EFT_ERR_BAD_ARG, "%s: null groups", what);
+    if (n_groups < 1 || n_groups > E2EFT_ADAMW_MAX_GROUPS)
+        return fail(E2EFT_ERR_BAD_ARG, "%s: n_groups %d outside 1..%d", what, (int)n_groups, E2EFT_ADAMW_MAX_GROUPS);
+    *t = AdamwGroups{};
+    t->n = n_groups;
+    int64_t last = 0;
+    for (int k = 0; k < n_groups; ++k) {
+        const e2eft_adamw_group& q = groups[k];
+        if (q.begin < 0) return fail(E2EFT_ERR_BAD_ARG, "%s: group %d: begin %lld < 0", what, k, (long long)q.begin);
+        if (q.begin > q.end) return fail(E2EFT_ERR_BAD_ARG, "%s: group %d: begin %lld > end %lld", what, k, (long long)q.begin, (long long)q.end);
+        if (q.begin < last)
+            return fail(E2EFT_ERR_BAD_ARG, "%s: group %d begins at %lld, before the end %lld of the groups ahead of it (ranges must ascend and not overlap)", what,
+                        k, (long long)q.begin, (long long)last);
+        if (q.end > n) return fail(E2EFT_ERR_BAD_ARG, "%s: group %d: end %lld > n %lld", what, k, (long long)q.end, (long long)n);
+        last = q.end;
+        t->begin[k] = (long)q.begin; t->end[k] = (long)q.end;
+        t->lr[k] = q.lr; t->b1[k] = q.beta1; t->b2[k] = q.beta2; t->eps[k] = q.eps; t->wd[k] = q.weight_decay;
+        t->first_block[k + 1] = t->first_block[k] + (q.end > q.begin ? grid_for(q.end - q.begin) : 0u);
+    }
+    return E2EFT_OK;
+}
+
+template <typename Hyper>
+static int adamw_groups_launch(const char* what, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const AdamwGroups& t, Hyper hyper,
+                               int64_t* state, float* coef, const double* grad_sumsq, float max_norm, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((adamw_groups_prepare_kernel<Hyper>), dim3(1), dim3(1), 0, s, (long long*)state, coef, grad_sumsq, t, hyper, max_norm);
+    const unsigned nb = t.first_block[t.n];
+    if (nb > 0)      // every group empty: the step still counts, there is nothing to update
+        hipLaunchKernelGGL((adamw_groups_kernel<Hyper>), dim3(nb), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, t, hyper, (const float*)coef);
+    return check_launch(what);
+}
+
+extern "C" int e2eft_adamw_step_groups(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const e2eft_adamw_group* groups,
+                                       int32_t n_groups, int64_t* state, float* coef, const double* grad_sumsq, float grad_scale, float max_norm,
+                                       void* stream) {
+    E2EFT_REQUIRE(param && grad && exp_avg && exp_avg_sq && state && coef && grad_sumsq && n > 0, "adamw_groups: bad args (null pointer or n <= 0)");
+    AdamwGroups t;
+    if (int rc = adamw_groups_table("adamw_groups", n, groups, n_groups, &t)) return rc;
+    return adamw_groups_launch("adamw_groups", param, grad, exp_avg, exp_avg_sq, t, GroupHyperArgs{grad_scale}, state, coef, grad_sumsq, max_norm, stream);
+}
+
+extern "C" int e2eft_adamw_step_groups_at(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const e2eft_adamw_group* groups,
+                                          int32_t n_groups, const float* hyper, int64_t* state, float* coef, const double* grad_sumsq, float max_norm,
+                                          void* stream) {
+    E2EFT_REQUIRE(param && grad && exp_avg && exp_avg_sq && hyper && state && coef && grad_sumsq && n > 0, "adamw_groups_at: bad args (null pointer or n <= 0)");
+    E2EFT_REQUIRE(((uintptr_t)hyper & 3) == 0, "adamw_groups_at: hyper must be a 4-byte aligned float[1 + n_groups]");
+    AdamwGroups t;
+    if (int rc = adamw_groups_table("adamw_groups_at", n, groups, n_groups, &t)) return rc;
+    return adamw_groups_launch("adamw_groups_at", param, grad, exp_avg, exp_avg_sq, t, GroupHyperDev{hyper}, state, coef, grad_sumsq, max_norm, stream);
 }
 
 extern "C" int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accumulate, const void* x, void* y, void* stream) {

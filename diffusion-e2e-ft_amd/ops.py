@@ -1637,6 +1637,46 @@ def adamw_step_guarded_at_(param, grad, exp_avg, exp_avg_sq, hyper, beta1, beta2
     return param
 
 
+def adamw_groups(groups):
+    """[(begin, end, lr, beta1, beta2, eps, weight_decay), ...] -> the host table `e2eft_adamw_step_groups` reads (a ctypes array of `_lib.AdamwGroup`; a table
+    built once may be passed again and again).  Ranges and counts are checked by the library."""
+    if isinstance(groups, C.Array) and groups._type_ is _lib.AdamwGroup:
+        return groups
+    return (_lib.AdamwGroup * len(groups))(*[_lib.AdamwGroup(int(b), int(e), lr, b1, b2, eps, wd) for b, e, lr, b1, b2, eps, wd in groups])
+
+
+def _check_adamw_groups(param, grad, exp_avg, exp_avg_sq, table, state, coef, grad_sumsq):
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel()
+    assert state.dtype == torch.int64 and state.numel() == 2 and grad_sumsq.dtype == torch.float64
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() >= 2 + 2 * len(table), "coef: fp32 [2 + 2 * n_groups]"
+
+
+def adamw_step_groups_(param, grad, exp_avg, exp_avg_sq, groups, state, coef, grad_sumsq, grad_scale=1.0, max_norm=0.0):
+    """`adamw_step_guarded_` over parameter groups: `groups` = [(begin, end, lr, beta1, beta2, eps, weight_decay), ...] (or `adamw_groups(...)` of it), up to 8
+    ascending ranges of the flat buffers with their own hyper-parameters; one clip factor, one guard, one step counter.  coef: fp32 [2 + 2 * n_groups]."""
+    _check_cuda(param, grad, exp_avg, exp_avg_sq, state, coef, grad_sumsq)
+    table = adamw_groups(groups)
+    _check_adamw_groups(param, grad, exp_avg, exp_avg_sq, table, state, coef, grad_sumsq)
+    check(_lib.load().e2eft_adamw_step_groups(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), table, len(table), _ptr(state),
+                                              _ptr(coef), _ptr(grad_sumsq), grad_scale, max_norm, _stream()))
+    return param
+
+
+def adamw_step_groups_at_(param, grad, exp_avg, exp_avg_sq, groups, hyper, state, coef, grad_sumsq, max_norm=0.0):
+    """`adamw_step_groups_` with grad_scale and every group's lr read when the kernels run from `hyper`, an fp32 DEVICE tensor {grad_scale, lr[0], ...,
+    lr[n_groups - 1]} (the lr of `groups` is ignored): the capture-safe form.  Same fp32 words -> the bits of `adamw_step_groups_`."""
+    _check_cuda(param, grad, exp_avg, exp_avg_sq, hyper, state, coef, grad_sumsq)
+    table = adamw_groups(groups)
+    _check_adamw_groups(param, grad, exp_avg, exp_avg_sq, table, state, coef, grad_sumsq)
+    if hyper.dtype != torch.float32 or hyper.numel() != 1 + len(table) or not hyper.is_contiguous():
+        raise TypeError("adamw_step_groups_at_: hyper must be a contiguous fp32 tensor of 1 + n_groups = %d elements {grad_scale, lr per group}, got %s %s"
+                        % (1 + len(table), hyper.dtype, tuple(hyper.shape)))
+    check(_lib.load().e2eft_adamw_step_groups_at(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), table, len(table), _ptr(hyper),
+                                                 _ptr(state), _ptr(coef), _ptr(grad_sumsq), max_norm, _stream()))
+    return param
+
+
 def ema_step_(shadow, param, one_minus_decay):
     """shadow -= one_minus_decay * (shadow - param) over flat fp32 buffers (diffusers EMAModel.step; csrc/bwd.hip ema_kernel)"""
     _check_cuda(shadow, param)

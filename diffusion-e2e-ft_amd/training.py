@@ -6,6 +6,8 @@
                        buffer: parameters and their .grad are views of two big allocations, so the data-parallel gradient
                        exchange is a handful of large RCCL all-reduces over contiguous slices (no bucket copies), launched
                        from autograd hooks while the rest of the backward is still running, and the update is one launch.
+  GroupedFlatAdamW   — FlatAdamW over up to 8 parameter groups with their own lr / betas / eps / weight decay, still one update launch
+                       (GeoWizard/geowizard/training/train_depth_normal.py:428-444; geowizard_param_groups restates its split)
   IterExponential    — training/util/lr_scheduler.py:10-36
   replace_unet_conv_in — training/util/unet_prep.py:6-20
 
@@ -366,6 +368,12 @@ class FlatAdamW(torch.optim.Optimizer):
             lr, betas, eps, weight_decay = group0.get("lr", lr), group0.get("betas", betas), group0.get("eps", eps), group0.get("weight_decay", weight_decay)
         else:
             plist = [p for p in params if p.requires_grad]
+        self._init_flat(plist, plist, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), max_grad_norm, n_slices, process_group,
+                        external_grad_sync, direct_grads)
+
+    def _init_flat(self, plist, torch_params, defaults, max_grad_norm, n_slices, process_group, external_grad_sync, direct_grads):
+        """everything behind the argument parsing: `plist` in the flat buffer's order, `torch_params` what `torch.optim.Optimizer` is built from (the same list, or
+        GroupedFlatAdamW's group dicts over the same parameters in the same order)"""
         if not plist:
             raise ValueError("no trainable parameters")
         dev = plist[0].device
@@ -374,7 +382,7 @@ class FlatAdamW(torch.optim.Optimizer):
                 raise TypeError("FlatAdamW keeps fp32 master parameters; got %s" % p.dtype)
             if p.device != dev:
                 raise ValueError("FlatAdamW: all parameters must live on one device")
-        super().__init__(plist, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        torch.optim.Optimizer.__init__(self, torch_params, defaults)
         self.params = plist
         self.max_grad_norm = max_grad_norm
         self.offsets, n = [], 0
@@ -618,6 +626,13 @@ class FlatAdamW(torch.optim.Optimizer):
         self._claimed = [False] * len(self.params)       # a loop that clears gradients with model.zero_grad() instead of ours still gets the sink next step
         F.bump_param_epoch()
 
+    hyper_words = 2      # the length of the device tensor `set_hyper` fills and `step_at` reads
+
+    def _capture_key(self):
+        """what a captured `step_at` bakes in by value (CapturedTrainStep's key); the learning rate is not part of it"""
+        g = self.param_groups[0]
+        return (tuple(g["betas"]), g["eps"], g["weight_decay"], float(self.max_grad_norm or 0.0), self.direct_grads)
+
     def set_hyper(self, hyper, lr_scale=1.0, grad_scale=1.0):
         """hyper (fp32 device tensor [2]) <- {lr * lr_scale, grad_scale / world}, each formed in double and rounded ONCE to fp32 as the scalar entry point's
         `c_float` argument is, written by one small fill launch each: nothing is copied from the host or read back"""
@@ -671,6 +686,112 @@ class FlatAdamW(torch.optim.Optimizer):
         for i, (p, o) in enumerate(zip(self.params, self.offsets)):      # autograd may have re-bound .grad (e.g. set_to_none by a caller)
             if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * o:
                 p.grad = self._slot(self.flat_grad, i)
+
+
+class GroupedFlatAdamW(FlatAdamW):
+    """`FlatAdamW` over parameter groups: `GroupedFlatAdamW([{"params": ..., "lr": ...}, {"params": ..., "weight_decay": 0.0}, ...], lr=, betas=, eps=,
+    weight_decay=)` as `torch.optim.AdamW` takes it — GeoWizard's trainer (GeoWizard/geowizard/training/train_depth_normal.py:428-444, see
+    `geowizard_param_groups`), or no weight decay on biases and norm scales.  Up to 8 groups (E2EFT_ADAMW_MAX_GROUPS), each with its own `lr`, `betas`, `eps` and
+    `weight_decay`; what a group leaves out comes from the keyword arguments.
+
+    The flat buffer is laid out group after group, each group's parameters in its own order (torch enumerates them the same way: the indices in
+    `state_dict()["param_groups"][i]["params"]` agree with a `torch.optim.AdamW` built from the same list, and checkpoints load in both directions), so group i is
+    ONE range `group_ranges[i]` of the buffer.  Parameters that do not require a gradient are dropped; a group left empty stays in `param_groups` (scheduler lambdas
+    and checkpoints keep lining up) and owns no elements.  Clip, guard and step counter are the whole buffer's: one `sumsq`, one `e2eft_adamw_step_groups` — the
+    same two launches as `FlatAdamW.step()`, whatever the number of groups.
+
+    `param_groups` is live: `LambdaLR(optimizer, IterExponential(...))` and `get_scheduler("constant", ...)` scale every group from its own base rate;
+    `step(lr_scale=)` multiplies all of them; the `lr` property reads and writes group 0 only.  Everything that hangs on the flat layout — the 16-bit twin, the
+    gradient sink (a q | k | v split across groups is not adjacent and takes the ordinary path), the exchange slices, `grad_norm()`, `EMAModel` — is FlatAdamW's."""
+
+    def __init__(self, params, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, n_slices=4, process_group=None,
+                 external_grad_sync=False, direct_grads=True):
+        from ._lib import ADAMW_MAX_GROUPS
+        params = list(params)
+        if not (params and isinstance(params[0], dict)):
+            params = [{"params": params}]
+        if len(params) > ADAMW_MAX_GROUPS:
+            raise ValueError("GroupedFlatAdamW: %d parameter groups, the update kernel takes at most %d (E2EFT_ADAMW_MAX_GROUPS)" % (len(params), ADAMW_MAX_GROUPS))
+        groups = []
+        for g in params:
+            g = dict(g)
+            g["params"] = [p for p in ([g["params"]] if isinstance(g["params"], torch.Tensor) else g["params"]) if p.requires_grad]
+            if "betas" in g:
+                g["betas"] = tuple(g["betas"])
+            groups.append(g)
+        plist = [p for g in groups for p in g["params"]]
+        self._init_flat(plist, groups, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), max_grad_norm, n_slices, process_group,
+                        external_grad_sync, direct_grads)
+        self.group_ranges, i = [], 0
+        for g in self.param_groups:           # [begin, end) of each group in the flat buffers: its parameters' slots, alignment padding included
+            k = i + len(g["params"])
+            begin = self.offsets[i] if i < len(self.params) else self.numel
+            self.group_ranges.append((begin, self.offsets[k] if k < len(self.params) else self.numel) if k > i else (begin, begin))
+            i = k
+        with ops.on_device_of(self.flat_param):
+            self._coef = torch.zeros(2 + 2 * len(self.param_groups), dtype=torch.float32, device=self.flat_param.device)
+
+    @property
+    def hyper_words(self):
+        return 1 + len(self.param_groups)
+
+    def _table(self, lr_scale=1.0):
+        """the by-value group table of one update, read from the live `param_groups`"""
+        return [(b, e, float(g["lr"]) * lr_scale, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+                for (b, e), g in zip(self.group_ranges, self.param_groups)]
+
+    def _capture_key(self):
+        return (tuple((b, e, tuple(g["betas"]), g["eps"], g["weight_decay"]) for (b, e), g in zip(self.group_ranges, self.param_groups)),
+                float(self.max_grad_norm or 0.0), self.direct_grads)
+
+    @torch.no_grad()
+    def step(self, closure=None, lr_scale=1.0, grad_scale=1.0):
+        """`FlatAdamW.step` with every group's own hyper-parameters: lr of group i = param_groups[i]["lr"] * lr_scale"""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        with ops.on_device_of(self.flat_param):
+            self._adopt_grads()
+            self._finish_exchange()
+            sumsq = ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws)
+            ops.adamw_step_groups_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._table(lr_scale), self._steps, self._coef, sumsq,
+                                   grad_scale=grad_scale / self.world, max_norm=float(self.max_grad_norm or 0.0))
+        self._after_step()
+        return loss
+
+    def set_hyper(self, hyper, lr_scale=1.0, grad_scale=1.0):
+        """hyper (fp32 device tensor [1 + n_groups]) <- {grad_scale / world, lr[0] * lr_scale, ...}, each formed in double and rounded ONCE to fp32 as the by-value
+        entry point's `float` fields are, one small fill launch per word"""
+        import ctypes
+        hyper[0:1].fill_(ctypes.c_float(grad_scale / self.world).value)
+        for i, g in enumerate(self.param_groups):
+            hyper[1 + i:2 + i].fill_(ctypes.c_float(float(g["lr"]) * lr_scale).value)
+        return hyper
+
+    @torch.no_grad()
+    def step_at(self, hyper):
+        """The device half of `step()` with grad_scale and the groups' learning rates read on the device from `hyper` (`set_hyper`): adopt, `sumsq`,
+        `e2eft_adamw_step_groups_at`.  Capture-safe; see `FlatAdamW.step_at`."""
+        if self.world != 1:
+            raise NotImplementedError("GroupedFlatAdamW.step_at: the gradient exchange is not part of it (world size %d)" % self.world)
+        with ops.on_device_of(self.flat_param):
+            self._adopt_grads()
+            sumsq = ops.sumsq(self.flat_grad, out=self._sumsq, ws=self._sumsq_ws)
+            ops.adamw_step_groups_at_(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._table(), hyper, self._steps, self._coef, sumsq,
+                                      max_norm=float(self.max_grad_norm or 0.0))
+
+
+def geowizard_param_groups(unet, learning_rate, class_embedding_lr_mult=10.0):
+    """The two parameter groups of GeoWizard's trainer (GeoWizard/geowizard/training/train_depth_normal.py:428-440): every parameter whose name contains
+    'class_embedding' at `learning_rate * class_embedding_lr_mult` (`--class_embedding_lr_mult`, default 10: the embedding is freshly initialised), everything else
+    at `learning_rate`.  A UNet without a class embedding gives an empty second group, as the reference's loop does.  Pass the list to `GroupedFlatAdamW` (or
+    `torch.optim.AdamW`) with `betas=`, `weight_decay=`, `eps=` as lines 441-443 do.
+    With `--scale_lr` (lines 411-414) pass learning_rate = learning_rate * gradient_accumulation_steps * train_batch_size * num_processes."""
+    params, params_class_embedding = [], []
+    for name, param in unet.named_parameters():
+        (params_class_embedding if "class_embedding" in name else params).append(param)
+    return [{"params": params, "lr": learning_rate}, {"params": params_class_embedding, "lr": learning_rate * class_embedding_lr_mult}]
 
 
 class EMAModel:
@@ -879,7 +1000,8 @@ class CapturedTrainStep:
               concatenated / phase weights) is REBUILT inside it, and the gradients are written into the flat buffer;
       later   micro-steps 1 .. accumulation-1 (absent for accumulation == 1): derived weights reused, gradients accumulated in place;
       update  `FlatAdamW.step_at`: adopt, `sumsq`, `e2eft_adamw_step_guarded_at`, which reads lr and grad_scale from two device words the host fills before the
-              replay — a scheduler-driven lr and a changing lr_scale need no recapture.
+              replay — a scheduler-driven lr and a changing lr_scale need no recapture.  A `GroupedFlatAdamW` is stepped the same way
+              (`e2eft_adamw_step_groups_at`, `optimizer.hyper_words` = 1 + n_groups device words; every group's range, betas, eps and weight decay are in the key).
     The micro-batch is copied into static buffers before each replay (host or device tensors).  After every step, replayed or not, the host does what
     `FlatAdamW.step()` + `zero_grad()` leave behind: slices re-armed, claims cleared, `.grad` None, the parameter epoch bumped — so an eager forward of the same
     UNet between steps rebuilds its derived weights from the new parameters, and `state_dict()` / `skipped_steps()` / `step_count` read the device words the
@@ -928,7 +1050,7 @@ class CapturedTrainStep:
         self.domain, self.depth_scale, self.normal_scale = domain, depth_scale, normal_scale
         self._entries = {}
         with ops.on_device_of(optimizer.flat_param):
-            self._hyper = torch.zeros(2, dtype=torch.float32, device=optimizer.flat_param.device)
+            self._hyper = torch.zeros(optimizer.hyper_words, dtype=torch.float32, device=optimizer.flat_param.device)
 
     @classmethod
     def geowizard(cls, unet, vae, optimizer, domain="indoor", depth_scale=0.5, normal_scale=1.0, noise_type="zeros", generator=None, accumulation=1, **kw):
@@ -947,10 +1069,9 @@ class CapturedTrainStep:
         """the part of the key that does not depend on the micro-batch (read once per call: the recompute flag walks the modules)"""
         core = getattr(self.unet, "module", self.unet)
         recompute = core.training and any(getattr(m, "gradient_checkpointing", False) for net in (core, self.vae) for m in net.modules())
-        g = self.optimizer.param_groups[0]
         return (self.loss, self.modality, self.domain, self.depth_scale, self.normal_scale, self.noise_type,
-                self.generator.seed if self.noise_type == "gaussian" else None, bool(recompute), getattr(core, "compute_dtype", core.dtype), self.accumulation,
-                tuple(g["betas"]), g["eps"], g["weight_decay"], float(self.optimizer.max_grad_norm or 0.0), self.optimizer.direct_grads)
+                self.generator.seed if self.noise_type == "gaussian" else None, bool(recompute), getattr(core, "compute_dtype", core.dtype),
+                self.accumulation) + self.optimizer._capture_key()
 
     def _batch_key(self, batch, embed):
         return (tuple((k, tuple(batch[k].shape), batch[k].dtype) for k in self._fields()), None if embed is None else (tuple(embed.shape), embed.dtype))

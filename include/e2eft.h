@@ -732,6 +732,30 @@ int e2eft_adamw_step_guarded(int64_t n, float* param, const float* grad, float* 
 int e2eft_adamw_step_guarded_at(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* hyper,
                                 float beta1, float beta2, float eps, float weight_decay, int64_t* state, float* coef,
                                 const double* grad_sumsq, float max_norm, void* stream);
+/* Parameter groups: the guarded update over up to E2EFT_ADAMW_MAX_GROUPS ranges of the flat buffer, each with its own learning rate, betas, eps and weight
+ * decay (GeoWizard/geowizard/training/train_depth_normal.py:428-444: the class embedding at ten times the rate; no decay on biases and norm scales).
+ * `groups` is a HOST array of n_groups (1 .. 8) entries, read at call time and carried to the kernels by value as launch arguments: no copy to the device,
+ * no synchronisation, capture-safe.  Ranges [begin, end) ascend and do not overlap, 0 <= begin <= end <= n; an empty range (begin == end) is legal and owns
+ * nothing; elements of [0, n) that lie in no range keep param, exp_avg and exp_avg_sq untouched.
+ * ONE clip factor from the global grad_sumsq, ONE guard (non-finite norm: state[1] += 1, no group changes) and ONE applied-step counter state[0] for all
+ * groups; 1 - beta1^t and sqrt(1 - beta2^t) are formed per group in double and rounded once.  The per-element arithmetic is e2eft_adamw_step_guarded's own
+ * body: a group's elements equal, bit for bit, what that entry point writes there with the group's hyper-parameters and the same grad_sumsq.
+ * coef: float[2 + 2 * n_groups] device scratch = {clip factor, 1 (stepped) or 0 (skipped), then per group (1 - beta1^t, sqrt(1 - beta2^t))}.
+ * One one-thread launch that forms coef and one update launch over all groups; nothing is launched before every argument has been checked. */
+#define E2EFT_ADAMW_MAX_GROUPS 8
+typedef struct e2eft_adamw_group {
+    int64_t begin, end; /* elements [begin, end) of the flat buffers */
+    float lr, beta1, beta2, eps, weight_decay;
+} e2eft_adamw_group;
+int e2eft_adamw_step_groups(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const e2eft_adamw_group* groups,
+                            int32_t n_groups, int64_t* state, float* coef, const double* grad_sumsq, float grad_scale, float max_norm,
+                            void* stream);
+/* The same with grad_scale and every group's lr read WHEN THE KERNELS RUN from hyper = float[1 + n_groups] device words {grad_scale, lr[0], ...,
+ * lr[n_groups - 1]} (4-byte aligned, only read): a captured graph serves every learning rate of every group.  The lr fields of `groups` are ignored.
+ * Same fp32 words -> the bits of e2eft_adamw_step_groups. */
+int e2eft_adamw_step_groups_at(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const e2eft_adamw_group* groups,
+                               int32_t n_groups, const float* hyper, int64_t* state, float* coef, const double* grad_sumsq, float max_norm,
+                               void* stream);
 /* y = (accumulate ? y : 0) + x * mul with dtype conversion (fp32 master weights -> 16-bit compute copies, 16-bit gradients
  * accumulated into the fp32 flat gradient buffer) */
 /* Exponential moving average of the parameters (diffusers `EMAModel.step`; GeoWizard/geowizard/training/train_depth_normal.py:352-353,785-786):
