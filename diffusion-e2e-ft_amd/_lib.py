@@ -198,6 +198,7 @@ SIGNATURES = {
     "e2eft_adamw_step_groups_at": (_I, [_L, _P, _P, _P, _P, C.POINTER(AdamwGroup), _I, _P, _P, _P, _P, _F, _P]),
     "e2eft_cast": (_I, [_I, _I, _L, _F, _I, _P, _P, _P]),
     "e2eft_ema_step": (_I, [_L, _P, _P, _F, _P]),
+    "e2eft_ema_step_at": (_I, [_L, _P, _P, _P, _P]),
     "e2eft_activation": (_I, [_I, _I, _L, _P, _P, _P]),
     "e2eft_masked_quantiles_workspace_bytes": (_Z, [_I]),
     "e2eft_masked_quantiles": (_I, [_I, _L, _P, _F, _F, _F, _F, _P, _P, _Z, _P]),
@@ -235,6 +236,11 @@ SIGNATURES = {
     "e2eft_pyramid_noise_weighted": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _F, _I, C.POINTER(C.c_int32), _P, _F, _P, _P, _Z, _P]),
     "e2eft_latent_x0": (_I, [_I, _L, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "e2eft_randn_fill_at": (_I, [_I, _I, _I, _I, _I, C.c_uint64, _P, C.c_uint32, _P, _P]),
+    "e2eft_pyramid_noise_at": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, _P, _F, _P, _P, _Z, _P]),
+    "e2eft_pyramid_noise_weighted_at": (_I, [_I, _I, _I, _I, _I, _I, C.c_uint64, _P, _F, _P, _F, _P, _P, _Z, _P]),
+    "e2eft_pyramid_table_set": (_I, [_P, C.c_uint32, _I, C.POINTER(C.c_int32), _I, _I, _P]),
+    "e2eft_randint_fill": (_I, [_L, _I, _L, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "e2eft_randint_fill_at": (_I, [_L, _I, _L, C.c_uint64, _P, C.c_uint32, _P, _P]),
     # multi-step inference (csrc/denoise.hip)
     "e2eft_ddim_step": (_I, [_I, _L, _I, _I, _I, _P, _P, _P, _P]),
     # diffusion objective of the GeoWizard trainer (csrc/diffusion.hip)

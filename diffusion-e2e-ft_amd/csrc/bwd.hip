@@ -634,9 +634,11 @@ extern "C" int e2eft_angular_loss_bwd(int32_t batch, int32_t hw, const float* pr
 }
 
 // EMA of the parameters (diffusers EMAModel.step, used by GeoWizard/geowizard/training/train_depth_normal.py:352-353,785-786): shadow -= (1 - decay) * (shadow - param),
-// torch's operation order (sub, mul, sub — no contraction), 16-byte vectors over the flat buffers: 12 B per element, HBM-bound
-__global__ __launch_bounds__(256) void ema_kernel(long n, float* __restrict__ shadow, const float* __restrict__ param, float omd) {
+// torch's operation order (sub, mul, sub — no contraction), 16-byte vectors over the flat buffers: 12 B per element, HBM-bound.
+// omd_at != nullptr (e2eft_ema_step_at): 1 - decay is read from that device word instead of the launch argument — one body, the same bits for the same value
+__global__ __launch_bounds__(256) void ema_kernel(long n, float* __restrict__ shadow, const float* __restrict__ param, float omd, const float* __restrict__ omd_at) {
 #pragma clang fp contract(off)
+    if (omd_at) omd = *omd_at;
     const long n4 = n >> 2;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         float4 s = reinterpret_cast<float4*>(shadow)[i];
@@ -653,8 +655,16 @@ __global__ __launch_bounds__(256) void ema_kernel(long n, float* __restrict__ sh
 extern "C" int e2eft_ema_step(int64_t n, float* shadow, const float* param, float one_minus_decay, void* stream) {
     E2EFT_REQUIRE(shadow && param && n > 0 && (((uintptr_t)shadow | (uintptr_t)param) & 15) == 0, "ema_step: bad args (16-byte aligned fp32 buffers)");
     unsigned nb = grid_for((n + 3) / 4);
-    hipLaunchKernelGGL(ema_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (long)n, shadow, param, one_minus_decay);
+    hipLaunchKernelGGL(ema_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (long)n, shadow, param, one_minus_decay, (const float*)nullptr);
     return check_launch("ema_step");
+}
+
+extern "C" int e2eft_ema_step_at(int64_t n, float* shadow, const float* param, const float* one_minus_decay, void* stream) {
+    E2EFT_REQUIRE(shadow && param && n > 0 && (((uintptr_t)shadow | (uintptr_t)param) & 15) == 0, "ema_step_at: bad args (16-byte aligned fp32 buffers)");
+    E2EFT_REQUIRE(one_minus_decay && ((uintptr_t)one_minus_decay & 3) == 0, "ema_step_at: null or misaligned one_minus_decay");
+    unsigned nb = grid_for((n + 3) / 4);
+    hipLaunchKernelGGL(ema_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (long)n, shadow, param, 0.f, one_minus_decay);
+    return check_launch("ema_step_at");
 }
 
 extern "C" size_t e2eft_sumsq_workspace_bytes(int64_t n) { return n > 0 ? (size_t)(grid_for(n) < SUMSQ_NBLK ? grid_for(n) : SUMSQ_NBLK) * sizeof(double) : 0; }

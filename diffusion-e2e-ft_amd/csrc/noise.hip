@@ -13,7 +13,9 @@
 //   2.4e-4).  Their complement 1 - u = ((2^24 - 1 - x) + 0.5) * 2^-24 is exact there, so for x >= 2^23 the kernel takes ln u = log1p(-(1 - u)) and
 //   cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u)): every u enters the arithmetic exactly.
 //   slot 0 is the base grid of a call, slot 1 + i the grid of pyramid level i; draw is the caller's per-call counter, passed by value — or, by e2eft_randn_fill_at,
-//   read from device memory (the low 32 bits of an int64), which is what a captured graph needs to draw fresh noise on every replay.
+//   read from device memory (the low 32 bits of an int64), which is what a captured graph needs to draw fresh noise on every replay.  The pyramid `_at` entry
+//   points read `draw` AND the level table from int64 device words (e2eft_pyramid_table_set fills them); e2eft_randint_fill[_at] turns the raw word of an element
+//   into an integer of [0, high):  t = ((uint64_t)word * (uint64_t)high) >> 32.
 //
 // Counter-based: any element of any grid is a pure function of (seed, draw, slot, e).  The pyramid kernel therefore evaluates the (at most four) bilinear
 // corners of every level on the fly — no level grid is ever stored — and the result does not depend on the launch geometry.
@@ -169,12 +171,23 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {      // 
 //   acc  = fmaf(w_i * tw_b, up_i, acc)                 w_i = (float)discount^i; ONE fp32 product, then the fused multiply-add of the unweighted form
 // — the CONTRACT of the weight (include/e2eft.h repeats it; tests/geowizard_pyramid_ref.py restates it from that text).  tw_b == 1 gives the unweighted bits,
 // tw_b == 0 leaves the base grid.  The unweighted instantiation never touches `timesteps` and keeps its arithmetic.
+// TABLE (the `_at` entry points): draw, the level count and the level sizes come from `table` = {draw, n_levels, rows_0, cols_0, .., rows_9, cols_9} (int64 device
+// words, uniform loads) instead of `draw` / `lv.n` / `lv.rows` / `lv.cols`; the weights stay lv.weight (all ten are formed on the host: they do not depend on the
+// table).  The host cannot see those words, so they are clamped here — n into [0, MAX_LEVELS], level rows into [1, rows], level cols into [1, cols] — and a stale
+// table can overflow neither the level arrays nor the int index arithmetic (lr * lc <= rows * cols).  One body: the same values give the by-value bits.
+__device__ __forceinline__ int clamp_word(long v, int lo, int hi) { return v < (long)lo ? lo : (v > (long)hi ? hi : (int)v); }
+
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void pyramid_total_kernel(long total, int c, int rows, int cols, PyrLevels lv, uint64_t seed, uint32_t draw,
-                                                            const int64_t* __restrict__ timesteps, float timestep_div, float* __restrict__ tot,
-                                                            double* __restrict__ partial) {
+                                                            const int64_t* __restrict__ table, const int64_t* __restrict__ timesteps, float timestep_div,
+                                                            float* __restrict__ tot, double* __restrict__ partial) {
     __shared__ double sh[256];
     const int hw = rows * cols;
+    int n_levels = lv.n;
+    if (table) {
+        draw = (uint32_t)table[0];
+        n_levels = clamp_word(table[1], 0, E2EFT_PYRAMID_MAX_LEVELS);
+    }
     float s1 = 0.f, s2 = 0.f;
     for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
         const long gp = it / c;                  // b * hw + pix
@@ -186,8 +199,8 @@ __global__ __launch_bounds__(256) void pyramid_total_kernel(long total, int c, i
         float tw = 1.f;
         if constexpr (WEIGHTED) tw = (float)timesteps[b] / timestep_div;
         float acc = normal_at(seed, draw, 0u, (uint64_t)(plane * hw + pix));
-        for (int i = 0; i < lv.n; ++i) {
-            const int lr = lv.rows[i], lc = lv.cols[i];
+        for (int i = 0; i < n_levels; ++i) {
+            const int lr = table ? clamp_word(table[2 + 2 * i], 1, rows) : lv.rows[i], lc = table ? clamp_word(table[3 + 2 * i], 1, cols) : lv.cols[i];
             int y0, y1, x0, x1;
             float ly, lx;
             bilinear_tap(yy, lr, rows, y0, y1, ly);
@@ -241,6 +254,41 @@ __global__ __launch_bounds__(256) void pyramid_scale_kernel(long total, int c, i
         for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
             const long gp = it / c;
             y[gp * ldy + (it - gp * c)] = from_f<T>(tot[it] / sd);
+        }
+    }
+}
+
+// ---- e2eft_pyramid_table_set ---------------------------------------------------------------------------------------------------------------------------
+constexpr int PYR_TABLE_WORDS = 2 + 2 * E2EFT_PYRAMID_MAX_LEVELS;
+struct PyrTableWords {
+    int64_t w[PYR_TABLE_WORDS];
+};
+
+// one thread: the values travel as kernel arguments (no host-to-device copy, no staging buffer), plain stores
+__global__ void pyramid_table_set_kernel(PyrTableWords v, int64_t* __restrict__ table) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < PYR_TABLE_WORDS; ++k) table[k] = v.w[k];
+    }
+}
+
+// ---- e2eft_randint_fill --------------------------------------------------------------------------------------------------------------------------------
+// element e < n takes word e & 3 of quad e >> 2 (the generator's raw uint32, tests/noise_ref.py::words): t = (word * high) >> 32 in [0, high), written to
+// out[r * n + e] for r < repeat (the trainer's `randint(0, T, (b,)).repeat(2)`)
+__global__ __launch_bounds__(256) void randint_fill_kernel(long n, int repeat, uint64_t high, uint64_t seed, uint32_t draw, const int64_t* __restrict__ draw_at,
+                                                           uint32_t slot, int64_t* __restrict__ out) {
+    if (draw_at) draw = (uint32_t)*draw_at;
+    const long quads = (n + 3) >> 2;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
+        uint32_t w[4];
+        philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), slot, draw, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long e = 4 * q + j;
+            if (e < n) {
+                const int64_t t = (int64_t)(((uint64_t)w[j] * high) >> 32);
+                for (int r = 0; r < repeat; ++r) out[(long)r * n + e] = t;
+            }
         }
     }
 }
@@ -319,10 +367,11 @@ extern "C" size_t e2eft_pyramid_noise_workspace_bytes(int32_t batch, int32_t c, 
     return pyr_tot_bytes((long)batch * c * hw) + (size_t)PYR_MAX_BLOCKS * 2 * sizeof(double);
 }
 
-// timesteps == nullptr: e2eft_pyramid_noise; otherwise e2eft_pyramid_noise_weighted — one validation, one launcher, one pass-1 body (a template on "weighted")
+// timesteps == nullptr: e2eft_pyramid_noise; otherwise e2eft_pyramid_noise_weighted — one validation, one launcher, one pass-1 body (a template on "weighted").
+// table != nullptr: the `_at` forms — draw, n_levels and level_sizes are not looked at (pass 0, 0, nullptr), the kernel reads and clamps them from the device words
 static int pyramid_noise_launch(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
-                                int32_t n_levels, const int32_t* level_sizes, const int64_t* timesteps, float timestep_div, void* y, void* workspace,
-                                size_t workspace_bytes, void* stream) {
+                                int32_t n_levels, const int32_t* level_sizes, const int64_t* table, const int64_t* timesteps, float timestep_div, void* y,
+                                void* workspace, size_t workspace_bytes, void* stream) {
     E2EFT_REQUIRE(y && workspace && (level_sizes || n_levels == 0), "pyramid_noise: null pointer");
     E2EFT_REQUIRE(dtype >= 0 && dtype <= 2, "pyramid_noise: bad dtype");
     E2EFT_REQUIRE(batch > 0 && c > 0 && rows > 0 && cols > 0 && (long)rows * cols < (1L << 31) && ldy >= c, "pyramid_noise: shape");
@@ -340,6 +389,8 @@ static int pyramid_noise_launch(int32_t dtype, int32_t batch, int32_t c, int32_t
             lv.rows[i] = level_sizes[2 * i];
             lv.cols[i] = level_sizes[2 * i + 1];
             E2EFT_REQUIRE(lv.rows[i] >= 1 && lv.cols[i] >= 1 && (long)lv.rows[i] * lv.cols[i] * batch * c < (1L << 31), "pyramid_noise: level %d size", i);
+        }
+        if (i < n_levels || table) {      // (a device table may hold any number of levels: all ten weights, the same running product)
             lv.weight[i] = (float)w;
             w *= (double)discount;
         }
@@ -349,8 +400,8 @@ static int pyramid_noise_launch(int32_t dtype, int32_t batch, int32_t c, int32_t
     float* tot = (float*)workspace;
     double* partial = (double*)((char*)workspace + pyr_tot_bytes(total));
     const unsigned g1 = blocks_for(total, PYR_MAX_BLOCKS);
-    if (timesteps) hipLaunchKernelGGL((pyramid_total_kernel<true>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, timesteps, timestep_div, tot, partial);
-    else hipLaunchKernelGGL((pyramid_total_kernel<false>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, (const int64_t*)nullptr, 1.f, tot, partial);
+    if (timesteps) hipLaunchKernelGGL((pyramid_total_kernel<true>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, table, timesteps, timestep_div, tot, partial);
+    else hipLaunchKernelGGL((pyramid_total_kernel<false>), dim3(g1), dim3(256), 0, s, total, c, rows, cols, lv, seed, draw, table, (const int64_t*)nullptr, 1.f, tot, partial);
     const size_t pixel_bytes = 4 * dtype_size(dtype);
     const bool vec = c == 4 && ldy % 4 == 0 && ((uintptr_t)y % pixel_bytes) == 0;
     E2EFT_DISPATCH_DTYPE(dtype, T, {
@@ -362,7 +413,8 @@ static int pyramid_noise_launch(int32_t dtype, int32_t batch, int32_t c, int32_t
 
 extern "C" int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
                                    int32_t n_levels, const int32_t* level_sizes, void* y, void* workspace, size_t workspace_bytes, void* stream) {
-    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, nullptr, 1.f, y, workspace, workspace_bytes, stream);
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, nullptr, nullptr, 1.f, y, workspace, workspace_bytes,
+                                stream);
 }
 
 extern "C" int e2eft_pyramid_noise_weighted(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw,
@@ -370,8 +422,65 @@ extern "C" int e2eft_pyramid_noise_weighted(int32_t dtype, int32_t batch, int32_
                                             void* workspace, size_t workspace_bytes, void* stream) {
     E2EFT_REQUIRE(timesteps, "pyramid_noise_weighted: null timesteps");
     E2EFT_REQUIRE(timestep_div > 0.f, "pyramid_noise_weighted: timestep_div must be positive");
-    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, timesteps, timestep_div, y, workspace, workspace_bytes,
-                                stream);
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, draw, discount, n_levels, level_sizes, nullptr, timesteps, timestep_div, y, workspace,
+                                workspace_bytes, stream);
+}
+
+extern "C" int e2eft_pyramid_noise_at(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, const int64_t* table,
+                                      float discount, void* y, void* workspace, size_t workspace_bytes, void* stream) {
+    E2EFT_REQUIRE(table && ((uintptr_t)table & 7) == 0, "pyramid_noise_at: null or misaligned table");
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, 0u, discount, 0, nullptr, table, nullptr, 1.f, y, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2eft_pyramid_noise_weighted_at(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, const int64_t* table,
+                                               float discount, const int64_t* timesteps, float timestep_div, void* y, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+    E2EFT_REQUIRE(table && ((uintptr_t)table & 7) == 0, "pyramid_noise_weighted_at: null or misaligned table");
+    E2EFT_REQUIRE(timesteps, "pyramid_noise_weighted_at: null timesteps");
+    E2EFT_REQUIRE(timestep_div > 0.f, "pyramid_noise_weighted_at: timestep_div must be positive");
+    return pyramid_noise_launch(dtype, batch, c, rows, cols, ldy, seed, 0u, discount, 0, nullptr, table, timesteps, timestep_div, y, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2eft_pyramid_table_set(int64_t* table, uint32_t draw, int32_t n_levels, const int32_t* level_sizes, int32_t rows, int32_t cols, void* stream) {
+    E2EFT_REQUIRE(table && ((uintptr_t)table & 7) == 0 && (level_sizes || n_levels == 0), "pyramid_table_set: null or misaligned pointer");
+    E2EFT_REQUIRE(rows > 0 && cols > 0 && (long)rows * cols < (1L << 31), "pyramid_table_set: shape");
+    E2EFT_REQUIRE(n_levels >= 0 && n_levels <= E2EFT_PYRAMID_MAX_LEVELS, "pyramid_table_set: at most %d levels", E2EFT_PYRAMID_MAX_LEVELS);
+    PyrTableWords v;
+    v.w[0] = (int64_t)draw;
+    v.w[1] = n_levels;
+    for (int i = 0; i < E2EFT_PYRAMID_MAX_LEVELS; ++i) {
+        int lr = 1, lc = 1;
+        if (i < n_levels) {
+            lr = level_sizes[2 * i];
+            lc = level_sizes[2 * i + 1];
+            E2EFT_REQUIRE(lr >= 1 && lc >= 1, "pyramid_table_set: level %d size", i);
+            E2EFT_REQUIRE(lr <= rows && lc <= cols, "pyramid_table_set: level %d (%d x %d) exceeds the output (%d x %d)", i, lr, lc, rows, cols);
+        }
+        v.w[2 + 2 * i] = lr;
+        v.w[3 + 2 * i] = lc;
+    }
+    hipLaunchKernelGGL(pyramid_table_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, v, table);
+    return check_launch("pyramid_table_set");
+}
+
+// draw_at == nullptr: e2eft_randint_fill; otherwise e2eft_randint_fill_at — one kernel body
+static int randint_fill_launch(const char* what, int64_t n, int32_t repeat, int64_t high, uint64_t seed, uint32_t draw, const int64_t* draw_at, uint32_t slot,
+                               int64_t* out, void* stream) {
+    E2EFT_REQUIRE(out && ((uintptr_t)out & 7) == 0, "%s: null or misaligned pointer", what);
+    E2EFT_REQUIRE(n >= 1 && n < (1L << 31) && repeat >= 1, "%s: n must be 1 .. 2^31 - 1 and repeat >= 1", what);
+    E2EFT_REQUIRE(high >= 1 && high <= 0x7FFFFFFFL, "%s: high must be 1 .. 2^31 - 1", what);
+    hipLaunchKernelGGL(randint_fill_kernel, dim3(blocks_for((n + 3) / 4, 16384)), dim3(256), 0, (hipStream_t)stream, (long)n, (int)repeat, (uint64_t)high, seed, draw,
+                       draw_at, slot, out);
+    return check_launch(what);
+}
+
+extern "C" int e2eft_randint_fill(int64_t n, int32_t repeat, int64_t high, uint64_t seed, uint32_t draw, uint32_t slot, int64_t* out, void* stream) {
+    return randint_fill_launch("randint_fill", n, repeat, high, seed, draw, nullptr, slot, out, stream);
+}
+
+extern "C" int e2eft_randint_fill_at(int64_t n, int32_t repeat, int64_t high, uint64_t seed, const int64_t* draw, uint32_t slot, int64_t* out, void* stream) {
+    E2EFT_REQUIRE(draw && ((uintptr_t)draw & 7) == 0, "randint_fill_at: null or misaligned draw");
+    return randint_fill_launch("randint_fill_at", n, repeat, high, seed, 0u, draw, slot, out, stream);
 }
 
 extern "C" int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,

@@ -10,8 +10,16 @@ captured with — they stay on the eager paths.  `randn_at` is the capture-safe 
 int64 device tensor that belongs to the graph, and the caller sets it with `set_draw(tensor, gen)` — `fill_(gen.next_draw())`, one launch with the value as a
 kernel argument, no host-to-device copy, no synchronisation — before each replay.  The host counter stays the single source of truth: eager and captured calls on
 one generator interleave and see the sequence they see without capture.  `DrawAt(seed, draw_dev)` is the generator-shaped handle for code that takes a
-`generator=`: `randn_into` on it is `randn_at` (training.CapturedTrainStep).  "pyramid" is not captured: its level sizes are fresh host draws of Python's `random`
+`generator=`: `randn_into` on it is `randn_at` (training.CapturedTrainStep).  "pyramid" by value is not captured: its level sizes are fresh host draws of Python's `random`
 per call, as in the reference, so its launch arguments differ from call to call.
+
+The level sizes never index memory, though: every level value is a pure function of (seed, draw, slot, element), and only the level TABLE differs between calls.
+`pyramid_noise_at` / `geowizard_pyramid_noise_at` (`e2eft_pyramid_noise_at`, `e2eft_pyramid_noise_weighted_at`) read the draw and the table from 22 int64 device
+words, and `set_pyramid_table(table_dev, gen, sizes, rows, cols)` fills them before a replay — the caller draws `sizes` on the host where the eager loop draws
+them, so Python's `random` / numpy's stream end where they end without capture.  `randint_into(dst_int64, high, gen, repeat)` is the counter-based
+`torch.randint(0, high, (n,)).repeat(repeat)` (the diffusion objective's timesteps), by value or — on a `DrawAt` — read on the device.  A captured micro-step
+may make several draws (timesteps, then noise): a `DrawAt` carries one device word per draw site, named by what reads it, and — when the noise is a pyramid — the
+table; every draw reads the value `gen.next_draw()` would have returned at that point of the eager order (training.CapturedTrainStepAt).
 
 The GeoWizard trainer has a multi-resolution noise of its own (GeoWizard/geowizard/training/train_depth_normal.py:286-296): level sizes shrunk from the original size by
 numpy's global stream, every level weighted per sample by `timesteps / 1000`.  `geowizard_pyramid_level_sizes` / `geowizard_pyramid_noise_into` are that function
@@ -39,15 +47,37 @@ class DeviceNoise:
 
 
 class DrawAt(DeviceNoise):
-    """a DeviceNoise whose draw is read ON THE DEVICE: `randn_into` with it is `randn_at(dst, seed, draw_dev)`.  What a captured graph is handed in place of the
-    caller's generator (training.CapturedTrainStep); the caller's generator stays the source of truth and feeds `draw_dev` through `set_draw`."""
+    """a DeviceNoise whose draws are read ON THE DEVICE: `randn_into` with it is `randn_at(dst, seed, draw_dev)`.  What a captured graph is handed in place of the
+    caller's generator (training.CapturedTrainStep); the caller's generator stays the source of truth and feeds the words through `set_draw` /
+    `set_pyramid_table`.
 
-    def __init__(self, seed, draw_dev):
+    One device word PER DRAW SITE of a micro-step, each named by what reads it — no cursor, no order to keep, and a draw that is executed again (a recomputed
+    segment) reads the same word again:
+      draw_dev      one-element int64: the Gaussian draw (`randn_into`)
+      randint_dev   one-element int64: the integer draw (`randint_into`: the diffusion objective's timesteps); None when the micro-step makes none
+      table         the 22-word level table of the pyramid draw (`pyramid_noise_into` / `geowizard_pyramid_noise_into`; its word 0 is that draw's `draw`,
+                    `set_pyramid_table`), with table_hw the latent (rows, cols) it is filled for; None when the micro-step draws no pyramid
+    A micro-step therefore makes at most one draw of each kind."""
+
+    def __init__(self, seed, draw_dev, table=None, table_hw=None, randint_dev=None):
         super().__init__(seed)
-        self.draw_dev = draw_dev
+        self.draw_dev, self.randint_dev = draw_dev, randint_dev
+        self.table, self.table_hw = table, (None if table_hw is None else (int(table_hw[0]), int(table_hw[1])))
 
     def next_draw(self):
         raise RuntimeError("noise.DrawAt holds no host counter: only the Gaussian draw (randn_into) can read its draw on the device")
+
+    def randint_word(self):
+        if self.randint_dev is None:
+            raise RuntimeError("noise.DrawAt: this handle carries no word for an integer draw (DrawAt(seed, draw_dev, randint_dev=...))")
+        return self.randint_dev
+
+    def table_for(self, rows, cols):
+        if self.table is None:
+            raise RuntimeError("noise.DrawAt: this handle carries no pyramid table (DrawAt(seed, draw_dev, table, (rows, cols)))")
+        if self.table_hw != (int(rows), int(cols)):
+            raise ValueError("noise.DrawAt: the pyramid table is filled for %s latents, the destination is %s" % (self.table_hw, (int(rows), int(cols))))
+        return self.table
 
 
 def pyramid_level_sizes(rows, cols, rng=random):
@@ -81,9 +111,43 @@ def randn_at(dst_nhwc_slice, seed, draw_dev):
     return ops.randn_fill_at_(dst_nhwc_slice, seed, draw_dev, slot=0)
 
 
+def randint_into(dst_int64, high, gen, repeat=1):
+    """`torch.randint(0, high, (n,)).repeat(repeat)` from the device generator into a contiguous int64 tensor of n * repeat elements (`e2eft_randint_fill`: the raw
+    word of every element, t = (word * high) >> 32); advances `gen.draw` once (a `DrawAt` reads its next draw word on the device instead)"""
+    if isinstance(gen, DrawAt):
+        return ops.randint_fill_at_(dst_int64, high, gen.seed, gen.randint_word(), slot=0, repeat=repeat)
+    return ops.randint_fill_(dst_int64, high, gen.seed, gen.next_draw(), slot=0, repeat=repeat)
+
+
+def set_pyramid_table(table_dev, gen, sizes, rows, cols):
+    """advance `gen.draw` and put the value drawn, with the level `sizes` of a rows x cols latent, into the 22-word int64 device table a captured
+    `pyramid_noise_at` / `geowizard_pyramid_noise_at` reads (one one-thread launch with the values as kernel arguments, nothing is copied or read)"""
+    return ops.pyramid_table_set_(table_dev, gen.next_draw(), sizes, rows, cols)
+
+
+def pyramid_noise_at(dst_nhwc_slice, seed, table_dev, discount=0.9):
+    """`pyramid_noise_into` with the draw and the level sizes read on the device from `table_dev` (see `set_pyramid_table`): the same bits for the same values,
+    safe inside a hipGraph capture"""
+    return ops.pyramid_noise_at_(dst_nhwc_slice, seed, table_dev, discount)
+
+
+def geowizard_pyramid_noise_at(dst_nhwc_slice, seed, table_dev, timesteps, discount=0.9):
+    """`geowizard_pyramid_noise_into` with the draw and the level sizes read on the device from `table_dev`"""
+    return ops.pyramid_noise_weighted_at_(dst_nhwc_slice, seed, table_dev, timesteps, discount, 1000.0)
+
+
+def _table_of(gen, dst_nhwc_slice, sizes):
+    if sizes is not None:
+        raise ValueError("a noise.DrawAt reads its level sizes from its device table: explicit `sizes` go through set_pyramid_table")
+    _, H, W, _ = dst_nhwc_slice.shape
+    return gen.table_for(H, W)
+
+
 def pyramid_noise_into(dst_nhwc_slice, gen, discount=0.9, sizes=None):
     """multi-resolution noise of unit std into an NHWC view [B,H,W,C]; `sizes` defaults to `pyramid_level_sizes(H, W)` (Python's `random`, as the
-    reference); advances `gen.draw`"""
+    reference); advances `gen.draw`.  A `DrawAt` reads draw and sizes from its device table instead (`pyramid_noise_at`) and draws nothing on the host."""
+    if isinstance(gen, DrawAt):
+        return pyramid_noise_at(dst_nhwc_slice, gen.seed, _table_of(gen, dst_nhwc_slice, sizes), discount)
     _, H, W, _ = dst_nhwc_slice.shape
     if sizes is None:
         sizes = pyramid_level_sizes(H, W)
@@ -109,8 +173,10 @@ def geowizard_pyramid_level_sizes(rows, cols, rng=np.random, scale=1.5):
 def geowizard_pyramid_noise_into(dst_nhwc_slice, gen, timesteps, discount=0.9, sizes=None):
     """the GeoWizard trainer's timestep-weighted multi-resolution noise (train_depth_normal.py:286-296, called at :658-659) of unit std into an NHWC view [B,H,W,C]:
     level i of sample b weighted by timesteps[b] / 1000 * discount^i (the literal 1000 of :294).  timesteps: int64 device tensor [B], read on the device; `sizes`
-    defaults to `geowizard_pyramid_level_sizes(H, W)` (numpy's global stream, as the reference); advances `gen.draw` once.  Not captured, for `pyramid_noise_into`'s
-    reason: the sizes are fresh host draws per call."""
+    defaults to `geowizard_pyramid_level_sizes(H, W)` (numpy's global stream, as the reference); advances `gen.draw` once.  By value it is not captured, for
+    `pyramid_noise_into`'s reason: the sizes are fresh host draws per call.  A `DrawAt` reads draw and sizes from its device table (`geowizard_pyramid_noise_at`)."""
+    if isinstance(gen, DrawAt):
+        return geowizard_pyramid_noise_at(dst_nhwc_slice, gen.seed, _table_of(gen, dst_nhwc_slice, sizes), timesteps, discount)
     _, H, W, _ = dst_nhwc_slice.shape
     if sizes is None:
         sizes = geowizard_pyramid_level_sizes(H, W)

@@ -1023,6 +1023,97 @@ def pyramid_noise_weighted_(dst, seed, draw, sizes, timesteps, discount=0.9, tim
     return dst
 
 
+PYRAMID_TABLE_WORDS = 22      # 2 + 2 * E2EFT_PYRAMID_MAX_LEVELS: {draw, n_levels, rows_0, cols_0, ..., rows_9, cols_9}
+
+
+def _check_pyramid_table(what, table):
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or table.numel() != PYRAMID_TABLE_WORDS or not table.is_contiguous():
+        raise TypeError("%s: table must be a contiguous int64 tensor of %d elements {draw, n_levels, 10 x (rows, cols)}, got %s"
+                        % (what, PYRAMID_TABLE_WORDS, "%s %s" % (table.dtype, tuple(table.shape)) if isinstance(table, torch.Tensor) else type(table)))
+
+
+def pyramid_table_set_(table, draw, sizes, rows, cols):
+    """table (int64 DEVICE tensor [22]) <- {draw, len(sizes), sizes..., (1, 1) for the unused levels} for an output of rows x cols: what `pyramid_noise_at_` /
+    `pyramid_noise_weighted_at_` read when they run.  One one-thread launch with the values as kernel arguments — nothing is copied from the host, nothing is
+    staged, nothing synchronises; a level larger than the output is refused before the launch."""
+    _check_pyramid_table("pyramid_table_set_", table)
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    if len(sizes) > 10:
+        raise ValueError("pyramid_table_set_: at most 10 levels, got %d" % len(sizes))
+    _check_cuda(table)
+    host = (C.c_int32 * max(2 * len(sizes), 2))(*[v for rc in sizes for v in rc])
+    check(_lib.load().e2eft_pyramid_table_set(_ptr(table), int(draw) & 0xFFFFFFFF, len(sizes), host, int(rows), int(cols), _stream()))
+    return table
+
+
+def pyramid_noise_at_(dst, seed, table, discount=0.9):
+    """`pyramid_noise_` with the draw and the level sizes read on the device from `table` (`pyramid_table_set_`) when the kernel runs: the capture-safe form — a
+    replayed graph draws over what the table holds at replay time.  Same table values -> the bits of `pyramid_noise_`."""
+    _check_pyramid_table("pyramid_noise_at_", table)
+    _check_cuda(dst, table)
+    B, H, W, Cc = dst.shape
+    lib = _lib.load()
+    nbytes = lib.e2eft_pyramid_noise_workspace_bytes(B, Cc, H * W)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dst.device)
+    check(lib.e2eft_pyramid_noise_at(dtype_id(dst.dtype), B, Cc, H, W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(table), float(discount), _ptr(dst),
+                                     _ptr(ws), nbytes, _stream()))
+    return dst
+
+
+def pyramid_noise_weighted_at_(dst, seed, table, timesteps, discount=0.9, timestep_div=1000.0):
+    """`pyramid_noise_weighted_` with the draw and the level sizes read on the device from `table` (`pyramid_table_set_`); timesteps as there.  Same table values
+    and timesteps -> the bits of `pyramid_noise_weighted_`."""
+    _check_pyramid_table("pyramid_noise_weighted_at_", table)
+    if not isinstance(timesteps, torch.Tensor) or timesteps.dtype != torch.int64:
+        raise TypeError("pyramid_noise_weighted_at_: timesteps must be an int64 tensor, got %s" % (timesteps.dtype if isinstance(timesteps, torch.Tensor) else type(timesteps)))
+    if dst.dim() != 4:
+        raise ValueError("pyramid_noise_weighted_at_: dst must be an NHWC view [B,H,W,C], got %s" % (tuple(dst.shape),))
+    B, H, W, Cc = dst.shape
+    if timesteps.numel() != B or not timesteps.is_contiguous():
+        raise ValueError("pyramid_noise_weighted_at_: timesteps must be contiguous with one entry per sample (%d), got shape %s stride %s"
+                         % (B, tuple(timesteps.shape), tuple(timesteps.stride())))
+    if not float(timestep_div) > 0.0:
+        raise ValueError("pyramid_noise_weighted_at_: timestep_div must be positive, got %r" % (timestep_div,))
+    _check_cuda(dst, table, timesteps)
+    lib = _lib.load()
+    nbytes = lib.e2eft_pyramid_noise_workspace_bytes(B, Cc, H * W)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dst.device)
+    check(lib.e2eft_pyramid_noise_weighted_at(dtype_id(dst.dtype), B, Cc, H, W, _nhwc_ld(dst), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(table), float(discount),
+                                              _ptr(timesteps), float(timestep_div), _ptr(dst), _ptr(ws), nbytes, _stream()))
+    return dst
+
+
+def _check_randint(what, out, high, repeat):
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or not out.is_contiguous():
+        raise TypeError("%s: out must be a contiguous int64 tensor" % what)
+    repeat, high = int(repeat), int(high)
+    if repeat < 1 or out.numel() < 1 or out.numel() % repeat:
+        raise ValueError("%s: out holds %d elements, not a positive multiple of repeat = %d" % (what, out.numel(), repeat))
+    if not 1 <= high <= 2 ** 31 - 1:
+        raise ValueError("%s: high must be 1 .. 2^31 - 1, got %d" % (what, high))
+    return out.numel() // repeat, repeat, high
+
+
+def randint_fill_(out, high, seed, draw, slot=0, repeat=1):
+    """out (int64, n * repeat elements) <- `repeat` copies of n integers of [0, high) from the device generator: element e takes the raw word of (seed, draw, slot,
+    e) and t = (word * high) >> 32 (include/e2eft.h).  `torch.randint(0, high, (n,)).repeat(repeat)` in shape; torch's stream is not reproduced."""
+    n, repeat, high = _check_randint("randint_fill_", out, high, repeat)
+    _check_cuda(out)
+    check(_lib.load().e2eft_randint_fill(n, repeat, high, int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, int(slot), _ptr(out), _stream()))
+    return out
+
+
+def randint_fill_at_(out, high, seed, draw, slot=0, repeat=1):
+    """`randint_fill_` with `draw` a one-element int64 DEVICE tensor read when the kernel runs: the capture-safe form, the integers of `randint_fill_` for the
+    same value"""
+    n, repeat, high = _check_randint("randint_fill_at_", out, high, repeat)
+    _check_cuda(out, draw)
+    if draw.dtype != torch.int64 or draw.numel() != 1:
+        raise TypeError("randint_fill_at_: draw must be a one-element int64 tensor, got %s %s" % (draw.dtype, tuple(draw.shape)))
+    check(_lib.load().e2eft_randint_fill_at(n, repeat, high, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(draw), int(slot), _ptr(out), _stream()))
+    return out
+
+
 def latent_x0(x_t, v, c_x, c_v, out=None):
     """out = c_x * x_t + c_v * v for NHWC views [B,H,W,C] of one shape (x_t typically the noise channels of the UNet input, read in place)."""
     _check_cuda(x_t, v, out)
@@ -1682,6 +1773,17 @@ def ema_step_(shadow, param, one_minus_decay):
     _check_cuda(shadow, param)
     assert shadow.dtype == param.dtype == torch.float32 and shadow.is_contiguous() and param.is_contiguous() and shadow.numel() == param.numel()
     check(_lib.load().e2eft_ema_step(shadow.numel(), _ptr(shadow), _ptr(param), float(one_minus_decay), _stream()))
+    return shadow
+
+
+def ema_step_at_(shadow, param, one_minus_decay):
+    """`ema_step_` with 1 - decay read on the device from a one-element fp32 tensor when the kernel runs: the capture-safe form, the bits of `ema_step_` for
+    the same fp32 value"""
+    if not isinstance(one_minus_decay, torch.Tensor) or one_minus_decay.dtype != torch.float32 or one_minus_decay.numel() != 1:
+        raise TypeError("ema_step_at_: one_minus_decay must be a one-element fp32 tensor, got %r" % (one_minus_decay,))
+    _check_cuda(shadow, param, one_minus_decay)
+    assert shadow.dtype == param.dtype == torch.float32 and shadow.is_contiguous() and param.is_contiguous() and shadow.numel() == param.numel()
+    check(_lib.load().e2eft_ema_step_at(shadow.numel(), _ptr(shadow), _ptr(param), _ptr(one_minus_decay), _stream()))
     return shadow
 
 

@@ -275,6 +275,9 @@ def geowizard_diffusion_loss(unet, vae, batch, imgs_embed, domain="indoor", nois
     doubled timesteps exist, level i of row r weighted by timesteps[r] / 1000 * 0.9^i on the device (no read-back), level sizes from numpy's global stream as in the
     reference; it then goes through add_noise and the masked MSE as "gaussian" does.  The name "pyramid" is refused (GEOWIZARD_PYRAMID_MESSAGE).
     timesteps: int64 [b] instead of drawn ones (drawn on the device from torch's generator, no read-back).
+    timesteps may also be a noise.DeviceNoise: the timesteps are then drawn by IT (`noise.randint_into`, the counter-based `randint(0, T, (b,)).repeat(2)`) BEFORE
+    the noise draw instead of by `torch.randint`; usually the same object as `generator`, which then advances twice per call.  Capture-safe with a `noise.DrawAt`
+    (training.CapturedTrainStepAt).  None keeps `torch.randint`.
     No selected cell: the loss is 0 and its gradient is zero everywhere, as e2e_ft_loss does for an all-invalid batch (the reference skips the term, :714).
     Returns the loss; return_parts: (loss, n_selected int64 [1], target fp32 [2b,4,h,w], x_t [2b,4,h,w])."""
     core = getattr(unet, "module", unet)
@@ -307,11 +310,15 @@ def _geowizard_diffusion_loss(unet, core, vae, batch, imgs_embed, domain, noise_
     if tuple(latent_mask.shape[1:]) != (h, w):
         raise ValueError("val_mask gives %s latent cells, the latents are %s" % (tuple(latent_mask.shape[1:]), (h, w)))
     T = noise_scheduler.config.num_train_timesteps
-    if timesteps is None:
-        timesteps = torch.randint(0, T, (b,), device=dev)
-    elif timesteps.numel() != b:
-        raise ValueError("timesteps must hold one entry per image (%d), got %d" % (b, timesteps.numel()))
-    timesteps = timesteps.to(device=dev, dtype=torch.long).reshape(b).repeat(2)
+    from . import noise as N
+    if isinstance(timesteps, N.DeviceNoise):
+        timesteps = N.randint_into(torch.empty((2 * b,), dtype=torch.long, device=dev), T, timesteps, repeat=2)      # (:651, already doubled)
+    else:
+        if timesteps is None:
+            timesteps = torch.randint(0, T, (b,), device=dev)
+        elif timesteps.numel() != b:
+            raise ValueError("timesteps must hold one entry per image (%d), got %d" % (b, timesteps.numel()))
+        timesteps = timesteps.to(device=dev, dtype=torch.long).reshape(b).repeat(2)
     nz = _geowizard_noise(noise_type, generator, noise, 2 * b, C, h, w, dt, dev, timesteps)      # (:656-663; the weighted pyramid reads the doubled timesteps on the device)
     abar = noise_scheduler.alphas_cumprod_on(dev)
     xin = torch.empty((2 * b, h, w, 2 * C), dtype=dt, device=dev)
@@ -866,6 +873,40 @@ class EMAModel:
             else:
                 s_param.copy_(param)
 
+    def _one_launch_source(self, parameters, what):
+        """the flat parameter buffer the one-launch form reads, or the reason why this EMA has no such form"""
+        parameters = list(parameters)
+        src = self._flat_source(parameters) if self._shadow_flat is not None else None
+        if src is None or src[1].numel() != self._shadow_flat.numel():
+            raise NotImplementedError("EMAModel.%s: the capture-safe EMA is the flat one-launch form: the shadow must lie over a FlatAdamW buffer and `parameters` "
+                                      "must be that optimizer's parameters in its order (construct the optimizer first, then EMAModel(unet.parameters()))" % what)
+        if not all(p.requires_grad for p in parameters):
+            raise NotImplementedError("EMAModel.%s: a parameter that does not require a gradient is copied, not averaged; the one-launch form averages every "
+                                      "slot, so it runs only when every parameter of the buffer is trainable" % what)
+        return src[1]
+
+    def set_decay_word(self, word):
+        """The HOST half of `step`: `optimization_step += 1`, `get_decay`, `cur_decay_value`, and word (one-element fp32 device tensor) <- (float)(1 - decay) — the
+        value `ops.ema_step_` receives from `step` — by one small fill launch: nothing is copied from the host or read back.  Call it once per optimizer step,
+        before the launch (or the replay) of `step_at`."""
+        import ctypes
+        if self._shadow_flat is None:
+            raise NotImplementedError("EMAModel.set_decay_word: the capture-safe EMA is the flat one-launch form: the shadow must lie over a FlatAdamW buffer")
+        self._one_launch_source(self._flat[0].params, "set_decay_word")      # (the optimizer the shadow was laid over: still flat, every parameter trainable)
+        self.optimization_step += 1
+        decay = self.get_decay(self.optimization_step)
+        self.cur_decay_value = decay
+        word.fill_(ctypes.c_float(1 - decay).value)
+        return word
+
+    @torch.no_grad()
+    def step_at(self, parameters, word):
+        """The DEVICE half of `step`: ONE `e2eft_ema_step_at` launch over the flat shadow with 1 - decay read on the device from `word` (`set_decay_word`) — bit
+        for bit the update of `step` for the same value.  Capture-safe; only the flat one-launch form exists (refused otherwise, with the reason)."""
+        flat = self._one_launch_source(parameters, "step_at")
+        with ops.on_device_of(flat):
+            ops.ema_step_at_(self._shadow_flat, flat, word)
+
     @torch.no_grad()
     def copy_to(self, parameters):
         parameters = list(parameters)
@@ -1035,6 +1076,10 @@ class CapturedTrainStep:
             raise NotImplementedError("CapturedTrainStep: gather_loss is a collective per micro-step; RCCL inside a capture is not built")
         if ema is not None:
             raise NotImplementedError("CapturedTrainStep: the EMA stays an eager call after the step (EMAModel.step)")
+        self._init_common(unet, vae, optimizer, empty_encoding, modality, noise_type, generator, accumulation, loss, domain, depth_scale, normal_scale)
+
+    def _init_common(self, unet, vae, optimizer, empty_encoding, modality, noise_type, generator, accumulation, loss, domain, depth_scale, normal_scale):
+        """what every captured step checks and holds, whatever loss and noise it was built for (the mode-specific refusals come before it)"""
         if not isinstance(optimizer, FlatAdamW):
             raise TypeError("CapturedTrainStep steps a FlatAdamW (the update it captures is FlatAdamW.step_at)")
         if getattr(optimizer, "world", 1) != 1 or optimizer._hooks:
@@ -1087,13 +1132,36 @@ class CapturedTrainStep:
         ent["gen"] = N.DrawAt(self.generator.seed, ent["draw"]) if self.noise_type == "gaussian" else None
         return ent
 
+    def _takes_embed(self):
+        """the GeoWizard UNet: one image embedding per micro-batch, and the class embedding read in place"""
+        return self.loss == "geowizard"
+
+    def _loss(self, ent):
+        if self.loss == "geowizard":
+            return geowizard_e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["embed"], self.domain, self.depth_scale, self.normal_scale,
+                                         noise_type=self.noise_type, generator=ent["gen"])
+        return e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["ctx"], self.modality, noise_type=self.noise_type, generator=ent["gen"])
+
+    def _feed(self, ent):
+        """before a micro-step runs or is replayed: the device words its draws read, from the caller's generator (the source of truth)"""
+        from . import noise as N
+        if ent["gen"] is not None:
+            N.set_draw(ent["draw"], self.generator)
+
+    def _alive(self, ent):
+        """what the captured forward reads in place: it must exist before the capture and outlive it"""
+        if self._takes_embed():
+            core = getattr(self.unet, "module", self.unet)
+            return geowizard_class_embedding(ent["batch"]["rgb"].shape[0], self.domain, getattr(core, "compute_dtype", core.dtype), core.device)
+        return None
+
+    def _update(self):
+        """the update graph's content (and the eager first call's update): only device work on the current stream"""
+        self.optimizer.step_at(self._hyper)
+
     def _micro(self, ent, first):
         """one micro-step on the entry's static buffers: `train_step`'s loop body.  Only device work on the current stream."""
-        if self.loss == "geowizard":
-            loss = geowizard_e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["embed"], self.domain, self.depth_scale, self.normal_scale,
-                                         noise_type=self.noise_type, generator=ent["gen"])
-        else:
-            loss = e2e_ft_loss(self.unet, self.vae, ent["batch"], ent["ctx"], self.modality, noise_type=self.noise_type, generator=ent["gen"])
+        loss = self._loss(ent)
         (loss / self.accumulation).backward()
         if first:
             ent["total"].copy_(loss.detach())
@@ -1103,9 +1171,7 @@ class CapturedTrainStep:
     def _capture(self, ent):
         from . import modules as M
         opt = self.optimizer
-        if self.loss == "geowizard":      # what the captured forward reads in place must exist before the capture and outlive it
-            core = getattr(self.unet, "module", self.unet)
-            ent["alive"] = geowizard_class_embedding(ent["batch"]["rgb"].shape[0], self.domain, getattr(core, "compute_dtype", core.dtype), core.device)
+        ent["alive"] = self._alive(ent)
         F.bump_param_epoch()              # every derived weight misses its cache: its builder's launches become part of the first graph
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
@@ -1118,7 +1184,7 @@ class CapturedTrainStep:
                 with torch.cuda.graph(graphs["later"], pool=pool):
                     self._micro(ent, False)
             with torch.cuda.graph(graphs["update"], pool=pool):
-                opt.step_at(self._hyper)
+                self._update()
         finally:
             M.PRESERVE_RNG_STATE = keep
             # nothing captured has run: the host goes back to the state before a step (gradients of the capture are addresses inside the graphs now)
@@ -1126,12 +1192,15 @@ class CapturedTrainStep:
             opt.zero_grad()
         ent["graphs"] = graphs
 
+    def _set_step_words(self, lr_scale):
+        """once per optimizer step, before any launch of it: the device words the update reads"""
+        self.optimizer.set_hyper(self._hyper, lr_scale)
+
     def __call__(self, batches, lr_scale=1.0, imgs_embed=None):
-        from . import noise as N
         n = self.accumulation
         if len(batches) != n:
             raise ValueError("CapturedTrainStep: %d micro-batches given, accumulation is %d (the graphs of an entry are one optimizer step)" % (len(batches), n))
-        if self.loss == "geowizard":
+        if self._takes_embed():
             if imgs_embed is None or len(imgs_embed) != n:
                 raise ValueError("CapturedTrainStep.geowizard: imgs_embed must hold one embedding per micro-batch (%d)" % n)
         elif imgs_embed is not None:
@@ -1153,27 +1222,155 @@ class CapturedTrainStep:
             elif ent["graphs"] is None:
                 self._capture(ent)
             graphs = ent["graphs"]
-            opt.set_hyper(self._hyper, lr_scale)
+            self._set_step_words(lr_scale)
             opt.sync_grads = True
             for i, (batch, embed) in enumerate(zip(batches, embeds)):
                 for k, t in ent["batch"].items():
                     t.copy_(batch[k])
                 if embed is not None:
                     ent["embed"].copy_(embed)
-                if ent["gen"] is not None:
-                    N.set_draw(ent["draw"], self.generator)
+                self._feed(ent)
                 if graphs is None:
                     self._micro(ent, i == 0)
                 else:
                     graphs["first" if i == 0 else "later"].replay()
             if graphs is None:
-                opt.step_at(self._hyper)
+                self._update()
             else:
                 graphs["update"].replay()
             opt._after_step()
             opt._opt_called = True          # (what torch's lr schedulers look at before they warn about a scheduler stepped ahead of its optimizer)
             opt.zero_grad()
             return ent["total"] / n
+
+
+class CapturedTrainStepAt(CapturedTrainStep):
+    """`CapturedTrainStep` for what the base class refuses because it changes from step to step on the host: every such value moves from a
+    launch argument into device words that belong to the graphs, and the host fills those words before the replay — what §3.26 did for `lr` and the Gaussian draw.
+
+      noise_type="pyramid" (E2E-FT loss) / "geowizard_pyramid" (both GeoWizard losses; the name "pyramid" stays refused there, GEOWIZARD_PYRAMID_MESSAGE):
+          the level sizes are drawn on the host per micro-step, in micro-step order, by `noise.pyramid_level_sizes` / `noise.geowizard_pyramid_level_sizes` from
+          Python's `random` / numpy's global stream — both end where the eager loop leaves them — and written with `noise.set_pyramid_table` before that
+          micro-step's replay; the captured kernels are `e2eft_pyramid_noise_at` / `e2eft_pyramid_noise_weighted_at`.
+      loss="diffusion" (`CapturedTrainStepAt.diffusion(unet, vae, optimizer, domain, noise_scheduler, prediction_type, noise_type, generator=, accumulation=,
+          ema=)`, called as `step(batches, lr_scale, imgs_embed=[...])` with the fields rgb / depth / normals / val_mask): `geowizard_diffusion_loss` with
+          `timesteps=` the generator — the timesteps come from the caller's `noise.DeviceNoise` (`e2eft_randint_fill_at`), drawn before the noise, so a generator
+          is needed even with noise_type="zeros".  The timesteps are not torch's: the eager loop this step reproduces passes `timesteps=generator` too.
+      ema=EMAModel: `EMAModel.step_at` is the LAST node of the update graph (it also runs after a step the guard skipped, as the eager call and diffusers do) and
+          the decay word is filled next to `set_hyper` (`EMAModel.set_decay_word`).  Only the flat one-launch EMA over this optimizer's buffer.
+
+    One micro-step may make two draws (timesteps, then noise): its `noise.DrawAt` carries one device word per draw and, for the pyramids, the table; each reads the
+    value `generator.next_draw()` returns at that point of the eager order.  The key gains the loss, the prediction type, `num_train_timesteps`, the discount, the
+    generator's seed and the identity of the EMA's shadow; the entry keeps alive what the graphs read in place (the scheduler's `alphas_cumprod` table on the
+    device, the class embedding; the timestep tensor is an allocation of the graphs' own pool).  Everything else — eager first call, capturing second,
+    `GroupedFlatAdamW`, activation recompute, static input buffers — is inherited.
+
+    Still refused, before any capture: world size > 1 / exchange hooks, `gather_loss`, an EMA that is not the flat one-launch form over this optimizer."""
+
+    DISCOUNT = 0.9            # what `e2e_ft_loss` / the GeoWizard losses draw their pyramids with (the default of noise.*pyramid_noise_into)
+
+    def __init__(self, unet, vae, optimizer, empty_encoding=None, modality="depth", noise_type="zeros", generator=None, accumulation=1, gather_loss=False,
+                 ema=None, loss="e2e_ft", domain="indoor", depth_scale=0.5, normal_scale=1.0, noise_scheduler=None, prediction_type=None):
+        from . import noise as N
+        if loss not in ("e2e_ft", "geowizard", "diffusion"):
+            raise ValueError("CapturedTrainStepAt: loss must be 'e2e_ft', 'geowizard' or 'diffusion', got %r" % (loss,))
+        if loss != "e2e_ft" and noise_type == "pyramid":
+            raise ValueError(GEOWIZARD_PYRAMID_MESSAGE)
+        if noise_type not in (("zeros", "gaussian", "pyramid", None) if loss == "e2e_ft" else ("zeros", "gaussian", "geowizard_pyramid")):
+            raise ValueError("Unknown noise type %s" % noise_type)
+        draws = loss == "diffusion" or noise_type in ("gaussian", "pyramid", "geowizard_pyramid")
+        if draws and (not isinstance(generator, N.DeviceNoise) or isinstance(generator, N.DrawAt)):
+            raise TypeError("CapturedTrainStepAt: %s draws on the device: pass generator=noise.DeviceNoise(seed)"
+                            % ("the diffusion objective (its timesteps)" if loss == "diffusion" else "noise_type=%r" % noise_type))
+        if gather_loss:
+            raise NotImplementedError("CapturedTrainStepAt: gather_loss is a collective per micro-step; RCCL inside a capture is not built")
+        self._init_common(unet, vae, optimizer, empty_encoding, modality, noise_type, generator, accumulation, loss, domain, depth_scale, normal_scale)
+        self.ema, self.noise_scheduler, self.prediction_type = ema, noise_scheduler, prediction_type
+        if loss == "diffusion":
+            if noise_scheduler is None:
+                from .scheduler import DDPMScheduler
+                self.noise_scheduler = DDPMScheduler()            # ONE scheduler for every step: its device table is uploaded once, outside any capture
+            self.prediction_type = prediction_type if prediction_type is not None else self.noise_scheduler.config.prediction_type
+            if self.prediction_type not in ("epsilon", "v_prediction"):
+                raise ValueError("Unknown prediction type %s" % self.prediction_type)
+        if ema is not None:
+            if not isinstance(ema, EMAModel):
+                raise TypeError("CapturedTrainStepAt: ema must be a training.EMAModel")
+            ema._one_launch_source(optimizer.params, "step_at")            # (raises with the reason)
+            if ema._flat[0] is not optimizer:
+                raise NotImplementedError("CapturedTrainStepAt: the EMA's shadow must lie over THIS optimizer's flat buffer")
+            with ops.on_device_of(optimizer.flat_param):
+                self._ema_word = torch.zeros(1, dtype=torch.float32, device=optimizer.flat_param.device)
+
+    @classmethod
+    def diffusion(cls, unet, vae, optimizer, domain="indoor", noise_scheduler=None, prediction_type=None, noise_type="gaussian", generator=None, accumulation=1,
+                  ema=None, **kw):
+        """the same step around `geowizard_diffusion_loss` (GeoWizard's default objective); call it as `step(batches, lr_scale, imgs_embed=[...])`"""
+        return cls(unet, vae, optimizer, None, None, noise_type, generator, accumulation, ema=ema, loss="diffusion", domain=domain, noise_scheduler=noise_scheduler,
+                   prediction_type=prediction_type, **kw)
+
+    def _pyramid(self):
+        return self.noise_type in ("pyramid", "geowizard_pyramid")
+
+    def _takes_embed(self):
+        return self.loss in ("geowizard", "diffusion")
+
+    def _fields(self):
+        if self.loss == "diffusion":
+            return ("rgb", "depth", "normals", "val_mask")
+        return super()._fields()
+
+    def _mode_key(self):
+        T = self.noise_scheduler.config.num_train_timesteps if self.loss == "diffusion" else None
+        return super()._mode_key() + (None if self.generator is None else self.generator.seed, self.prediction_type, T, self.DISCOUNT if self._pyramid() else None,
+                                      None if self.ema is None else self.ema._shadow_flat.data_ptr())
+
+    def _new_entry(self, batch, embed):
+        from . import noise as N
+        ent = super()._new_entry(batch, embed)
+        dev = ent["total"].device
+        words = int(self.loss == "diffusion") + int(self.noise_type == "gaussian")
+        ent["draw"] = torch.zeros(2, dtype=torch.int64, device=dev)                          # one word per draw site of a micro-step: [timesteps, Gaussian noise]
+        ent["table"] = torch.zeros(ops.PYRAMID_TABLE_WORDS, dtype=torch.int64, device=dev) if self._pyramid() else None      # (its word 0 is the pyramid's draw)
+        f = 2 ** (len(self.vae.config.block_out_channels) - 1)
+        ent["hw"] = (batch["rgb"].shape[-2] // f, batch["rgb"].shape[-1] // f)               # the latent grid the level sizes are drawn for
+        ent["gen"] = (N.DrawAt(self.generator.seed, ent["draw"][1:2], ent["table"], ent["hw"], randint_dev=ent["draw"][0:1])
+                      if (words or self._pyramid()) else None)
+        return ent
+
+    def _loss(self, ent):
+        if self.loss == "diffusion":
+            return geowizard_diffusion_loss(self.unet, self.vae, ent["batch"], ent["embed"], self.domain, self.noise_scheduler, self.noise_type, ent["gen"],
+                                            timesteps=ent["gen"], prediction_type=self.prediction_type)
+        return super()._loss(ent)
+
+    def _feed(self, ent):
+        """the words of this micro-step's draws, in the eager order: timesteps, then noise; the level sizes are the host draw the eager loss would make here"""
+        from . import noise as N
+        if self.loss == "diffusion":
+            N.set_draw(ent["gen"].randint_dev, self.generator)
+        if self.noise_type == "gaussian":
+            N.set_draw(ent["gen"].draw_dev, self.generator)
+        elif self._pyramid():
+            rows, cols = ent["hw"]
+            sizes = N.pyramid_level_sizes(rows, cols) if self.noise_type == "pyramid" else N.geowizard_pyramid_level_sizes(rows, cols)
+            N.set_pyramid_table(ent["table"], self.generator, sizes, rows, cols)
+
+    def _alive(self, ent):
+        alive = super()._alive(ent)
+        if self.loss == "diffusion":
+            return (alive, self.noise_scheduler, self.noise_scheduler.alphas_cumprod_on(ent["total"].device))
+        return alive
+
+    def _set_step_words(self, lr_scale):
+        super()._set_step_words(lr_scale)
+        if self.ema is not None:
+            self.ema.set_decay_word(self._ema_word)
+
+    def _update(self):
+        super()._update()
+        if self.ema is not None:
+            self.ema.step_at(self.optimizer.params, self._ema_word)
 
 
 def synthetic_batch(batch, height, width, device, seed=0, dtype=torch.float32):

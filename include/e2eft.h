@@ -37,7 +37,8 @@ extern "C" {
 #define E2EFT_VERSION 119 /* 0.1.1: backward entry points; 111: test-time ensembling, CLIP towers, sample preparation; 119 later gained one export
                              (e2eft_attn_f32split_supported) and one option (E2EFT_OPT_F32_SPLIT_ATTN) without a new number; so did the
                              workspace of e2eft_sumsq and the queries e2eft_sumsq_workspace_bytes / e2eft_ssi_loss_bwd_workspace_bytes
-                             (a stale binary is told apart by e2eft_build_id); so did e2eft_ddim_step and e2eft_randn_fill_at */
+                             (a stale binary is told apart by e2eft_build_id); so did e2eft_ddim_step and e2eft_randn_fill_at, and the
+                             capture-safe forms e2eft_pyramid_noise_at / _weighted_at, e2eft_pyramid_table_set, e2eft_randint_fill / _at, e2eft_ema_step_at */
 
 enum {
     E2EFT_OK = 0,
@@ -761,6 +762,9 @@ int e2eft_adamw_step_groups_at(int64_t n, float* param, const float* grad, float
 /* Exponential moving average of the parameters (diffusers `EMAModel.step`; GeoWizard/geowizard/training/train_depth_normal.py:352-353,785-786):
  * shadow[i] -= one_minus_decay * (shadow[i] - param[i]) in torch's operation order; both buffers fp32, 16-byte aligned (the flat buffers of FlatAdamW). */
 int e2eft_ema_step(int64_t n, float* shadow, const float* param, float one_minus_decay, void* stream);
+/* e2eft_ema_step with one_minus_decay read WHEN THE KERNEL RUNS from one fp32 device word (4-byte aligned, only read): a captured graph serves every decay of a
+ * warm-up.  The same kernel body: for the same fp32 value every element of shadow equals e2eft_ema_step's, the n & 3 tail included. */
+int e2eft_ema_step_at(int64_t n, float* shadow, const float* param, const float* one_minus_decay, void* stream);
 int e2eft_cast(int32_t dt_in, int32_t dt_out, int64_t n, float mul, int32_t accumulate, const void* x, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
@@ -812,6 +816,33 @@ int e2eft_pyramid_noise(int32_t dtype, int32_t batch, int32_t c, int32_t rows, i
 int e2eft_pyramid_noise_weighted(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, uint32_t draw, float discount,
                                  int32_t n_levels, const int32_t* level_sizes, const int64_t* timesteps, float timestep_div, void* y, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* The two entry points above with `draw` AND the level table read from DEVICE memory when the kernel runs — the capture-safe forms: one captured graph draws
+ * fresh noise over fresh level sizes on every replay.  table = int64[2 + 2 * E2EFT_PYRAMID_MAX_LEVELS] device words, 8-byte aligned, only read:
+ *   {draw (its low 32 bits), n_levels, rows_0, cols_0, ..., rows_9, cols_9}          filled by e2eft_pyramid_table_set
+ * discount, seed, the shapes, the workspace and (weighted) timesteps / timestep_div stay launch arguments; the weights (float)discount^i are formed on the
+ * host for all ten levels (they do not depend on the table).  The launch geometry depends on the output size alone.  One pass-1 body serves the by-value and
+ * the device-read forms: the same table values give the bits of e2eft_pyramid_noise / e2eft_pyramid_noise_weighted.
+ * CONTRACT of the table: levels never exceed the output size (1 <= rows_i <= rows, 1 <= cols_i <= cols), 0 <= n_levels <= E2EFT_PYRAMID_MAX_LEVELS.  The
+ * host cannot check device words, so the kernel clamps n_levels into [0, E2EFT_PYRAMID_MAX_LEVELS], level rows into [1, rows] and level cols into [1, cols]:
+ * a stale or foreign table changes the noise, but overflows neither the level arrays nor the 32-bit index arithmetic. */
+int e2eft_pyramid_noise_at(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, const int64_t* table,
+                           float discount, void* y, void* workspace, size_t workspace_bytes, void* stream);
+int e2eft_pyramid_noise_weighted_at(int32_t dtype, int32_t batch, int32_t c, int32_t rows, int32_t cols, int32_t ldy, uint64_t seed, const int64_t* table,
+                                    float discount, const int64_t* timesteps, float timestep_div, void* y, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+/* Fill a table of the `_at` entry points for an output of rows x cols: {draw, n_levels, level_sizes..., 1, 1 for the unused levels}.  level_sizes is a HOST
+ * array of n_levels (rows, cols) pairs read before the call returns.  Everything is checked before anything is launched: pointers, 0 <= n_levels <=
+ * E2EFT_PYRAMID_MAX_LEVELS, every size >= 1 and — the table's contract — no level larger than the output.  Then ONE one-thread launch with the 22 values as
+ * kernel arguments: no host-to-device copy, no staging buffer a later call could overwrite while an earlier replay is still queued, no synchronisation. */
+int e2eft_pyramid_table_set(int64_t* table, uint32_t draw, int32_t n_levels, const int32_t* level_sizes, int32_t rows, int32_t cols, void* stream);
+/* Integers of [0, high) from the generator's raw words (the trainer's `torch.randint(0, T, (b,)).repeat(2)`, train_depth_normal.py:651).  Element e < n takes
+ * word e & 3 of the counter of quad e >> 2 (the uint32 before any conversion to a uniform), and
+ *   t = ((uint64_t)word * (uint64_t)high) >> 32
+ * is written to out[r * n + e] for every r < repeat (int64, 8-byte aligned, n * repeat elements).  1 <= high <= 2^31 - 1, 1 <= n <= 2^31 - 1, repeat >= 1.
+ * The bias of a value against the uniform distribution is at most high / 2^32.  Bit parity with torch's stream is not a goal, as for the noise.
+ * e2eft_randint_fill_at reads `draw` from the device (the low 32 bits of an int64) as e2eft_randn_fill_at does: same value, same integers. */
+int e2eft_randint_fill(int64_t n, int32_t repeat, int64_t high, uint64_t seed, uint32_t draw, uint32_t slot, int64_t* out, void* stream);
+int e2eft_randint_fill_at(int64_t n, int32_t repeat, int64_t high, uint64_t seed, const int64_t* draw, uint32_t slot, int64_t* out, void* stream);
 /* x0[p, 0:c] = c_x * x_t[p, 0:c] + c_v * v[p, 0:c] in fp32 (train.py:509-518 by prediction_type; the caller folds 1 / scaling_factor, :528, into both
  * coefficients).  x_t is read in place from the noise channels of the UNet input (pixel stride ldxt), v and x0 have their own pixel strides. */
 int e2eft_latent_x0(int32_t dtype, int64_t pixels, int32_t c, int32_t ldxt, int32_t ldv, int32_t ldo, float c_x, float c_v, const void* xt,
